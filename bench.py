@@ -23,11 +23,18 @@ The flags of the reference's bin/deflate_bench.zig:101-114 are accepted too: -l 
 -z (zlib), -o FILE (write rank 0's first stream), -c (the same to stdout), plus an input file.
 
 Prints ONE JSON line (rank 0).  `value` = uncompressed MB/s (1e6 B/s) of the whole job.
-Extra keys: `roofline` (dominant kernel, HIP-event timed on the launch stream inside the
-timed region), `cpu_baseline` (the CPU oracle on a bounded sample, rank 0, N = 1),
-`cpu_baseline_all_cores`, `e2e_host` (host buffers in and out over PCIe), `decompress`
-(GPU inflate of the produced streams, same batch), `other_workloads` (all-zero, Silesia-like,
-1 MiB streams; smaller buffers, same run).
+`ms_per_step` = milliseconds of one timed step; `roofline` (dominant kernel, HIP-event timed on
+the launch stream inside the timed region).
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  Everything else is
+behind `--full`: `cpu_baseline` (the CPU oracle on a bounded sample, rank 0, N = 1; also a parity
+check of those chunks), `cpu_baseline_all_cores`, `e2e_host` (host buffers in and out over PCIe),
+`decompress` (GPU inflate of the produced streams, same batch, and the round trip check),
+`other_workloads` (all-zero, Silesia-like, 1 MiB streams; smaller buffers, same run), and the
+oracle samples of the other configurations.  Without `--full` those keys are null or absent.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (see
+dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -70,6 +77,11 @@ def parse():
     ap.add_argument("--no-decompress", action="store_true",
                     help="skip the inflate leg (one wave per stream: a single huge stream would take minutes)")
     ap.add_argument("--no-extras", action="store_true", help="skip other_workloads / e2e_host / all-core baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the inflate leg, the oracle checks, e2e_host and other_workloads "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step produced as DIR/<name>.npy (float32/float64, < 64 MB in all)")
     a = ap.parse_args()
     # the configuration's defaults
     d = {2: dict(workload="text", mode=6, container=0, chunk=CHUNK, bytes=1 << 30),
@@ -252,6 +264,43 @@ def roofline_of(prof, steps, algo_bytes, traffic=None):
             "kernels_ms_per_step": {k: round(v[0] / steps, 4) for k, v in sorted(prof.items())}}
 
 
+DUMP_SEED = 1951
+DUMP_ROWS = 128                # streams whose bytes bytes.npy holds
+DUMP_ROW_BYTES = 48_000_000    # bytes.npy's size at most (float32)
+DUMP_MAX_STREAMS = 1 << 20     # lengths.npy / status.npy: a seeded sample beyond this many streams
+
+
+def dump_outputs(out_dir, buf, off_np, lens, status):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files of at most ~61 MB together.
+    lengths.npy (float64), status.npy (float32): every stream's byte count and status (beyond DUMP_MAX_STREAMS streams a
+    seeded sample of them, named by length_index.npy).  bytes.npy (float32): one row per stream of a seeded sample
+    (bytes_index.npy), the bytes of the stream at its slot `off_np[i]` one value each, -1 past its end, cut at the row
+    width.  The picks depend only on the number of streams and their slots, never on what the step produced."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(lens)
+    off = np.asarray(off_np, dtype=np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    li = np.arange(n) if n <= DUMP_MAX_STREAMS else np.sort(rng.choice(n, DUMP_MAX_STREAMS, replace=False))
+    np.save(os.path.join(out_dir, "lengths.npy"), lens[li].astype(np.float64))
+    np.save(os.path.join(out_dir, "status.npy"), np.asarray(status)[li].astype(np.float32))
+    if n > DUMP_MAX_STREAMS:
+        np.save(os.path.join(out_dir, "length_index.npy"), li.astype(np.float64))
+    k = min(n, DUMP_ROWS)
+    if k == 0:
+        return
+    pick = np.sort(rng.choice(n, k, replace=False))
+    slots = (off[1:] - off[:-1])[pick]
+    width = int(max(1, min(slots.max(), DUMP_ROW_BYTES // (4 * k))))
+    rows = np.full((k, width), -1, dtype=np.float32)
+    for r, i in enumerate(pick):
+        m = max(0, min(int(lens[i]), int(slots[r]), width))
+        rows[r, :m] = buf[int(off[i]):int(off[i]) + m].cpu().numpy()
+    np.save(os.path.join(out_dir, "bytes.npy"), rows)
+    np.save(os.path.join(out_dir, "bytes_index.npy"), pick.astype(np.float64))
+
+
 def main():
     args = parse()
     maybe_spawn(args)
@@ -340,30 +389,34 @@ def run_compress(args, torch, dist, eng, world, rank, device):
         assert not gather.overflowed(), "a packed shard outgrew the calibrated gather width"
     ms_per_step = dt / args.steps * 1e3
     value = world * n_in * args.steps / dt / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, job.out, job.out_off_np, lens, job.status.cpu().numpy())
 
-    # ---- decompress leg: GPU inflate of the streams just produced (same batch) ----
-    comp, comp_off, _ = job.packed(lens)
+    # ---- decompress leg (--full): GPU inflate of the streams just produced (same batch) ----
+    no_decompress = args.no_decompress or not args.full
+    if args.full:
+        comp, comp_off, _ = job.packed(lens)
     dsteps = max(1, min(args.steps, 3))
     ddt, dprof, roundtrip_ok = float("nan"), {}, True
-    if not args.no_decompress:
+    if not no_decompress:
         inf = InflateJob(torch, eng, comp, comp_off, job.n_chunks, job.in_off, n_in, args.container)
         ddt, dprof = timed(torch, dist, eng, inf.step, dsteps, 1, world)
         roundtrip_ok = int(inf.dec_st.abs().sum().item()) == 0 and bool(torch.equal(inf.dec[:n_in], data))
         assert roundtrip_ok or args.no_verify, "inflate(deflate(x)) != x"  # --no-verify: kernel tuning experiments only
 
     nsw = None
-    if world > 1 and args.headline and not args.no_extras:
+    if world > 1 and args.headline and args.full and not args.no_extras:
         nsw = north_star_workloads(args, torch, dist, eng, world, rank, device)  # (every rank: its timing is a collective)
     result = None
     if rank == 0:
         algo_bytes = n_in + n_out  # read every input byte once, write every output byte once
         roofline = roofline_of(prof, args.steps, algo_bytes, lambda k: measured_traffic(args, n_in, k))
         cpu = cpu_all = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args, data, job.off_np, job.out, job.out_off_np, lens)
             if not args.no_extras:
                 cpu_all = cpu_baseline_all_cores(args, data, job.off_np)
-        elif not args.no_verify:
+        elif args.full and not args.no_verify:
             verify_sample(args, data, job.off_np, job.out, job.out_off_np, lens, 64)
         dd = max(dprof.items(), key=lambda kv: kv[1][0]) if dprof else ("none", (0.0, 1))
         mode_name = MODE_NAMES.get(args.mode, "level %d" % args.mode)
@@ -385,12 +438,12 @@ def run_compress(args, torch, dist, eng, world, rank, device):
             "roofline": roofline,
             "cpu_baseline": cpu,
             "cpu_baseline_all_cores": cpu_all,
-            "decompress": None if args.no_decompress else {
+            "decompress": None if no_decompress else {
                 "value": round(world * n_in * dsteps / ddt / 1e6, 2), "unit": "MB/s",
                 "ms_per_step": round(ddt / dsteps * 1e3, 3), "kernel": dd[0], "roundtrip_equal": roundtrip_ok,
                 "roofline_frac": round((n_in + n_out) / (ddt / dsteps) / 1e9 / HBM_PEAK_GBS, 5)},
         }
-        if args.headline and world == 1 and not args.no_extras:
+        if args.headline and world == 1 and args.full and not args.no_extras:
             result["e2e_host"] = e2e_host(torch, eng, data, job)
             result["other_workloads"] = other_workloads(args, torch, eng, device)
         elif nsw is not None:
@@ -402,7 +455,7 @@ def run_compress(args, torch, dist, eng, world, rank, device):
                     f.write(first)
             else:
                 args.stdout_stream = first  # -c: the stream owns stdout, the JSON line goes to stderr
-    if gather is not None:
+    if gather is not None and args.full:
         # the reassembled shard of this rank must be the packed streams themselves
         gather.run(job.out, job.out_off, job.out_len)
         torch.cuda.synchronize()
@@ -430,11 +483,13 @@ def run_config5(args, torch, dist, eng, world, rank, device):
     comp, comp_off, n_comp = mk.packed(lens)
     inf = InflateJob(torch, eng, comp, comp_off, m, mk.in_off, m * sz, 1)
     dt, prof = timed(torch, dist, eng, inf.step, args.steps, args.warmup, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, inf.dec, mk.off_np, inf.dec_len.cpu().numpy(), inf.dec_st.cpu().numpy())
     ok = int(inf.dec_st.abs().sum().item()) == 0 and bool(torch.equal(inf.dec[: m * sz], raw))
     assert ok, "gunzip output != input"
     if rank != 0:
         return None
-    if not args.no_verify:  # the members are what the reference would have written
+    if args.full and not args.no_verify:  # the members are what the reference would have written
         O = _oracle()
         for i in (0, m // 2, m - 1):
             a = int(comp_off[i].item())

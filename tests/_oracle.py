@@ -4,6 +4,8 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
 import this module.  The product package (flate_amd) never does.
 """
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -13,6 +15,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _ORACLE_DIR = os.path.join(_ROOT, "oracle")
 _SO = os.path.join(_ORACLE_DIR, "libflate_oracle.so")
 _PUFF = os.path.join(_ORACLE_DIR, "_ref", "libpuff.so")
+_PUFF_VERDICTS = os.path.join(_ROOT, "tests", "golden", "puff_verdicts.json")
 
 RAW, GZIP, ZLIB = 0, 1, 2
 STORE, HUFFMAN = 0, 1
@@ -169,8 +172,7 @@ def huffman_generate(freq, max_bits):
 def decompress(data, container=RAW, flags=0, cap=None):
     """returns (status_name, output_bytes, consumed)."""
     p, n, keep = _buf(data)
-    if cap is None:
-        cap = max(1 << 16, n * 1100 + 1024)
+    cap = _puff_cap(n, cap)
     out = np.empty(cap, dtype=np.uint8)
     olen = C.c_size_t(0)
     used = C.c_size_t(0)
@@ -257,10 +259,49 @@ def puff(data, cap=None):
         _puff.puff.argtypes = [C.c_void_p, C.POINTER(C.c_ulong), C.c_void_p, C.POINTER(C.c_ulong)]
         _puff.puff.restype = C.c_int
     p, n, keep = _buf(data)
-    if cap is None:
-        cap = max(1 << 16, n * 1100 + 1024)
+    cap = _puff_cap(n, cap)
     out = np.empty(cap, dtype=np.uint8)
     dl = C.c_ulong(cap)
     sl = C.c_ulong(n)
     rc = _puff.puff(out.ctypes.data, C.byref(dl), p, C.byref(sl))
     return rc, out[: dl.value].tobytes()
+
+
+# ---- puff.c's verdicts on every stream the tests hand it, stored in tests/golden/puff_verdicts.json ----
+# (oracle/_ref is built only where the reference tree is; tests/golden/make_puff_fixtures.py writes the file from it)
+_verdicts = None
+
+
+def digest(b):
+    return hashlib.sha256(bytes(b)).hexdigest()
+
+
+def _puff_cap(n, cap):
+    return max(1 << 16, n * 1100 + 1024) if cap is None else cap
+
+
+def puff_key(data, cap=None):
+    return "%s/%d" % (digest(data), _puff_cap(len(data), cap))
+
+
+def stored_puff_verdicts():
+    global _verdicts
+    if _verdicts is None:
+        with open(_PUFF_VERDICTS) as f:
+            _verdicts = json.load(f)
+    return _verdicts
+
+
+def puff_verdict(data, cap=None):
+    """puff.c on `data`: (rc, sha-256 of its output when rc == 0, else None).  From the library when oracle/_ref holds it
+    (and then equal to the stored verdict, if there is one), else the stored verdict."""
+    data = bytes(data)
+    stored = stored_puff_verdicts().get(puff_key(data, cap))
+    if puff_available():
+        rc, out = puff(data, cap)
+        got = (rc, digest(out) if rc == 0 else None)
+        assert stored is None or tuple(stored) == got, "puff.c and tests/golden/puff_verdicts.json disagree: %s" % puff_key(data, cap)
+        return got
+    assert stored is not None, ("no stored puff.c verdict for stream %s: tests/golden/make_puff_fixtures.py writes them"
+                                % puff_key(data, cap))
+    return tuple(stored)

@@ -4,9 +4,9 @@
 R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-rXX}
 O=$R/gpurun_out/${TAG}_levels.txt
-echo "# for l in 4..9: python bench.py -l \$l --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-decompress ; then -g (gzip, level 6) and -z -l 4" > $O
+echo "# for l in 4..9: python bench.py -l \$l --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-decompress ; then -g (gzip, level 6) and -z -l 4" > $O
 run() {
-  python $R/bench.py "$@" --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-decompress 2>/dev/null | python -c "
+  python $R/bench.py "$@" --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-decompress 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); print('$*', d['value'], d['ms_per_step'], d['roofline']['kernels_ms_per_step'])" >> $O
 }

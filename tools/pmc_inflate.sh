@@ -4,7 +4,7 @@
 # with the decompress leg; per-kernel sums of k_inflate land in gpurun_out/<tag>_inflate_pmc.json, the command first.
 R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-rXX}; shift
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-extras --no-verify $*"
+ARGS="--full --steps 1 --warmup 0 --no-cpu-baseline --no-extras --no-verify $*"
 cd /tmp && export TMPDIR=/tmp
 P1="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_INSTS_SMEM"
 P2="SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES"

@@ -13,10 +13,10 @@ run() {  # name, bench args...
   { echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py $*"; grep -E '^"?Name|^"?(void )?k_[a-z_0-9]+[<(]' "$f" | head -40; } > $R/gpurun_out/${TAG}_${name}_kernel_stats.csv
   tail -1 $R/gpurun_out/${TAG}_${name}_bench.json | cut -c1-400
 }
-run config2 --steps 5 --warmup 2 --no-cpu-baseline --no-extras
-run config3 --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-extras
-run config4 --config 4 --steps 5 --warmup 2 --no-cpu-baseline --no-extras
-run config5 --config 5 --steps 3 --warmup 1 --no-cpu-baseline --no-extras
+run config2 --steps 5 --warmup 2 --no-cpu-baseline --no-extras --full
+run config3 --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --full
+run config4 --config 4 --steps 5 --warmup 2 --no-cpu-baseline --no-extras --full
+run config5 --config 5 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --full
 # one long stream through the inflater (spans): the kernels of tools/span_probe.py
 rm -rf /tmp/prof_onestream
 rocprofv3 --kernel-trace --stats -d /tmp/prof_onestream -o p --output-format csv -- python $R/tools/span_probe.py 170 6 1 text > $R/gpurun_out/${TAG}_onestream_probe.txt 2> /tmp/prof_onestream.err

@@ -5,7 +5,7 @@
 R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-rXX}
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-extras --no-verify"
+ARGS="--full --steps 1 --warmup 0 --no-cpu-baseline --no-extras --no-verify"
 rm -rf /tmp/tf /tmp/tw
 rocprofv3 --pmc FETCH_SIZE -d /tmp/tf -o p --output-format csv -- python $R/bench.py $ARGS > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE -d /tmp/tw -o p --output-format csv -- python $R/bench.py $ARGS > /dev/null 2>&1

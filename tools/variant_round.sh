@@ -8,7 +8,7 @@ names="$@"
 [ -z "$names" ] && names=$(ls flate_amd/lib/var/lib_*.so | xargs -n1 basename | sed 's/^lib_//; s/\.so$//' | grep -v '^prof')
 for n in $names; do
   f=$PWD/flate_amd/lib/var/lib_$n.so
-  FLATE_HIP_LIB=$f python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras ${BENCH_ARGS} 2>/dev/null | python -c "
+  FLATE_HIP_LIB=$f python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras ${BENCH_ARGS} 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 print('$n', d['value'], 'roundtrip', d['decompress']['roundtrip_equal'] if d.get('decompress') else None, {k: round(v, 3) for k, v in d['roofline']['kernels_ms_per_step'].items()})" >> $out 2>&1
