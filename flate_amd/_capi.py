@@ -17,6 +17,8 @@ MAX_LZ_CHUNK = 65535
 INFLATE_STRICT_Q6 = 1
 DEFLATE_REPAIR_Q1 = 1          # flate_hip_set_flags
 ST_REFERENCE_Q1_STREAM = 102   # compress status: the reference's bytes, which do not inflate to the input (include/flate_hip.h)
+ST_NEED_INPUT = 104            # inflater feed: all input absorbed, member not finished
+ST_NEED_OUTPUT = 105           # inflater feed: the output slot is full
 
 # every symbol include/flate_hip.h declares
 SYMBOLS = [
@@ -29,6 +31,7 @@ SYMBOLS = [
     "flate_hip_compress_batch_sharded", "flate_hip_decompress_batch_sharded",
     "flate_hip_plan_compress", "flate_hip_compress_planned", "flate_hip_plan_destroy",
     "flate_hip_checksum", "flate_hip_checksum_combine", "flate_hip_debug_reload_env",
+    "flate_hip_inflater_create", "flate_hip_inflater_destroy", "flate_hip_inflater_reset", "flate_hip_inflater_feed",
 ]
 
 
@@ -121,6 +124,14 @@ def lib():
     L.flate_hip_checksum.restype = C.c_int
     L.flate_hip_checksum_combine.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]
     L.flate_hip_checksum_combine.restype = C.c_uint32
+    L.flate_hip_inflater_create.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.flate_hip_inflater_create.restype = C.c_int
+    L.flate_hip_inflater_destroy.argtypes = [vp, vp]
+    L.flate_hip_inflater_destroy.restype = C.c_int
+    L.flate_hip_inflater_reset.argtypes = [vp, vp, vp, C.c_uint32]
+    L.flate_hip_inflater_reset.restype = C.c_int
+    L.flate_hip_inflater_feed.argtypes = [vp, vp, vp, u64p, vp, vp, u64p, u64p, u64p, i32p, C.c_int]
+    L.flate_hip_inflater_feed.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.flate_hip_debug_tokens.restype = C.c_int64
     _lib = L

@@ -348,6 +348,107 @@ class _Decompressor:
         self._out, self._rp, self._ended = None, 0, False
 
 
+class _PieceDecompressor:
+    """Inflate (inflate.zig:43-355) in bounded memory: a one-stream inflater on the device (flate_hip_inflater_*) is fed
+    the reader `piece` bytes at a time and output is handed out as it is decoded, at most 64 KiB a next()
+    (inflate.zig:322-336).  A piece is read only when everything read before has been absorbed, so the reader is never
+    more than one piece ahead of the decoder; what the current member does not absorb belongs to the next one (reset()).
+    Memory: the piece, one 64 KiB output slot and the device-side state, whatever the stream's length."""
+
+    CHUNK = 65536
+
+    def __init__(self, container, reader, engine=None, flags=0, piece=1 << 20):
+        if int(piece) < 1:
+            raise ValueError("piece must be at least 1 byte")
+        self._container, self._piece = container, int(piece)
+        self._eng = engine or default_engine()
+        self._slot = min(max(self.CHUNK, 4 * self._piece), 64 << 20)  # output of one feed (handed out 64 KiB at a time)
+        self._inf = self._eng.inflater(1, container, flags)
+        self._set_input(reader)
+        self._clear()
+
+    def _set_input(self, reader):
+        if isinstance(reader, (bytes, bytearray, memoryview)):
+            reader = io.BytesIO(bytes(reader))
+        self._rd = reader
+        self._in = b""    # read from the reader and not absorbed yet
+        self._eof = False
+
+    def _clear(self):
+        self._out = bytearray()  # decoded, not handed out yet
+        self._done = False       # the member is complete (footer checked)
+        self._ended = False      # ... and everything of it has been handed out
+
+    def _step(self):
+        """one feed: more output, or the end of the member"""
+        if not self._in and not self._eof:
+            self._in = bytes(self._rd.read(self._piece) or b"")
+            self._eof = not self._in
+        outs, st, used = self._inf.feed([self._in], final=[self._eof], caps=[self._slot])
+        self._in = self._in[used[0]:]
+        self._out += outs[0]
+        if st[0] == 0:
+            self._done = True
+        elif st[0] not in (_capi.ST_NEED_INPUT, _capi.ST_NEED_OUTPUT):
+            raise_for_status(st[0])
+
+    def get(self, limit=0):  # inflate.zig:326-336
+        want = min(limit, self.CHUNK) if limit else self.CHUNK
+        while not self._out and not self._done:
+            self._step()
+        buf = bytes(self._out[:want])
+        del self._out[:len(buf)]
+        if not buf:
+            self._ended = True
+        return buf
+
+    def next(self):  # inflate.zig:315-319
+        buf = self.get(0)
+        return buf if buf else None
+
+    def read(self, n=-1):  # inflate.zig:343-347 (n < 0: read to the end, Python convention)
+        if n is None or n < 0:
+            parts = []
+            while True:
+                buf = self.next()
+                if buf is None:
+                    return b"".join(parts)
+                parts.append(buf)
+        return self.get(n) if n else b""
+
+    def reader(self):  # inflate.zig:349-351
+        return self
+
+    def decompress(self, writer):  # inflate.zig:292-296
+        while True:
+            buf = self.next()
+            if buf is None:
+                break
+            writer.write(buf)
+
+    def reset(self):  # inflate.zig:301-309: next stream of the same reader
+        if not self._ended:
+            raise InvalidState("reset() before the end of the stream")
+        self._inf.reset([0])
+        self._clear()
+
+    def more_input(self):
+        """True when input is left after the stream just decoded (a further concatenated member).  Meant for the end of
+        a member, after next() has returned None: called earlier, it decodes the rest of the current member first and
+        keeps that output buffered for next() -- host memory of the member's remaining output, not O(piece + slot)."""
+        while not self._done:
+            self._step()
+        if not self._in and not self._eof:
+            self._in = bytes(self._rd.read(self._piece) or b"")
+            self._eof = not self._in
+        return bool(self._in)
+
+    def set_reader(self, new_reader):  # inflate.zig:283-288
+        self._set_input(new_reader)
+        self._inf.reset([0])
+        self._clear()
+
+
 class _Simple:
     """huffman / store namespaces (flate.zig:44-71)."""
 
@@ -388,8 +489,12 @@ class ContainerModule:
     def decompress(self, reader, writer, engine=None):
         self.decompressor(reader, engine).decompress(writer)
 
-    def decompressor(self, reader, engine=None):
-        return _Decompressor(self._container, reader, engine)
+    def decompressor(self, reader, engine=None, *, piece=None):
+        """piece=None: the whole-stream decompressor.  piece=N: bounded memory -- the reader is read N bytes at a time
+        and decoded by a resumable inflater as it arrives (_PieceDecompressor)."""
+        if piece is None:
+            return _Decompressor(self._container, reader, engine)
+        return _PieceDecompressor(self._container, reader, engine, piece=piece)
 
     Decompressor = decompressor
 

@@ -51,13 +51,14 @@ enum KernelId {
     K_SPAN_SCAN,
     K_INFLATE_SPAN,
     K_GATHER,
+    K_INFLATER,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
                                            "k_lz_chain", "k_lz_parse", "k_lz_links", "k_lz_walk", "k_lz_emit",
                                            "k_st_parse", "k_st_emit", "k_plan",
                                            "k_offsets",  "k_encode",    "k_inflate",  "k_inflate_par", "k_span_scan", "k_inflate_span",
-                                           "k_gather"};
+                                           "k_gather", "k_inflater"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -1325,6 +1326,8 @@ const char* flate_hip_status_name(int s) {
         case 100: return "OutputTooSmall";
         case 101: return "ChunkTooLarge";
         case 102: return "ReferenceQ1Stream";
+        case 104: return "NeedInput";
+        case 105: return "NeedOutput";
         default: return "Unknown";
     }
 }
@@ -2671,6 +2674,165 @@ uint32_t flate_hip_checksum_combine(int container, uint32_t a, uint32_t b, uint6
     const uint32_t an = (a1 + a2 + 65521u - 1u) % 65521u;
     const uint32_t bn = (uint32_t)(((uint64_t)b1 + b2 + (uint64_t)rem * ((a1 + 65521u - 1u) % 65521u)) % 65521u);
     return an | (bn << 16);
+}
+
+}  // extern "C"
+
+// ---- resumable inflate (kernels_inflate.h, k_inflater) ----
+struct flate_hip_inflater {
+    uint32_t n = 0;
+    int container = 0, flags = 0;
+    void* sess = nullptr;  // FL_RS_STRIDE bytes per stream: state, carry, input window, history, output window
+    // host-memory feeds: the pieces, offsets and slots on the device
+    DevBuf in, in_off, fin, out, out_off, out_len, consumed, status, which;
+    std::vector<uint8_t> host_out;  // host-memory feeds of many streams: the slots on their way to the caller
+};
+
+namespace {
+int inflater_reset_all(flate_hip_ctx* h, flate_hip_inflater* s, const uint32_t* d_which, uint32_t n) {
+    if (n == 0) return FLATE_HIP_OK;
+    hipLaunchKernelGGL(k_inflater_reset, dim3((n + 255) / 256), dim3(256), 0, h->stream, (uint8_t*)s->sess, d_which, n, s->n,
+                       s->container);
+    HIP_OK(h, hipGetLastError());
+    return FLATE_HIP_OK;
+}
+int inflater_buf(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
+    if (bytes <= b.cap) return FLATE_HIP_OK;
+    (void)hipStreamSynchronize(h->stream);
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    const size_t want = bytes + bytes / 8 + 256;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        b.p = nullptr;
+        h->last_error = "hipMalloc(" + std::to_string(want) + ") for an inflater feed failed";
+        return FLATE_HIP_E_ALLOC;
+    }
+    b.cap = want;
+    return FLATE_HIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int flate_hip_inflater_create(flate_hip_handle h, uint32_t n_streams, int container, int flags, flate_hip_inflater_t* out) {
+    if (!h || !out || n_streams == 0 || container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
+    *out = nullptr;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    flate_hip_inflater* s = new flate_hip_inflater();
+    s->n = n_streams;
+    s->container = container;
+    s->flags = flags & FLATE_HIP_INFLATE_STRICT_Q6;
+    if (hipMalloc(&s->sess, (size_t)n_streams * FL_RS_STRIDE) != hipSuccess) {
+        h->last_error = "hipMalloc of the inflater's state (" + std::to_string((size_t)n_streams * FL_RS_STRIDE) + " bytes) failed";
+        delete s;
+        return FLATE_HIP_E_ALLOC;
+    }
+    int rc = inflater_reset_all(h, s, nullptr, n_streams);
+    if (rc == FLATE_HIP_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = FLATE_HIP_E_LAUNCH;
+    if (rc) {
+        (void)hipFree(s->sess);
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_inflater_destroy(flate_hip_handle h, flate_hip_inflater_t s) {
+    if (!h || !s) return FLATE_HIP_E_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    for (DevBuf* b : {&s->in, &s->in_off, &s->fin, &s->out, &s->out_off, &s->out_len, &s->consumed, &s->status, &s->which})
+        if (b->p) (void)hipFree(b->p);
+    (void)hipFree(s->sess);
+    delete s;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_inflater_reset(flate_hip_handle h, flate_hip_inflater_t s, const uint32_t* which, uint32_t n_which) {
+    if (!h || !s || (n_which && !which)) return FLATE_HIP_E_INVALID_ARG;
+    for (uint32_t k = 0; k < n_which; k++)
+        if (which[k] >= s->n) return FLATE_HIP_E_INVALID_ARG;
+    if (n_which == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    int rc = inflater_buf(h, s->which, sizeof(uint32_t) * n_which);
+    if (rc) return rc;
+    // (a pageable source: the copy has been taken when hipMemcpyAsync returns, the kernel is ordered behind it)
+    HIP_OK(h, hipMemcpyAsync(s->which.p, which, sizeof(uint32_t) * n_which, hipMemcpyHostToDevice, h->stream));
+    if ((rc = inflater_reset_all(h, s, (const uint32_t*)s->which.p, n_which))) return rc;
+    if (h->sync) HIP_OK(h, hipStreamSynchronize(h->stream));
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const uint8_t* in, const uint64_t* in_off,
+                            const uint8_t* final_, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                            uint64_t* consumed, int32_t* status, int memkind) {
+    if (!h || !s || !in_off || !final_ || !out_off || !out_len || !consumed || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    const uint32_t n = s->n;
+    if (memkind == FLATE_HIP_MEM_DEVICE) {  // enqueue only: the kernel reads the offsets itself
+        ProfScope ps(h, K_INFLATER);
+        hipLaunchKernelGGL(k_inflater, dim3(n), dim3(64), 0, st, in, in_off, final_, out, out_off, out_len, consumed, status,
+                           (uint8_t*)s->sess, s->container, s->flags, h->crc);
+        HIP_OK(h, hipGetLastError());
+        if (h->sync) HIP_OK(h, hipStreamSynchronize(st));
+        return FLATE_HIP_OK;
+    }
+    // host memory: check the slots, stage pieces and offsets, run, bring the produced bytes home
+    for (uint32_t i = 0; i < n; i++) {
+        if (in_off[i + 1] < in_off[i] || out_off[i + 1] < out_off[i]) return FLATE_HIP_E_INVALID_ARG;
+        const uint64_t slot = out_off[i + 1] - out_off[i];
+        const bool skipped = in_off[i + 1] == in_off[i] && !final_[i] && slot == 0;
+        if (!skipped && slot > 0 && slot < 258) return FLATE_HIP_E_INVALID_ARG;
+    }
+    const uint64_t in_lo = in_off[0], in_n = in_off[n] - in_lo, out_lo = out_off[0], out_n = out_off[n] - out_lo;
+    std::vector<uint64_t> hin(n + 1), hout(n + 1);
+    for (uint32_t i = 0; i <= n; i++) {
+        hin[i] = in_off[i] - in_lo;
+        hout[i] = out_off[i] - out_lo;
+    }
+    int rc;
+    if ((rc = inflater_buf(h, s->in, in_n + 16)) || (rc = inflater_buf(h, s->out, out_n + 16)) ||
+        (rc = inflater_buf(h, s->in_off, 8 * (n + 1))) || (rc = inflater_buf(h, s->out_off, 8 * (n + 1))) ||
+        (rc = inflater_buf(h, s->fin, n)) || (rc = inflater_buf(h, s->out_len, 8 * n)) ||
+        (rc = inflater_buf(h, s->consumed, 8 * n)) || (rc = inflater_buf(h, s->status, 4 * n)))
+        return rc;
+    if (in_n) HIP_OK(h, hipMemcpyAsync(s->in.p, in + in_lo, in_n, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(s->in_off.p, hin.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(s->out_off.p, hout.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(s->fin.p, final_, n, hipMemcpyHostToDevice, st));
+    {
+        ProfScope ps(h, K_INFLATER);
+        hipLaunchKernelGGL(k_inflater, dim3(n), dim3(64), 0, st, (const uint8_t*)s->in.p, (const uint64_t*)s->in_off.p,
+                           (const uint8_t*)s->fin.p, (uint8_t*)s->out.p, (const uint64_t*)s->out_off.p,
+                           (uint64_t*)s->out_len.p, (uint64_t*)s->consumed.p, (int32_t*)s->status.p, (uint8_t*)s->sess,
+                           s->container, s->flags, h->crc);
+        HIP_OK(h, hipGetLastError());
+    }
+    HIP_OK(h, hipMemcpyAsync(out_len, s->out_len.p, 8 * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(consumed, s->consumed.p, 8 * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(status, s->status.p, 4 * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipStreamSynchronize(st));
+    // only the produced bytes reach the caller's slots (what lies beyond out_len[i] stays as it was): a few streams
+    // by a copy each, many by one copy of the slots to the host and a copy of each stream's bytes from there
+    if (n > 16) {
+        if (out_n) {
+            s->host_out.resize(out_n);
+            HIP_OK(h, hipMemcpyAsync(s->host_out.data(), s->out.p, out_n, hipMemcpyDeviceToHost, st));
+            HIP_OK(h, hipStreamSynchronize(st));
+            for (uint32_t i = 0; i < n; i++)
+                if (out_len[i]) std::memcpy(out + out_off[i], s->host_out.data() + hout[i], out_len[i]);
+        }
+    } else {
+        for (uint32_t i = 0; i < n; i++)
+            if (out_len[i])
+                HIP_OK(h, hipMemcpyAsync(out + out_off[i], (uint8_t*)s->out.p + hout[i], out_len[i], hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(h, hipStreamSynchronize(st));
+    return FLATE_HIP_OK;
 }
 
 }  // extern "C"

@@ -1193,3 +1193,568 @@ __global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1))
         if (consumed) consumed[c] = fl_br_consumed(r);
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Resumable inflate (flate_hip_inflater_*): the decoder above, stopped and restarted at safe points, with its state in
+// device memory between calls (the reference's Decompressor keeps the same things in its ring and bit reader,
+// inflate.zig:43-355).  One wave per stream, the small LDS ring and the same workspace as k_inflate<2048>; the device
+// functions above are called as they are.
+//
+// Per stream, one block of FL_RS_STRIDE bytes of session memory:
+//   [0, 512)         fl_rs_state: phase, counters, running checksum, the current dynamic block's code lengths
+//   stage            FL_RS_CARRY bytes of carry (right-aligned) followed by a window of FL_RS_WIN_IN bytes of the piece:
+//                    the decoder reads carry ++ window as one buffer
+//   hist             32 KiB: the last min(total, 32768) output bytes, right-aligned, followed by
+//   outwin           FL_RS_WOUT bytes where a window of output is decoded (far matches read hist ++ outwin as one buffer)
+//
+// A unit (a literal or a match with its extra bits, BFINAL/BTYPE, a dynamic block header, a stored header, a byte of a
+// stored body, a byte of the container's header -- XLEN whole --, a 32-bit word of its footer) is decoded only when it
+// finishes with the bits present: a symbol is decoded on a copy of the bit reader, which is kept only when the unit did
+// not run past the end of what is staged.  A stream stops at the start of the unit it cannot finish; the bytes from there on go to the carry.
+#define FL_RS_CARRY 1024u
+#define FL_RS_WIN_IN 8192u
+#define FL_RS_WOUT 32768u
+#define FL_RS_HIST 32768u
+#define FL_RS_STATE 512u
+#define FL_RS_STRIDE (FL_RS_STATE + FL_RS_CARRY + FL_RS_WIN_IN + FL_RS_HIST + FL_RS_WOUT)
+#define FL_RS_DYN_MAX_BITS 4608  // a dynamic block header is at most 14 + 19 * 3 + 316 * 14 bits
+#define FL_RS_NEED_INPUT 104
+#define FL_RS_NEED_OUTPUT 105
+
+enum { FL_RS_HEADER = 0, FL_RS_BLOCK, FL_RS_SHDR, FL_RS_STORED, FL_RS_FIXED, FL_RS_DHDR, FL_RS_DYNAMIC, FL_RS_FOOTER,
+       FL_RS_DONE, FL_RS_ERROR };
+
+struct fl_rs_state {
+    uint64_t total;       // output bytes of the member so far
+    uint64_t foot;        // footer bytes read so far (little-endian)
+    uint32_t phase;       // FL_RS_*
+    uint32_t sub;         // byte of the container header / footer
+    uint32_t bfinal;      // BFINAL of the current block
+    uint32_t stored_left; // bytes left in the current stored block
+    uint32_t check;       // CRC-32 / Adler-32 of the output so far
+    int32_t status;       // the error, once phase == FL_RS_ERROR
+    uint32_t carry_len;   // bytes in the carry (stage[FL_RS_CARRY - carry_len, FL_RS_CARRY))
+    uint32_t carry_bit;   // bits of the carry's first byte already consumed
+    uint32_t hflags;      // gzip FLG | 0x100 when the fixed header was wrong
+    uint32_t hcount;      // gzip FEXTRA bytes left
+    uint32_t pad[6];
+    uint8_t lens[320];    // code lengths of the current dynamic block (lens layout of fl_inflate_ws16)
+};
+static_assert(sizeof(fl_rs_state) <= FL_RS_STATE, "inflater state");
+
+enum { FL_RS_STOP_IN = 1, FL_RS_STOP_OUT, FL_RS_STOP_FOOT, FL_RS_STOP_END };
+
+// one byte of the stream (the container's header and footer are parsed byte by byte)
+__device__ __forceinline__ bool fl_rs_byte(fl_bitr& r, uint32_t& v) {
+    if (r.left < 8) return false;
+    fl_br_read(r, 8, v);
+    return true;
+}
+
+// inflate.zig:104-121 for ONE symbol (fl_inf_fixed's loop body); -1 at the end of the block
+__device__ __forceinline__ int fl_rs_fixed_symbol(fl_bitr& r, fl_inf_out& o, uint32_t lane) {
+    FL_TRY(fl_br_fill(r, 9));
+    const uint32_t code7 = fl_rev_bits(fl_br_peek(r, 7), 7);
+    FL_TRY(fl_br_shift(r, 7));
+    uint32_t code;
+    if (code7 <= 0x17) {
+        code = code7 + 256;
+    } else if (code7 <= 0x5f) {
+        const uint32_t e = fl_br_peek(r, 1);
+        FL_TRY(fl_br_shift(r, 1));
+        code = (code7 << 1) + e - 0x30;
+    } else if (code7 <= 0x63) {
+        const uint32_t e = fl_br_peek(r, 1);
+        FL_TRY(fl_br_shift(r, 1));
+        code = ((code7 - 0x60) << 1) + e + 280;
+    } else {
+        const uint32_t e = fl_rev_bits(fl_br_peek(r, 2), 2);
+        FL_TRY(fl_br_shift(r, 2));
+        code = ((code7 - 0x64) << 2) + e + 144;
+    }
+    if (code <= 255) return fl_inf_literal(o, code, lane);
+    if (code == 256) return -1;
+    if (code > 285) return 7;
+    FL_TRY(fl_br_fill(r, 5 + 5 + 13));
+    uint32_t length, distance;
+    FL_TRY(fl_inf_length(r, code - 257, length));
+    const uint32_t dcode = fl_rev_bits(fl_br_peek(r, 5), 5);
+    FL_TRY(fl_br_shift(r, 5));
+    FL_TRY(fl_inf_distance(r, dcode, distance));
+    return fl_inf_match(o, length, distance, lane);
+}
+
+// the decoders of the current dynamic block again, from the code lengths the header left (tables are not saved)
+__device__ __forceinline__ void fl_rs_rebuild(FL_LDS fl_inflate_ws16* ws, const fl_rs_state* S, uint32_t lane) {
+    fl_wave_lds_sync();
+    for (uint32_t i = lane; i < 80; i += 64) ((FL_LDS uint32_t*)ws->lens)[i] = ((const uint32_t*)S->lens)[i];
+    fl_wave_lds_sync();
+    fl_hdec_generate(&ws->lit, ws->lens, ws->offs, 286, 286, 15, lane);
+    fl_hdec_generate(&ws->dst, ws->lens + 288, ws->offs, 30, 30, 15, lane);
+    fl_hdec_build_lut<false>(&ws->lit, ws->lit_lut, FL_INF_LIT_BITS, lane);
+    fl_hdec_build_lut<true>(&ws->dst, ws->dst_lut, FL_INF16_DST_BITS, lane);
+    for (uint32_t i = lane; i < 80; i += 64) ((FL_LDS uint32_t*)ws->lens)[i] = 0;  // the fast rounds' owner array
+    fl_wave_lds_sync();
+}
+
+// wave-uniform decoder state between two safe points
+struct fl_rs_regs {
+    uint64_t total, foot;
+    uint32_t phase, sub, bfinal, stored_left, hflags, hcount, check;
+    int32_t status;
+};
+
+// Decode from the current safe point until a stop: FL_RS_STOP_IN (the next unit does not finish with the bits staged, and
+// more may follow), FL_RS_STOP_OUT (the output window is full), FL_RS_STOP_FOOT (the last block ended: the caller folds
+// the checksum before the footer is read), FL_RS_STOP_END (the member is complete, or an error).  `safe_left` is r.left at
+// the start of the unit the decoder stopped in front of.  fin: no input follows what is staged (the reference's
+// EndOfStream model applies).
+__device__ __forceinline__ int fl_rs_run(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, fl_inf_out& o, fl_rs_regs& s, fl_rs_state* S,
+                                      bool fin, int container, int flags, uint32_t lane, int64_t& safe_left) {
+#define FL_RS_ERR(code)                          \
+    do {                                         \
+        s.status = (int32_t)(code);              \
+        s.phase = FL_RS_ERROR;                   \
+        safe_left = r.left;                      \
+        return FL_RS_STOP_END;                   \
+    } while (0)
+#define FL_RS_SHORT()                            \
+    do {                                         \
+        safe_left = r.left;                      \
+        if (fin) FL_RS_ERR(1);                   \
+        return FL_RS_STOP_IN;                    \
+    } while (0)
+    for (;;) {
+        switch (s.phase) {
+            case FL_RS_HEADER: {  // container.zig:119-152, a byte at a time (XLEN, read as one 16-bit field there, is one unit)
+                if (container == 1) {
+                    for (;;) {
+                        if (s.sub == 10 && !(s.hflags & 0x04)) s.sub = 13;
+                        if (s.sub == 10) {
+                            if (r.left < 16) FL_RS_SHORT();
+                            uint32_t xl;
+                            fl_br_read(r, 16, xl);
+                            s.hcount = fl_uni(xl);
+                            s.sub = 12;
+                        }
+                        if (s.sub == 12 && s.hcount == 0) s.sub = 13;
+                        if (s.sub == 13 && !(s.hflags & 0x08)) s.sub = 14;
+                        if (s.sub == 14 && !(s.hflags & 0x10)) s.sub = 15;
+                        if (s.sub == 15 && !(s.hflags & 0x02)) s.sub = 17;
+                        if (s.sub == 17) break;
+                        uint32_t v;
+                        if (!fl_rs_byte(r, v)) FL_RS_SHORT();
+                        v = fl_uni(v);
+                        if (s.sub < 10) {
+                            if ((s.sub == 0 && v != 0x1f) || (s.sub == 1 && v != 0x8b) || (s.sub == 2 && v != 0x08)) s.hflags |= 0x100;
+                            if (s.sub == 3) s.hflags |= v;
+                            s.sub++;
+                            if (s.sub == 10 && (s.hflags & 0x100)) FL_RS_ERR(2);
+                        } else if (s.sub == 12) {
+                            s.hcount--;
+                        } else if (s.sub == 13 || s.sub == 14) {
+                            if (v == 0) s.sub++;
+                        } else {  // FHCRC
+                            s.sub++;
+                        }
+                    }
+                } else if (container == 2) {
+                    while (s.sub < 2) {
+                        uint32_t v;
+                        if (!fl_rs_byte(r, v)) FL_RS_SHORT();
+                        v = fl_uni(v);
+                        if (s.sub == 0) s.hflags = v;
+                        s.sub++;
+                    }
+                    if ((s.hflags & 15) != 8 || (s.hflags >> 4) > 7) FL_RS_ERR(3);
+                }
+                s.sub = 0;
+                s.phase = FL_RS_BLOCK;
+                break;
+            }
+            case FL_RS_BLOCK: {  // inflate.zig:251-280
+                if (r.left < 3) FL_RS_SHORT();
+                uint32_t bfinal, btype;
+                fl_br_read(r, 1, bfinal);
+                fl_br_read(r, 2, btype);
+                s.bfinal = fl_uni(bfinal);
+                btype = fl_uni(btype);
+                if (btype == 0) {
+                    s.phase = FL_RS_SHDR;
+                } else if (btype == 1) {
+                    s.phase = FL_RS_FIXED;
+                } else if (btype == 2) {
+                    s.phase = FL_RS_DHDR;
+                } else {
+                    FL_RS_ERR(12);
+                }
+                break;
+            }
+            case FL_RS_SHDR: {  // inflate.zig:89-97
+                if (!fin && r.left < (int64_t)((r.left & 7) + 32)) FL_RS_SHORT();
+                // (no input follows: EndOfStream where the one-shot path's reads stop)
+                fl_br_align(r);
+                uint32_t len, nlen;
+                if (r.left < 16) FL_RS_SHORT();
+                fl_br_read(r, 16, len);
+                if (r.left < 16) FL_RS_SHORT();
+                fl_br_read(r, 16, nlen);
+                len = fl_uni(len);
+                nlen = fl_uni(nlen);
+                if (len != ((~nlen) & 0xffff)) FL_RS_ERR(13);
+                s.stored_left = len;
+                s.phase = FL_RS_STORED;
+                break;
+            }
+            case FL_RS_STORED: {  // inflate.zig:98-101, a byte at a time
+                if (s.stored_left) {
+                    const uint64_t avail = (uint64_t)r.left >> 3;
+                    // (no input follows: as the one-shot path, the whole block or EndOfStream)
+                    if (fin && (uint64_t)s.stored_left > avail) FL_RS_ERR(1);
+                    uint32_t n = (uint32_t)min((uint64_t)s.stored_left, min(avail, o.cap - o.wp));
+                    n = fl_uni(n);
+                    if (n == 0) {
+                        safe_left = r.left;
+                        if (avail == 0) FL_RS_SHORT();
+                        return FL_RS_STOP_OUT;
+                    }
+                    const uint32_t src_off = (uint32_t)fl_br_consumed(r);
+                    const uint8_t* src = r.data + src_off;
+                    fl_inf_flush(o, o.wp, lane);
+                    for (uint32_t i = lane; i < n; i += 64) o.out[o.wp + i] = src[i];
+                    const uint32_t tail = n < o.rmask + 1 ? n : o.rmask + 1;
+                    fl_lds_order();
+                    for (uint32_t i = lane; i < tail; i += 64)
+                        o.ring[((uint32_t)(o.wp + n - tail + i) + o.bias) & o.rmask] = src[n - tail + i];
+                    fl_lds_order();
+                    o.wp += n;
+                    o.flushed = o.wp;
+                    r.left -= (int64_t)n * 8;
+                    fl_br_seek(r, src_off + n);
+                    s.stored_left -= n;
+                    if (s.stored_left) break;
+                }
+                s.phase = s.bfinal ? FL_RS_FOOTER : FL_RS_BLOCK;
+                if (s.bfinal) {
+                    fl_br_align(r);
+                    s.sub = 0;
+                    safe_left = r.left;
+                    return FL_RS_STOP_FOOT;
+                }
+                break;
+            }
+            case FL_RS_FIXED:
+            case FL_RS_DYNAMIC: {
+                const bool dyn = s.phase == FL_RS_DYNAMIC;
+                int rc = 0;
+                for (;;) {
+                    if (dyn && r.left >= FL_INF_FAST_MIN_BITS) {
+                        int frc;
+                        do {
+                            frc = fl_inf_fast_round(r, ws, o, lane);
+                        } while (frc == 0 && r.left >= FL_INF_FAST_MIN_BITS);
+                        fl_br_resync(r);
+                        if (frc == 1) {
+                            rc = -1;
+                            break;
+                        }
+                    }
+                    fl_bitr r2 = r;  // the unit is kept only if it finished with the bits staged
+                    rc = (int)fl_uni((uint32_t)(dyn ? fl_inf_dynamic_symbol(r2, ws, o, lane) : fl_rs_fixed_symbol(r2, o, lane)));
+                    if (rc == 100) {
+                        safe_left = r.left;
+                        return FL_RS_STOP_OUT;
+                    }
+                    // out of bits, or a code that the zero bits past the end made invalid
+                    if (rc == 1 || (rc == 7 && dyn && r2.left < 15)) {
+                        safe_left = r.left;
+                        if (!fin) return FL_RS_STOP_IN;
+                    }
+                    r = r2;
+                    if (rc) break;
+                }
+                if (rc > 0) FL_RS_ERR(rc);
+                if (s.bfinal) {
+                    fl_br_align(r);
+                    s.phase = FL_RS_FOOTER;
+                    s.sub = 0;
+                    safe_left = r.left;
+                    return FL_RS_STOP_FOOT;
+                }
+                s.phase = FL_RS_BLOCK;
+                break;
+            }
+            case FL_RS_DHDR: {  // inflate.zig:144-184 on a copy of the reader: kept when it finished
+                fl_bitr r2 = r;
+                const int rc = (int)fl_uni((uint32_t)fl_inf_dynamic_header(r2, ws, flags, lane));
+                if (rc && !fin && r.left < FL_RS_DYN_MAX_BITS) {
+                    // (an error so close to the end may be the end's doing: decided when more is staged)
+                    safe_left = r.left;
+                    return FL_RS_STOP_IN;
+                }
+                r = r2;
+                if (rc) FL_RS_ERR(rc);
+                for (uint32_t i = lane; i < 80; i += 64) {
+                    ((uint32_t*)S->lens)[i] = ((FL_LDS uint32_t*)ws->lens)[i];
+                    ((FL_LDS uint32_t*)ws->lens)[i] = 0;  // the fast rounds' owner array
+                }
+                fl_lds_order();
+                s.phase = FL_RS_DYNAMIC;
+                break;
+            }
+            case FL_RS_FOOTER: {  // container.zig:154-166, a 32-bit word at a time (as the one-shot path reads it)
+                const uint32_t nfoot = container == 1 ? 8u : container == 2 ? 4u : 0u;
+                while (s.sub < nfoot) {
+                    if (r.left < 32) FL_RS_SHORT();
+                    uint32_t v;
+                    fl_br_read(r, 32, v);
+                    s.foot |= (uint64_t)fl_uni(v) << (8 * s.sub);
+                    s.sub += 4;
+                    if (container == 1 && s.sub == 4 && (uint32_t)s.foot != s.check) FL_RS_ERR(4);
+                    if (container == 1 && s.sub == 8 && (uint32_t)(s.foot >> 32) != (uint32_t)s.total) FL_RS_ERR(5);
+                    if (container == 2 && s.sub == 4 && (uint32_t)s.foot != __builtin_bswap32(s.check)) FL_RS_ERR(6);
+                }
+                s.phase = FL_RS_DONE;
+                s.status = 0;
+                safe_left = r.left;
+                return FL_RS_STOP_END;
+            }
+            default:
+                safe_left = r.left;
+                return FL_RS_STOP_END;
+        }
+    }
+#undef FL_RS_SHORT
+#undef FL_RS_ERR
+}
+
+// dst[0, n) = src[0, n), forward, 1 KiB a step with all of a step's loads in flight before its stores (also a move
+// inside one buffer when dst <= src)
+__device__ __forceinline__ void fl_rs_copy(uint8_t* dst, const uint8_t* src, uint64_t n, uint32_t lane) {
+    for (uint64_t i0 = 0; i0 < n; i0 += 1024) {
+        uint8_t b[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const uint64_t j = i0 + 64 * k + lane;
+            b[k] = j < n ? src[j] : (uint8_t)0;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const uint64_t j = i0 + 64 * k + lane;
+            if (j < n) dst[j] = b[k];
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+}
+
+// the checksum of out[0, n) folded into the running one (crc(A || B) = crc(A) x^(8|B|) + crc(B); Adler-32 likewise)
+__device__ __forceinline__ uint32_t fl_rs_fold(uint32_t check, const uint8_t* p, uint64_t n, int container,
+                                               const fl_crc_consts& cc, FL_LDS fl_inflate_ws16* ws, uint32_t lane) {
+    if (n == 0 || container == 0) return check;
+    if (container == 1) {
+        const uint32_t c = fl_wave_crc32(p, n, cc, (FL_LDS uint32_t*)ws->lit_lut, lane);
+        fl_wave_lds_sync();
+        return fl_uni(fl_crc_mulmod(check, fl_crc_xpow8n(cc.xpow8, n)) ^ c);
+    }
+    const uint32_t b = fl_wave_adler32(p, n, lane);
+    const uint32_t a1 = check & 0xffff, b1 = check >> 16, a2 = b & 0xffff, b2 = b >> 16;
+    const uint32_t rem = (uint32_t)(n % 65521u);
+    const uint32_t an = (a1 + a2 + 65521u - 1u) % 65521u;
+    const uint32_t bn = (uint32_t)(((uint64_t)b1 + b2 + (uint64_t)rem * ((a1 + 65521u - 1u) % 65521u)) % 65521u);
+    return fl_uni(an | (bn << 16));
+}
+
+// One feed: stream i continues with in[in_off[i], in_off[i + 1]) and writes to out[out_off[i], out_off[i + 1]).
+__global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                               const uint8_t* __restrict__ final_, uint8_t* __restrict__ out,
+                                                               const uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                                               uint64_t* __restrict__ consumed, int32_t* __restrict__ status,
+                                                               uint8_t* __restrict__ sess, int container, int flags,
+                                                               fl_crc_consts cc) {
+    __shared__ fl_inflate_ws16 ws_mem;
+    __shared__ alignas(8) uint8_t ring_mem[FL_INF_RING_SMALL];
+    __shared__ uint32_t inring_mem[FL_INF_INRING / 4];
+    FL_LDS fl_inflate_ws16* ws = (FL_LDS fl_inflate_ws16*)&ws_mem;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    uint8_t* base = sess + (uint64_t)i * FL_RS_STRIDE;
+    fl_rs_state* S = (fl_rs_state*)base;
+    uint8_t* stage = base + FL_RS_STATE;                      // carry ++ window
+    uint8_t* hist = stage + FL_RS_CARRY + FL_RS_WIN_IN;       // FL_RS_HIST + FL_RS_WOUT
+    const uint64_t i0 = in_off[i], plen = in_off[i + 1] - i0;
+    const uint64_t o0 = out_off[i], slot = out_off[i + 1] - o0;
+    const bool fin = final_[i] != 0;
+    fl_rs_regs s;
+    s.phase = S->phase;
+    s.status = S->status;
+    if (plen == 0 && !fin && slot == 0) {  // skipped: untouched
+        if (lane == 0) {
+            out_len[i] = 0;
+            consumed[i] = 0;
+            status[i] = s.phase == FL_RS_ERROR ? s.status : s.phase == FL_RS_DONE ? 0 : FL_RS_NEED_INPUT;
+        }
+        return;
+    }
+    if (s.phase >= FL_RS_DONE || (slot > 0 && slot < 258)) {  // a complete member or an error: nothing moves
+        if (lane == 0) {
+            out_len[i] = 0;
+            consumed[i] = 0;
+            status[i] = (slot > 0 && slot < 258 && s.phase < FL_RS_DONE) ? -2 /* FLATE_HIP_E_INVALID_ARG */
+                                                                         : s.phase == FL_RS_ERROR ? s.status : 0;
+        }
+        return;
+    }
+    s.foot = S->foot;
+    s.sub = S->sub;
+    s.bfinal = S->bfinal;
+    s.stored_left = S->stored_left;
+    s.hflags = S->hflags;
+    s.hcount = S->hcount;
+    s.check = S->check;
+    s.total = S->total;
+    uint32_t carry = S->carry_len, carry_bit = S->carry_bit;
+    if (s.phase == FL_RS_DYNAMIC) fl_rs_rebuild(ws, S, lane);
+    uint8_t* const slot_p = out + o0;
+    uint64_t p = 0, spos = 0, folded = 0, used = 0;
+    int stop = FL_RS_STOP_END;
+    for (;;) {  // input windows
+        const uint32_t w = (uint32_t)min(plen - p, (uint64_t)FL_RS_WIN_IN);
+        const bool fin_w = fin && p + w == plen;
+        fl_rs_copy(stage + FL_RS_CARRY, in + i0 + p, w, lane);
+        fl_bitr r;
+        r.data = stage + FL_RS_CARRY - carry;
+        r.nbytes = carry + w;
+        r.left = (int64_t)r.nbytes * 8 - carry_bit;
+        r.lane = lane;
+        r.inring = (FL_LDS uint32_t*)inring_mem;
+        fl_br_seek(r, 0);
+        fl_br_resync(r);
+        int64_t safe_left = r.left;
+        for (;;) {  // output windows
+            const uint64_t H = min(s.total, (uint64_t)FL_RS_HIST);
+            const bool win_limited = slot - spos > FL_RS_WOUT;
+            fl_inf_out o;
+            o.out = hist + FL_RS_HIST - H;
+            o.ring = (FL_LDS uint8_t*)ring_mem;
+            o.rmask = FL_INF_RING_SMALL - 1;
+            o.near_max = FL_INF_RING_SMALL - 260;
+            o.cap = H + min(slot - spos, (uint64_t)FL_RS_WOUT);
+            o.wp = H;
+            o.flushed = H;
+            o.fenced = H;
+            o.bias = (uint32_t)((uintptr_t)o.out & 7);
+            {  // the ring holds the last output bytes
+                const uint32_t nr = (uint32_t)min(H, (uint64_t)FL_INF_RING_SMALL);
+                fl_lds_order();
+                for (uint32_t k = lane; k < nr; k += 64) {
+                    const uint64_t at = H - nr + k;
+                    o.ring[((uint32_t)at + o.bias) & o.rmask] = o.out[at];
+                }
+                fl_wave_lds_sync();
+            }
+            stop = fl_rs_run(r, ws, o, s, S, fin_w, container, flags, lane, safe_left);
+            // this window's output: to the caller's slot, and its last 32 KiB become the history
+            fl_inf_flush(o, o.wp, lane);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            const uint64_t P = o.wp - H;
+            if (P) {
+                fl_rs_copy(slot_p + spos, o.out + H, P, lane);
+                const uint64_t H2 = min(H + P, (uint64_t)FL_RS_HIST);
+                fl_rs_copy(hist + FL_RS_HIST - H2, o.out + H + P - H2, H2, lane);
+                s.total += P;
+                spos += P;
+            }
+            if (stop == FL_RS_STOP_FOOT) {
+                s.check = fl_rs_fold(s.check, slot_p + folded, spos - folded, container, cc, ws, lane);
+                folded = spos;
+                continue;
+            }
+            if (stop == FL_RS_STOP_OUT && win_limited) {  // the window was full, not the slot
+                r.left = safe_left;
+                {
+                    const uint64_t pos = (uint64_t)r.nbytes * 8 - (uint64_t)r.left;
+                    fl_br_seek(r, (uint32_t)(pos >> 3));
+                    fl_br_resync(r);
+                }
+                continue;
+            }
+            break;
+        }
+        // where the stream stands in carry ++ window
+        const uint64_t u = (uint64_t)r.nbytes * 8 - (uint64_t)safe_left;
+        const uint32_t ub = (uint32_t)(u >> 3);
+        if (stop == FL_RS_STOP_IN) {  // the rest of what is staged is the start of the next unit: it becomes the carry
+            const uint32_t nc = r.nbytes - ub;
+            if (nc > FL_RS_CARRY) {  // (cannot happen: no unit is that long)
+                s.phase = FL_RS_ERROR;
+                s.status = 1;
+                used = p + w;
+                break;
+            }
+            fl_rs_copy(stage + FL_RS_CARRY - nc, r.data + ub, nc, lane);
+            carry = nc;
+            carry_bit = (uint32_t)(u & 7);
+            p += w;
+            used = p;
+            if (p < plen) continue;
+            break;
+        }
+        if (stop == FL_RS_STOP_OUT) {  // the slot is full: what the unit started in the carry stays there
+            const uint32_t keep = max(carry, ub + ((u & 7) ? 1u : 0u));
+            const uint32_t nc = keep - ub;
+            fl_rs_copy(stage + FL_RS_CARRY - nc, r.data + ub, nc, lane);
+            used = p + (keep - carry);
+            carry = nc;
+            carry_bit = (uint32_t)(u & 7);
+            break;
+        }
+        // the member is complete, or an error
+        const uint32_t end = (uint32_t)((u + 7) >> 3);
+        used = p + (end > carry ? end - carry : 0u);
+        carry = 0;
+        carry_bit = 0;
+        break;
+    }
+    if (s.phase != FL_RS_DONE && s.phase != FL_RS_ERROR)
+        s.check = fl_rs_fold(s.check, slot_p + folded, spos - folded, container, cc, ws, lane);
+    if (lane == 0) {
+        S->total = s.total;
+        S->foot = s.foot;
+        S->phase = s.phase;
+        S->sub = s.sub;
+        S->bfinal = s.bfinal;
+        S->stored_left = s.stored_left;
+        S->hflags = s.hflags;
+        S->hcount = s.hcount;
+        S->check = s.check;
+        S->status = s.status;
+        S->carry_len = carry;
+        S->carry_bit = carry_bit;
+        out_len[i] = spos;
+        consumed[i] = used;
+        status[i] = s.phase == FL_RS_ERROR ? s.status
+                    : s.phase == FL_RS_DONE ? 0
+                    : stop == FL_RS_STOP_OUT ? FL_RS_NEED_OUTPUT : FL_RS_NEED_INPUT;
+    }
+}
+
+// start a new member on the listed streams (Inflate.reset, inflate.zig:301-309)
+__global__ void k_inflater_reset(uint8_t* __restrict__ sess, const uint32_t* __restrict__ which, uint32_t n, uint32_t n_streams,
+                                 int container) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t i = which ? which[k] : k;
+    if (i >= n_streams) return;
+    fl_rs_state* S = (fl_rs_state*)(sess + (uint64_t)i * FL_RS_STRIDE);
+    S->total = 0;
+    S->foot = 0;
+    S->phase = FL_RS_HEADER;
+    S->sub = 0;
+    S->bfinal = 0;
+    S->stored_left = 0;
+    S->check = container == 2 ? 1u : 0u;
+    S->status = 0;
+    S->carry_len = 0;
+    S->carry_bit = 0;
+    S->hflags = 0;
+    S->hcount = 0;
+}

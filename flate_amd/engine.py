@@ -204,6 +204,18 @@ class Engine:
                                                 out_off_ptr, out_len_ptr, status_ptr, consumed_ptr, MEM_DEVICE)
         self._check(rc, "flate_hip_decompress_batch")
 
+    def inflater(self, n, container, flags=0):
+        """n resumable stream decoders (flate_hip_inflater_*): feed each its input piece by piece, in bounded memory."""
+        return Inflater(self, n, container, flags)
+
+    def inflater_feed_device(self, inflater, in_ptr, in_off_ptr, final_ptr, out_ptr, out_off_ptr, out_len_ptr,
+                             consumed_ptr, status_ptr):
+        """One feed of an inflater on device memory (n + 1 offsets, n final flags / lengths / statuses): enqueued on the
+        handle's stream, the kernel reads the offsets itself; set_sync decides about the final wait."""
+        rc = self._L.flate_hip_inflater_feed(self._h, inflater._s, in_ptr, in_off_ptr, final_ptr, out_ptr, out_off_ptr,
+                                             out_len_ptr, consumed_ptr, status_ptr, MEM_DEVICE)
+        self._check(rc, "flate_hip_inflater_feed")
+
     def gather_streams_device(self, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr, dst_off_ptr):
         """Pack the produced streams back to back in device memory (dst_off gets n_chunks + 1 entries)."""
         rc = self._L.flate_hip_gather_streams(self._h, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr,
@@ -259,6 +271,66 @@ class Engine:
         if n < 0:
             raise FlateHipError("flate_hip_debug_tokens failed with %d" % n)
         return buf[:n].copy()
+
+
+class Inflater:
+    """n independent stream decoders whose state stays on the device between feeds (include/flate_hip.h)."""
+
+    def __init__(self, engine, n, container, flags=0):
+        self._eng, self.n, self.container = engine, int(n), container
+        self._s = C.c_void_p()
+        engine._check(engine._L.flate_hip_inflater_create(engine._h, self.n, container, int(flags), C.byref(self._s)),
+                      "flate_hip_inflater_create")
+
+    def feed(self, pieces, final=None, caps=None):
+        """pieces: n bytes-like, or None = skip that stream (empty piece, not final, no slot).  final: a bool for all or
+        one per stream (default False).  caps: output slot per stream (default max(64 KiB, 8 x the piece); at least 258).
+        Returns (list of output bytes, list of statuses, list of consumed input bytes)."""
+        n = self.n
+        if len(pieces) != n:
+            raise ValueError("feed() wants %d pieces" % n)
+        if final is None or isinstance(final, (bool, int)):
+            final = [bool(final)] * n
+        if caps is None or isinstance(caps, int):
+            caps = [caps] * n
+        skip = [p is None for p in pieces]
+        data = [b"" if p is None else bytes(p) for p in pieces]
+        fin = np.array([0 if skip[i] else int(bool(final[i])) for i in range(n)], dtype=np.uint8)
+        cap = np.array([0 if skip[i] else (caps[i] if caps[i] is not None else max(1 << 16, 8 * len(data[i])))
+                        for i in range(n)], dtype=np.uint64)
+        in_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(d) for d in data], dtype=np.uint64), out=in_off[1:])
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(cap, out=out_off[1:])
+        blob = np.frombuffer(b"".join(data), dtype=np.uint8) if in_off[-1] else np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(int(out_off[-1]), 1), dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint64)
+        consumed = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int32)
+        L = self._eng._L
+        rc = L.flate_hip_inflater_feed(self._eng._h, self._s, blob.ctypes.data, in_off.ctypes.data, fin.ctypes.data,
+                                       out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, consumed.ctypes.data,
+                                       status.ctypes.data, MEM_HOST)
+        self._eng._check(rc, "flate_hip_inflater_feed")
+        outs = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
+        return outs, [int(v) for v in status], [int(v) for v in consumed]
+
+    def reset(self, indices):
+        """Start a new member on these streams (Inflate.reset, inflate.zig:301-309)."""
+        w = np.ascontiguousarray(list(indices), dtype=np.uint32)
+        rc = self._eng._L.flate_hip_inflater_reset(self._eng._h, self._s, w.ctypes.data if w.size else None, w.size)
+        self._eng._check(rc, "flate_hip_inflater_reset")
+
+    def close(self):
+        if getattr(self, "_s", None) and self._s.value and self._eng._h.value:
+            self._eng._L.flate_hip_inflater_destroy(self._eng._h, self._s)
+        self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 _default = None

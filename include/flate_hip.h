@@ -90,7 +90,10 @@ enum {
      * (the first block stored) or holds them twice (the second).  Every inflater -- the reference's included -- then
      * reports a wrong checksum / size for gzip and zlib, and returns other bytes than went in for a raw stream.
      * See FLATE_HIP_DEFLATE_REPAIR_Q1. */
-    FLATE_HIP_ST_REFERENCE_Q1_STREAM = 102
+    FLATE_HIP_ST_REFERENCE_Q1_STREAM = 102,
+    /* 103 is taken host-side (InvalidState of the Python mirror) */
+    FLATE_HIP_ST_NEED_INPUT = 104,  /* inflater feed: all input absorbed, the member is not finished, more input may follow */
+    FLATE_HIP_ST_NEED_OUTPUT = 105  /* inflater feed: the output slot is full; feed the unabsorbed rest again with room */
 };
 
 /* handle flags (flate_hip_set_flags).  bit0: compress at levels 4..9 hands every block the bytes its tokens cover -- the
@@ -238,6 +241,42 @@ int flate_hip_decompress_batch_sharded(flate_hip_handle h, void* nccl_comm, int 
                                        int container, int flags, uint8_t* gathered, uint64_t slice_bytes,
                                        const uint64_t* out_off, uint64_t* out_len, int32_t* status,
                                        uint64_t* consumed);
+
+/*
+ * Resumable inflate: n_streams independent stream decoders whose state stays in device memory between calls
+ * (the reference's Decompressor, inflate.zig:43-355, that reads from a reader in bounded memory).  Each stream
+ * is fed its compressed bytes piece by piece and hands out output as it is decoded; about 74 KiB of device memory
+ * per stream (state, carry, 32 KiB history and the decoder's input and output windows), whatever the length of
+ * the stream.  flags bit 0 = FLATE_HIP_INFLATE_STRICT_Q6.
+ *
+ * One feed, per stream i:
+ *   in[in_off[i] .. in_off[i+1])  continues the stream where the previous feed left it; consumed[i] bytes of it
+ *                                 were absorbed (never passed again; the rest must be).  All of it is absorbed
+ *                                 unless the member ended inside it or the output slot filled.
+ *   final[i]                      1 = no input follows this piece (the EndOfStream model of the one-shot path)
+ *   out[out_off[i] .. out_off[i+1])  slot for this feed's output; out_len[i] bytes written, the rest of the slot is
+ *                                 left as it was.  The output of all feeds,
+ *                                 concatenated, is what flate_hip_decompress_batch makes of the concatenated input.
+ *   status[i]                     FLATE_HIP_ST_OK (member complete, footer checked), FLATE_HIP_ST_NEED_INPUT,
+ *                                 FLATE_HIP_ST_NEED_OUTPUT, or an error 1..14 -- sticky: later feeds return it and
+ *                                 absorb nothing.  An error is reported while final[i] = 0 only if no later input
+ *                                 could change it.  The feed that reports an error absorbs the input up to the
+ *                                 error; bytes an earlier feed absorbed stay absorbed.
+ * A complete member produces and absorbs nothing until flate_hip_inflater_reset (trailing bytes belong to the next
+ * member).  A stream with an empty piece, final 0 and an empty slot is skipped (its state is untouched).  A slot of
+ * 1..257 bytes for a stream that is not skipped is FLATE_HIP_E_INVALID_ARG (host memory: the call; device memory: that
+ * stream's status, state untouched); 258 bytes or more always make progress.
+ * FLATE_HIP_MEM_HOST: synchronous.  FLATE_HIP_MEM_DEVICE: every array is device memory and the call only enqueues
+ * (no host wait, no host read of the offsets); flate_hip_set_sync decides about the final wait.
+ * flate_hip_inflater_reset (host array `which`) starts a new member on the listed streams.
+ */
+typedef struct flate_hip_inflater* flate_hip_inflater_t;
+int flate_hip_inflater_create(flate_hip_handle h, uint32_t n_streams, int container, int flags, flate_hip_inflater_t* s);
+int flate_hip_inflater_destroy(flate_hip_handle h, flate_hip_inflater_t s);
+int flate_hip_inflater_reset(flate_hip_handle h, flate_hip_inflater_t s, const uint32_t* which, uint32_t n_which);
+int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const uint8_t* in, const uint64_t* in_off,
+                            const uint8_t* final_, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                            uint64_t* consumed, int32_t* status, int memkind);
 
 /* The containers' checksums on their own (container.zig:168-206: std.hash.Crc32 / Adler32 over the raw
  * input): container 1 = CRC-32, 2 = Adler-32 of a host buffer, computed by the checksum kernels; and the

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""gunzip <file>.gz: writes <file> with the MI355X engine -- the reference's bin/gunzip.zig:25-27
+"""gunzip [--piece N] <file>.gz: writes <file> with the MI355X engine -- the reference's bin/gunzip.zig:25-27
 (`gzip.decompress(br.reader(), output_file.writer())`; refuses names without the .gz suffix, :15-19).
-Concatenated members are decoded one after the other (Inflate.reset, inflate.zig:301-309)."""
+Concatenated members are decoded one after the other (Inflate.reset, inflate.zig:301-309).  With --piece N the file is
+read N bytes at a time and decoded by the resumable inflater: memory stays bounded whatever the file's size."""
 import os
 os.environ.setdefault("FLATE_HIP_PRELOAD_TORCH_HIP", "1")  # one HIP runtime per process: torch, imported later, brings its own (flate_amd/_capi.py)
 import sys
@@ -11,8 +12,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
+    piece = None
+    if len(argv) == 3 and argv[0] == "--piece" and argv[1].isdigit() and int(argv[1]) > 0:
+        piece, argv = int(argv[1]), argv[2:]
     if len(argv) != 1:
-        print("usage: gunzip.py <file>.gz", file=sys.stderr)
+        print("usage: gunzip.py [--piece N] <file>.gz", file=sys.stderr)
         return 2
     name = argv[0]
     if not name.endswith(".gz"):
@@ -24,7 +28,7 @@ def main(argv=None):
     out_name, tmp_name = name[:-3], name[:-3] + ".gunzip-tmp"
     try:
         with open(name, "rb") as src, open(tmp_name, "wb") as dst:
-            d = gzip.decompressor(src)
+            d = gzip.decompressor(src) if piece is None else gzip.decompressor(src, piece=piece)
             d.decompress(dst)
             while d.more_input():  # further members of the same file
                 d.reset()
