@@ -19,6 +19,7 @@ DEFLATE_REPAIR_Q1 = 1          # flate_hip_set_flags
 ST_REFERENCE_Q1_STREAM = 102   # compress status: the reference's bytes, which do not inflate to the input (include/flate_hip.h)
 ST_NEED_INPUT = 104            # inflater feed: all input absorbed, member not finished
 ST_NEED_OUTPUT = 105           # inflater feed: the output slot is full
+FEED_MORE, FEED_FLUSH, FEED_FINISH = 0, 1, 2  # deflater feed ops
 
 # every symbol include/flate_hip.h declares
 SYMBOLS = [
@@ -32,6 +33,8 @@ SYMBOLS = [
     "flate_hip_plan_compress", "flate_hip_compress_planned", "flate_hip_plan_destroy",
     "flate_hip_checksum", "flate_hip_checksum_combine", "flate_hip_debug_reload_env",
     "flate_hip_inflater_create", "flate_hip_inflater_destroy", "flate_hip_inflater_reset", "flate_hip_inflater_feed",
+    "flate_hip_deflater_create", "flate_hip_deflater_destroy", "flate_hip_deflater_reset", "flate_hip_deflater_feed",
+    "flate_hip_debug_device_bytes",
 ]
 
 
@@ -132,6 +135,16 @@ def lib():
     L.flate_hip_inflater_reset.restype = C.c_int
     L.flate_hip_inflater_feed.argtypes = [vp, vp, vp, u64p, vp, vp, u64p, u64p, u64p, i32p, C.c_int]
     L.flate_hip_inflater_feed.restype = C.c_int
+    L.flate_hip_deflater_create.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.flate_hip_deflater_create.restype = C.c_int
+    L.flate_hip_deflater_destroy.argtypes = [vp, vp]
+    L.flate_hip_deflater_destroy.restype = C.c_int
+    L.flate_hip_deflater_reset.argtypes = [vp, vp, vp, C.c_uint32]
+    L.flate_hip_deflater_reset.restype = C.c_int
+    L.flate_hip_deflater_feed.argtypes = [vp, vp, vp, u64p, vp, vp, u64p, u64p, u64p, i32p, C.c_int]
+    L.flate_hip_deflater_feed.restype = C.c_int
+    L.flate_hip_debug_device_bytes.argtypes = [vp, vp]
+    L.flate_hip_debug_device_bytes.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.flate_hip_debug_tokens.restype = C.c_int64
     _lib = L

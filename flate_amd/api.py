@@ -239,6 +239,81 @@ class _Compressor:
         self._done = True
 
 
+class _PieceCompressor:
+    """SimpleCompressor (deflate.zig:449-529) in bounded memory: writes are gathered into pieces of `piece` bytes, each
+    goes to a resumable compressor on the device (flate_hip_deflater_*) and the blocks it completes go to the writer at
+    once.  The bytes are those of _Compressor for the same write / flush / finish calls.  Host memory: the piece and
+    one output slot, whatever the stream's length."""
+
+    def __init__(self, container, mode, writer, engine=None, piece=1 << 20):
+        if int(piece) < 1:
+            raise ValueError("piece must be at least 1 byte")
+        self._eng = engine or default_engine()
+        self._wrt, self._piece = writer, int(piece)
+        self._slot = self._piece + 5 * (self._piece // 65535) + (1 << 17)
+        self._d = self._eng.deflater(1, container, int(mode))
+        self._buf = bytearray()
+        self._done = False
+
+    def _feed(self, data, op):
+        # the stream never has output pending when a step starts (it is drained below): the piece is taken at once
+        outs, st, cons = self._d.feed([data], op=op, caps=self._slot)
+        if cons[0] != len(data):
+            raise InvalidState("the resumable compressor did not take its piece")
+        self._wrt.write(outs[0])
+        while st[0] == _capi.ST_NEED_OUTPUT:
+            outs, st, _ = self._d.feed([b""], op=_capi.FEED_MORE, caps=self._slot)
+            self._wrt.write(outs[0])
+        _compress_status(st[0] if op == _capi.FEED_FINISH else 0)
+
+    def _live(self):
+        if self._done:
+            raise InvalidState("compressor used after finish()")
+
+    def write(self, data):  # deflate.zig:495-511
+        self._live()
+        mv = memoryview(data).cast("B")
+        n = len(mv)
+        while len(mv):
+            take = min(self._piece - len(self._buf), len(mv))
+            self._buf += mv[:take]
+            mv = mv[take:]
+            if len(self._buf) == self._piece:
+                self._feed(bytes(self._buf), _capi.FEED_MORE)
+                self._buf.clear()
+        return n
+
+    def compress(self, reader):  # deflate.zig:304-321, the reader `piece` bytes at a time
+        self._live()
+        if isinstance(reader, (bytes, bytearray, memoryview)):
+            self.write(reader)
+            return
+        while True:
+            b = reader.read(self._piece - len(self._buf))
+            if not b:
+                return
+            self.write(b)
+
+    def writer(self):
+        return self
+
+    def flush(self):  # deflate.zig:474-478
+        self._live()
+        self._feed(bytes(self._buf), _capi.FEED_FLUSH)
+        self._buf.clear()
+
+    def set_writer(self, new_writer):
+        self._wrt = new_writer
+
+    def finish(self):  # deflate.zig:480-484
+        if self._done:
+            return
+        self._feed(bytes(self._buf), _capi.FEED_FINISH)
+        self._buf.clear()
+        self._done = True
+        self._d.close()
+
+
 class _Decompressor:
     """Inflate (inflate.zig:43-355) seen from the caller.  The reader is consumed as far as the current stream
     needs it, in steps that double: a decode that runs out of input (EndOfStream) while the reader still has
@@ -455,13 +530,17 @@ class _Simple:
     def __init__(self, container, mode):
         self._container, self._mode = container, mode
 
-    def compress(self, reader, writer, engine=None):
-        c = self.compressor(writer, engine)
+    def compress(self, reader, writer, engine=None, *, piece=None):
+        c = self.compressor(writer, engine, piece=piece)
         c.compress(reader)
         c.finish()
 
-    def compressor(self, writer, engine=None):
-        return _Compressor(self._container, self._mode, writer, engine)
+    def compressor(self, writer, engine=None, *, piece=None):
+        """piece=None: the whole-stream compressor.  piece=N: bounded memory -- the input goes to a resumable
+        compressor N bytes at a time and its blocks reach the writer as they are made (_PieceCompressor)."""
+        if piece is None:
+            return _Compressor(self._container, self._mode, writer, engine)
+        return _PieceCompressor(self._container, self._mode, writer, engine, piece=piece)
 
     Compressor = compressor
 
@@ -475,13 +554,17 @@ class ContainerModule:
         self.store = _Simple(container, _capi.MODE_STORE)
         self.Options, self.Level = Options, Level
 
-    def compress(self, reader, writer, options=None, engine=None):
-        c = self.compressor(writer, options, engine)
+    def compress(self, reader, writer, options=None, engine=None, *, piece=None):
+        c = self.compressor(writer, options, engine, piece=piece)
         c.compress(reader)
         c.finish()
 
-    def compressor(self, writer, options=None, engine=None):
+    def compressor(self, writer, options=None, engine=None, *, piece=None):
+        """piece=N: bounded memory (_PieceCompressor); only huffman-only and store-only streams are resumable, a
+        level 4..9 compressor with piece= raises ValueError."""
         options = options or Options()
+        if piece is not None:
+            raise ValueError("piece= needs the huffman or store namespace: levels 4..9 are not resumable")
         return _Compressor(self._container, int(options.level), writer, engine, repair_q1=options.repair_q1)
 
     Compressor = compressor

@@ -20,6 +20,7 @@
 #include "../../include/flate_hip.h"
 #include "kernels_block.h"
 #include "kernels_common.h"
+#include "kernels_deflater.h"
 #include "kernels_inflate.h"
 #include "kernels_inflate_par.h"
 #include "kernels_lz.h"
@@ -52,13 +53,14 @@ enum KernelId {
     K_INFLATE_SPAN,
     K_GATHER,
     K_INFLATER,
+    K_DEFLATER,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
                                            "k_lz_chain", "k_lz_parse", "k_lz_links", "k_lz_walk", "k_lz_emit",
                                            "k_st_parse", "k_st_emit", "k_plan",
                                            "k_offsets",  "k_encode",    "k_inflate",  "k_inflate_par", "k_span_scan", "k_inflate_span",
-                                           "k_gather", "k_inflater"};
+                                           "k_gather", "k_inflater", "k_deflater"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -146,6 +148,7 @@ struct flate_hip_ctx {
     hipEvent_t ms_ev0 = nullptr, ms_ev1 = nullptr;
     bool ms_pending = false;
     bool ck_pending = false;
+    uint64_t dfl_bytes = 0;  // device memory the handle's deflaters hold (flate_hip_debug_device_bytes)
     // last level 4..9 call, for the debug seam
     uint32_t dbg_pass_chunks = 0;
     uint32_t dbg_first_chunk = 0;
@@ -2832,6 +2835,342 @@ int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const ui
                 HIP_OK(h, hipMemcpyAsync(out + out_off[i], (uint8_t*)s->out.p + hout[i], out_len[i], hipMemcpyDeviceToHost, st));
     }
     HIP_OK(h, hipStreamSynchronize(st));
+    return FLATE_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- resumable compress, huffman-only / store-only (kernels_deflater.h) ----
+struct flate_hip_deflater {
+    uint32_t n = 0;
+    int container = 0, mode = 0;
+    DevBuf state, bufs;  // fl_dfl_state and FL_DFL_BUF bytes of SimpleCompressor buffer per stream
+    // output a feed made beyond its slot: handed out by the next feeds, before the stream takes more input
+    std::vector<DevBuf> pend;
+    std::vector<uint64_t> pend_len, pend_pos;
+    // host mirror of the per-stream counters the feeds plan with
+    std::vector<uint32_t> bl;
+    std::vector<uint8_t> hdr_done, finished;
+    // feed workspace: the pieces (host feeds), the staged input, the produced blocks, the tables
+    DevBuf src, win, wout, chunks, blk, sb, ckblk, cksb, jobs, produced, plans, hist, cks;
+};
+
+namespace {
+int deflater_buf(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
+    if (bytes <= b.cap) return FLATE_HIP_OK;
+    (void)hipStreamSynchronize(h->stream);
+    if (b.p) {
+        (void)hipFree(b.p);
+        h->dfl_bytes -= b.cap;
+    }
+    b.p = nullptr;
+    b.cap = 0;
+    const size_t want = bytes + bytes / 8 + 256;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        h->last_error = "hipMalloc(" + std::to_string(want) + ") for a deflater feed failed";
+        return FLATE_HIP_E_ALLOC;
+    }
+    b.cap = want;
+    h->dfl_bytes += want;
+    return FLATE_HIP_OK;
+}
+void deflater_free(flate_hip_ctx* h, DevBuf& b) {
+    if (b.p) {
+        (void)hipFree(b.p);
+        h->dfl_bytes -= b.cap;
+    }
+    b.p = nullptr;
+    b.cap = 0;
+}
+// the largest piece one feed takes for a stream: its buffer and the piece are staged together, positions are 32-bit
+constexpr uint64_t kDeflaterMaxPiece = 0xfff00000ull - FL_DFL_BUF;
+}  // namespace
+
+extern "C" {
+
+int flate_hip_deflater_create(flate_hip_handle h, uint32_t n_streams, int container, int mode, uint32_t flags,
+                              flate_hip_deflater_t* out) {
+    if (!h || !out || n_streams == 0 || container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
+    // (FLATE_HIP_DEFLATE_REPAIR_Q1 is the only flag: Q1 is a seam between token blocks, so it never arises in the modes a
+    // deflater runs -- nothing to keep)
+    if (flags & ~(uint32_t)FLATE_HIP_DEFLATE_REPAIR_Q1) return FLATE_HIP_E_INVALID_ARG;
+    *out = nullptr;
+    fl_params prm{};
+    if (!level_args(mode, prm)) return FLATE_HIP_E_INVALID_ARG;
+    if (mode >= 4) {
+        h->last_error = "flate_hip_deflater_create: levels 4..9 are not resumable; modes 0 (store) and 1 (huffman) are";
+        return FLATE_HIP_E_UNSUPPORTED;
+    }
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    flate_hip_deflater* d = new flate_hip_deflater();
+    d->n = n_streams;
+    d->container = container;
+    d->mode = mode;
+    d->pend.resize(n_streams);
+    d->pend_len.assign(n_streams, 0);
+    d->pend_pos.assign(n_streams, 0);
+    d->bl.assign(n_streams, 0);
+    d->hdr_done.assign(n_streams, 0);
+    d->finished.assign(n_streams, 0);
+    int rc = deflater_buf(h, d->state, sizeof(fl_dfl_state) * (size_t)n_streams);
+    if (!rc) rc = deflater_buf(h, d->bufs, (size_t)FL_DFL_BUF * n_streams);
+    if (!rc && (hipMemsetAsync(d->state.p, 0, sizeof(fl_dfl_state) * (size_t)n_streams, h->stream) != hipSuccess ||
+                hipStreamSynchronize(h->stream) != hipSuccess))
+        rc = FLATE_HIP_E_LAUNCH;
+    if (rc) {
+        deflater_free(h, d->state);
+        deflater_free(h, d->bufs);
+        delete d;
+        return rc;
+    }
+    *out = d;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_deflater_destroy(flate_hip_handle h, flate_hip_deflater_t d) {
+    if (!h || !d) return FLATE_HIP_E_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    for (DevBuf* b : {&d->state, &d->bufs, &d->src, &d->win, &d->wout, &d->chunks, &d->blk, &d->sb, &d->ckblk, &d->cksb,
+                      &d->jobs, &d->produced, &d->plans, &d->hist, &d->cks})
+        deflater_free(h, *b);
+    for (DevBuf& b : d->pend) deflater_free(h, b);
+    delete d;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_deflater_reset(flate_hip_handle h, flate_hip_deflater_t d, const uint32_t* which, uint32_t n_which) {
+    if (!h || !d || (n_which && !which)) return FLATE_HIP_E_INVALID_ARG;
+    for (uint32_t k = 0; k < n_which; k++)
+        if (which[k] >= d->n) return FLATE_HIP_E_INVALID_ARG;
+    if (n_which == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    for (uint32_t k = 0; k < n_which; k++) {
+        const uint32_t i = which[k];
+        d->bl[i] = 0;
+        d->hdr_done[i] = 0;
+        d->finished[i] = 0;
+        d->pend_len[i] = d->pend_pos[i] = 0;
+        HIP_OK(h, hipMemsetAsync((fl_dfl_state*)d->state.p + i, 0, sizeof(fl_dfl_state), h->stream));
+    }
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_deflater_feed(flate_hip_handle h, flate_hip_deflater_t d, const uint8_t* in, const uint64_t* in_off,
+                            const uint8_t* op, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                            uint64_t* consumed, int32_t* status, int memkind) {
+    if (!h || !d || !in_off || !op || !out_off || !out_len || !consumed || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    const uint32_t n = d->n;
+    const bool dev = memkind == FLATE_HIP_MEM_DEVICE;
+    const hipMemcpyKind to_out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    // offsets and ops on the host: the block tables are built here (device feeds wait for them)
+    std::vector<uint64_t> hin(n + 1), hout(n + 1);
+    std::vector<uint8_t> hop(n);
+    if (dev) {
+        HIP_OK(h, hipMemcpyAsync(hin.data(), in_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(hout.data(), out_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(hop.data(), op, n, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+    } else {
+        std::memcpy(hin.data(), in_off, 8 * ((size_t)n + 1));
+        std::memcpy(hout.data(), out_off, 8 * ((size_t)n + 1));
+        std::memcpy(hop.data(), op, n);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        if (hin[i + 1] < hin[i] || hout[i + 1] < hout[i] || hop[i] > FLATE_HIP_FEED_FINISH) return FLATE_HIP_E_INVALID_ARG;
+        if (hin[i + 1] - hin[i] > kDeflaterMaxPiece) return FLATE_HIP_E_INVALID_ARG;
+    }
+    if (hin[n] > hin[0] && !in) return FLATE_HIP_E_INVALID_ARG;
+    std::vector<uint64_t> r_len(n, 0), r_cons(n, 0);
+    std::vector<int32_t> r_st(n, FLATE_HIP_ST_NEED_INPUT);
+    int rc;
+
+    // streams with output left over: drain it, take nothing; finished ones take nothing; the rest take their piece
+    std::vector<uint32_t> act;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t pn = hin[i + 1] - hin[i], slot = hout[i + 1] - hout[i];
+        if (d->pend_len[i] > d->pend_pos[i]) {
+            const uint64_t give = std::min(slot, d->pend_len[i] - d->pend_pos[i]);
+            if (give)
+                HIP_OK(h, hipMemcpyAsync(out + hout[i], (const uint8_t*)d->pend[i].p + d->pend_pos[i], give, to_out, st));
+            d->pend_pos[i] += give;
+            r_len[i] = give;
+            const bool left = d->pend_pos[i] < d->pend_len[i];
+            // (everything delivered: NEED_INPUT, or the final status of a finished stream; consumed 0 says the piece was
+            // not taken and goes again)
+            r_st[i] = left ? FLATE_HIP_ST_NEED_OUTPUT : (d->finished[i] ? FLATE_HIP_ST_OK : FLATE_HIP_ST_NEED_INPUT);
+            if (!left) d->pend_len[i] = d->pend_pos[i] = 0;
+        } else if (d->finished[i]) {
+            r_st[i] = FLATE_HIP_ST_OK;
+        } else if (!(pn == 0 && hop[i] == FLATE_HIP_FEED_MORE && slot == 0)) {
+            act.push_back(i);
+        }
+    }
+
+    if (!act.empty()) {
+        const uint32_t nj = (uint32_t)act.size();
+        fl_params prm{};
+        (void)level_args(d->mode, prm);
+        prm.container = d->container;
+        prm.mode = d->mode;
+        prm.n_chunks = nj;
+        prm.stream = 0;
+        std::vector<fl_dfl_job> jobs(nj);
+        std::vector<fl_chunk> chunks(nj);
+        std::vector<fl_sblock> sbl, cku;
+        std::vector<uint32_t> blk, ckblk;
+        uint64_t win_n = 0, out_n = 0, max_units = 1;
+        const uint64_t in_lo = hin[0];
+        for (uint32_t j = 0; j < nj; j++) {
+            const uint32_t i = act[j];
+            fl_dfl_job& jb = jobs[j];
+            fl_chunk& c = chunks[j];
+            std::memset(&c, 0, sizeof c);
+            jb.stream = i;
+            jb.bl = d->bl[i];
+            jb.n = (uint32_t)(hin[i + 1] - hin[i]);
+            jb.src_off = dev ? hin[i] : hin[i] - in_lo;
+            jb.hdr = d->hdr_done[i] ? 0u : 1u;
+            jb.finish = hop[i] == FLATE_HIP_FEED_FINISH ? 1u : 0u;
+            c.first_block = (uint32_t)sbl.size();
+            jb.keep = fl_dfl_blocks(jb.bl, jb.n, hop[i], sbl);
+            c.n_blocks = (uint32_t)sbl.size() - c.first_block;
+            for (uint32_t k = 0; k < c.n_blocks; k++) blk.push_back(j);
+            jb.ck_first = (uint32_t)cku.size();
+            jb.ck_n = fl_dfl_checksum_units(jb.bl, jb.n, cku);
+            for (uint32_t k = 0; k < jb.ck_n; k++) ckblk.push_back(j);
+            const uint32_t L = jb.bl + jb.n;
+            c.in_off = win_n;
+            c.in_len = L;
+            win_n += (((uint64_t)L + 15) & ~15ull) + 16;
+            c.out_off = out_n;
+            c.out_cap = fl_dfl_out_bound(jb.bl, jb.n);
+            out_n += (c.out_cap + 15) & ~15ull;
+            c.unfinished = jb.finish ? 0u : 1u;
+            max_units = std::max<uint64_t>(max_units, ((uint64_t)L + 15) / 16);
+        }
+        const uint32_t nb = (uint32_t)sbl.size(), nck = (uint32_t)cku.size();
+        prm.n_blocks = nb;
+        const uint8_t* src = in;
+        if (!dev) {
+            if ((rc = deflater_buf(h, d->src, hin[n] - in_lo + 16))) return rc;
+            if (hin[n] > in_lo) HIP_OK(h, hipMemcpyAsync(d->src.p, in + in_lo, hin[n] - in_lo, hipMemcpyHostToDevice, st));
+            src = (const uint8_t*)d->src.p;
+        }
+        if ((rc = deflater_buf(h, d->win, win_n + 16)) || (rc = deflater_buf(h, d->wout, out_n + 16)) ||
+            (rc = deflater_buf(h, d->jobs, sizeof(fl_dfl_job) * nj)) || (rc = deflater_buf(h, d->chunks, sizeof(fl_chunk) * nj)) ||
+            (rc = deflater_buf(h, d->produced, 8 * (size_t)nj)) ||
+            (rc = deflater_buf(h, d->blk, 4 * (size_t)std::max(nb, 1u))) || (rc = deflater_buf(h, d->sb, sizeof(fl_sblock) * std::max(nb, 1u))) ||
+            (rc = deflater_buf(h, d->ckblk, 4 * (size_t)std::max(nck, 1u))) ||
+            (rc = deflater_buf(h, d->cksb, sizeof(fl_sblock) * std::max(nck, 1u))) ||
+            (rc = deflater_buf(h, d->plans, sizeof(fl_block_plan) * std::max(nb, 1u))) ||
+            (rc = deflater_buf(h, d->hist, 4 * 320 * (size_t)std::max(nb, 1u))) ||
+            (rc = deflater_buf(h, d->cks, 8 * (size_t)std::max(nck, 1u))))
+            return rc;
+        HIP_OK(h, hipMemcpyAsync(d->jobs.p, jobs.data(), sizeof(fl_dfl_job) * nj, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipMemcpyAsync(d->chunks.p, chunks.data(), sizeof(fl_chunk) * nj, hipMemcpyHostToDevice, st));
+        if (nb) {
+            HIP_OK(h, hipMemcpyAsync(d->blk.p, blk.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, st));
+            HIP_OK(h, hipMemcpyAsync(d->sb.p, sbl.data(), sizeof(fl_sblock) * nb, hipMemcpyHostToDevice, st));
+        }
+        if (nck) {
+            HIP_OK(h, hipMemcpyAsync(d->ckblk.p, ckblk.data(), 4 * (size_t)nck, hipMemcpyHostToDevice, st));
+            HIP_OK(h, hipMemcpyAsync(d->cksb.p, cku.data(), sizeof(fl_sblock) * nck, hipMemcpyHostToDevice, st));
+        }
+        HIP_OK(h, hipMemsetAsync(d->wout.p, 0, out_n, st));  // (the bit packer ORs into the output)
+        const fl_dfl_job* djobs = (const fl_dfl_job*)d->jobs.p;
+        const fl_chunk* dch = (const fl_chunk*)d->chunks.p;
+        const uint32_t* dblk = (const uint32_t*)d->blk.p;
+        const fl_sblock* dsb = (const fl_sblock*)d->sb.p;
+        fl_block_plan* dpl = (fl_block_plan*)d->plans.p;
+        {
+            ProfScope ps(h, K_DEFLATER);
+            const uint32_t slices = (uint32_t)std::min<uint64_t>(1024, (max_units + 255) / 256);
+            hipLaunchKernelGGL(k_deflater_stage, dim3(nj, slices), dim3(256), 0, st, src, djobs, dch, (const uint8_t*)d->bufs.p,
+                               (uint8_t*)d->win.p);
+        }
+        const uint8_t* dwin = (const uint8_t*)d->win.p;
+        if (d->container != 0 && nck) {
+            ProfScope ps(h, K_CHECKSUM);
+            hipLaunchKernelGGL(k_checksum, dim3(nck), dim3(64), 0, st, dwin, dch, (const uint32_t*)d->ckblk.p,
+                               (const fl_sblock*)d->cksb.p, prm, h->crc, (uint32_t*)d->cks.p);
+        }
+        if (nb) {
+            ProfScope ps(h, K_PLAN);
+            if (d->mode == 0) {
+                hipLaunchKernelGGL(k_plan_store, dim3((nb + 255) / 256), dim3(256), 0, st, dch, dblk, dsb, nb, dpl);
+            } else {
+                hipLaunchKernelGGL(k_byte_hist, dim3(nb), dim3(256), 0, st, dwin, dch, dblk, dsb, (uint32_t*)d->hist.p);
+                hipLaunchKernelGGL(k_plan, dim3((nb + FL_PLAN_WAVES - 1) / FL_PLAN_WAVES), dim3(64 * FL_PLAN_WAVES), 0, st,
+                                   dch, dblk, dsb, prm, (const uint32_t*)d->hist.p, dpl);
+            }
+        }
+        {
+            ProfScope ps(h, K_DEFLATER);
+            hipLaunchKernelGGL(k_deflater_offsets, dim3(nj), dim3(64), 0, st, djobs, dch, prm, h->crc, dpl,
+                               (const uint32_t*)d->cks.p, (fl_dfl_state*)d->state.p, (uint8_t*)d->wout.p,
+                               (uint64_t*)d->produced.p);
+        }
+        if (nb) {
+            ProfScope ps(h, K_ENCODE);
+            hipLaunchKernelGGL(k_encode<false>, dim3(nb), dim3(64 * FL_ENC_WAVES), 0, st, dwin, dch, dblk,
+                               (const fl_block_plan*)dpl, (const uint32_t*)nullptr, (uint32_t*)d->wout.p);
+        }
+        {
+            ProfScope ps(h, K_DEFLATER);
+            hipLaunchKernelGGL(k_deflater_commit, dim3(nj), dim3(256), 0, st, djobs, dch, (const uint64_t*)d->produced.p, dwin,
+                               (const uint8_t*)d->wout.p, (fl_dfl_state*)d->state.p, (uint8_t*)d->bufs.p);
+        }
+        HIP_OK(h, hipGetLastError());
+        std::vector<uint64_t> prod(nj);
+        HIP_OK(h, hipMemcpyAsync(prod.data(), d->produced.p, 8 * (size_t)nj, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+        for (uint32_t j = 0; j < nj; j++) {
+            const uint32_t i = act[j];
+            const uint64_t p = prod[j], slot = hout[i + 1] - hout[i];
+            if (p > chunks[j].out_cap) {
+                h->last_error = "deflater feed: a stream produced more than its bound";
+                return FLATE_HIP_E_LAUNCH;
+            }
+            const uint64_t give = std::min(p, slot);
+            const uint8_t* from = (const uint8_t*)d->wout.p + chunks[j].out_off;
+            if (give) HIP_OK(h, hipMemcpyAsync(out + hout[i], from, give, to_out, st));
+            if (p > give) {
+                if ((rc = deflater_buf(h, d->pend[i], p - give))) return rc;
+                HIP_OK(h, hipMemcpyAsync(d->pend[i].p, from + give, p - give, hipMemcpyDeviceToDevice, st));
+                d->pend_len[i] = p - give;
+                d->pend_pos[i] = 0;
+            }
+            d->bl[i] = jobs[j].keep;
+            d->hdr_done[i] = 1;
+            if (jobs[j].finish) d->finished[i] = 1;
+            r_len[i] = give;
+            r_cons[i] = jobs[j].n;
+            r_st[i] = p > give ? FLATE_HIP_ST_NEED_OUTPUT : (jobs[j].finish ? FLATE_HIP_ST_OK : FLATE_HIP_ST_NEED_INPUT);
+        }
+    }
+    if (dev) {
+        HIP_OK(h, hipMemcpyAsync(out_len, r_len.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipMemcpyAsync(consumed, r_cons.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipMemcpyAsync(status, r_st.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    } else {
+        std::memcpy(out_len, r_len.data(), 8 * (size_t)n);
+        std::memcpy(consumed, r_cons.data(), 8 * (size_t)n);
+        std::memcpy(status, r_st.data(), 4 * (size_t)n);
+    }
+    HIP_OK(h, hipStreamSynchronize(st));
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_debug_device_bytes(flate_hip_handle h, uint64_t* bytes) {
+    if (!h || !bytes) return FLATE_HIP_E_INVALID_ARG;
+    *bytes = h->dfl_bytes;
     return FLATE_HIP_OK;
 }
 

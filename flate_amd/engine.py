@@ -216,6 +216,25 @@ class Engine:
                                              out_len_ptr, consumed_ptr, status_ptr, MEM_DEVICE)
         self._check(rc, "flate_hip_inflater_feed")
 
+    def deflater(self, n, container, mode, flags=0):
+        """n resumable compressors (flate_hip_deflater_*, modes 0 and 1): feed each its input piece by piece, in bounded
+        memory."""
+        return Deflater(self, n, container, mode, flags)
+
+    def deflater_feed_device(self, deflater, in_ptr, in_off_ptr, op_ptr, out_ptr, out_off_ptr, out_len_ptr,
+                             consumed_ptr, status_ptr):
+        """One feed of a deflater on device memory (n + 1 offsets, n ops / lengths / statuses).  The feed reads the
+        offsets and ops back and waits for its kernels."""
+        rc = self._L.flate_hip_deflater_feed(self._h, deflater._d, in_ptr, in_off_ptr, op_ptr, out_ptr, out_off_ptr,
+                                             out_len_ptr, consumed_ptr, status_ptr, MEM_DEVICE)
+        self._check(rc, "flate_hip_deflater_feed")
+
+    def device_bytes(self):
+        """Device bytes the handle's deflaters hold (state, buffers, feed workspace, pending output)."""
+        v = C.c_uint64(0)
+        self._check(self._L.flate_hip_debug_device_bytes(self._h, C.byref(v)), "flate_hip_debug_device_bytes")
+        return int(v.value)
+
     def gather_streams_device(self, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr, dst_off_ptr):
         """Pack the produced streams back to back in device memory (dst_off gets n_chunks + 1 entries)."""
         rc = self._L.flate_hip_gather_streams(self._h, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr,
@@ -325,6 +344,66 @@ class Inflater:
         if getattr(self, "_s", None) and self._s.value and self._eng._h.value:
             self._eng._L.flate_hip_inflater_destroy(self._eng._h, self._s)
         self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Deflater:
+    """n independent huffman-only / store-only compressors whose state stays on the device between feeds
+    (include/flate_hip.h)."""
+
+    def __init__(self, engine, n, container, mode, flags=0):
+        self._eng, self.n, self.container, self.mode = engine, int(n), container, mode
+        self._d = C.c_void_p()
+        engine._check(engine._L.flate_hip_deflater_create(engine._h, self.n, container, int(mode), int(flags),
+                                                          C.byref(self._d)), "flate_hip_deflater_create")
+
+    def feed(self, pieces, op=0, caps=None):
+        """pieces: n bytes-like, or None = an empty piece.  op: FEED_MORE / FEED_FLUSH / FEED_FINISH for all, or one per
+        stream.  caps: output slot per stream (default: room for everything the piece can produce).
+        Returns (list of output bytes, list of statuses, list of consumed input bytes)."""
+        n = self.n
+        if len(pieces) != n:
+            raise ValueError("feed() wants %d pieces" % n)
+        if isinstance(op, int):
+            op = [op] * n
+        if caps is None or isinstance(caps, int):
+            caps = [caps] * n
+        data = [b"" if p is None else bytes(p) for p in pieces]
+        ops = np.array([int(o) for o in op], dtype=np.uint8)
+        cap = np.array([caps[i] if caps[i] is not None else len(data[i]) + 5 * (len(data[i]) // 65535) + (1 << 17)
+                        for i in range(n)], dtype=np.uint64)
+        in_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(d) for d in data], dtype=np.uint64), out=in_off[1:])
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(cap, out=out_off[1:])
+        blob = np.frombuffer(b"".join(data), dtype=np.uint8) if in_off[-1] else np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(int(out_off[-1]), 1), dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint64)
+        consumed = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int32)
+        rc = self._eng._L.flate_hip_deflater_feed(self._eng._h, self._d, blob.ctypes.data, in_off.ctypes.data,
+                                                  ops.ctypes.data, out.ctypes.data, out_off.ctypes.data,
+                                                  out_len.ctypes.data, consumed.ctypes.data, status.ctypes.data,
+                                                  MEM_HOST)
+        self._eng._check(rc, "flate_hip_deflater_feed")
+        outs = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
+        return outs, [int(v) for v in status], [int(v) for v in consumed]
+
+    def reset(self, indices):
+        """Start a new stream (a new gzip / zlib member) on these streams."""
+        w = np.ascontiguousarray(list(indices), dtype=np.uint32)
+        rc = self._eng._L.flate_hip_deflater_reset(self._eng._h, self._d, w.ctypes.data if w.size else None, w.size)
+        self._eng._check(rc, "flate_hip_deflater_reset")
+
+    def close(self):
+        if getattr(self, "_d", None) and self._d.value and self._eng._h.value:
+            self._eng._L.flate_hip_deflater_destroy(self._eng._h, self._d)
+        self._d = C.c_void_p()
 
     def __del__(self):
         try:

@@ -278,6 +278,49 @@ int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const ui
                             const uint8_t* final_, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
                             uint64_t* consumed, int32_t* status, int memkind);
 
+/*
+ * Resumable compress: n_streams independent huffman-only (mode 1) or store-only (mode 0) compressors whose state stays
+ * in device memory between calls -- the reference's SimpleCompressor (deflate.zig:449-529) written to piece by piece.
+ * Levels 4..9 are not resumable yet: flate_hip_deflater_create returns FLATE_HIP_E_UNSUPPORTED for them.  `flags`: 0 or
+ * FLATE_HIP_DEFLATE_REPAIR_Q1, which has no effect in modes 0 and 1 (Q1 is a seam between token blocks); other bits
+ * are FLATE_HIP_E_INVALID_ARG.
+ *
+ * One feed, per stream i, with op[i] one of FLATE_HIP_FEED_*:
+ *   in[in_off[i] .. in_off[i+1])  the stream's next piece (at most 0xffef0000 bytes), written to the compressor
+ *   op[i]                         MORE: write(piece); FLUSH: write(piece) then flush(); FINISH: write(piece) then finish()
+ *   out[out_off[i] .. out_off[i+1])  slot for this feed's output (any size, 0 included); out_len[i] bytes written
+ *   consumed[i]                   the piece's length (taken whole) or 0 (not taken: send it and its op again)
+ *   status[i]                     FLATE_HIP_ST_NEED_INPUT (everything delivered, more may be written),
+ *                                 FLATE_HIP_ST_NEED_OUTPUT (output is still pending after this feed), or, after FINISH
+ *                                 with everything delivered, the status flate_hip_compress_batch reports for the whole
+ *                                 input (0).
+ * A feed takes no input from a stream that still has output from an earlier feed: it only hands that output into the
+ * slot (consumed 0), and reports NEED_INPUT or the final status once nothing is left.  The output of all feeds from create / reset to FINISH, concatenated, does not depend on how the input was cut:
+ * with no FLUSH it is flate_hip_compress_batch of the whole input, with FLUSH feeds flate_hip_compress_flush with flush
+ * points at the ends of those feeds -- and streams may be longer than 4 GiB (ISIZE is the length mod 2^32).  After a
+ * MORE feed every complete 65535-byte block has been handed out but the last partial byte; after a FLUSH feed
+ * everything up to the flush's marker.  A finished stream takes nothing and reports its final status until reset.  A
+ * stream with an empty piece, op MORE and an empty slot is skipped (state untouched).
+ * Memory: per stream 64 KiB of buffer and 24 bytes of state (carry bits, running checksum, 64-bit total) on the device,
+ * whatever the stream's length; a feed's workspace is about 2.1 x the bytes fed plus 64 KiB per stream fed, and output
+ * that did not fit a slot is kept (at most one feed's output per stream).  flate_hip_debug_device_bytes reports what
+ * the handle's deflaters hold.
+ * FLATE_HIP_MEM_HOST: synchronous.  FLATE_HIP_MEM_DEVICE: every array is device memory; the feed reads the offsets and
+ * ops back to the host, builds its block tables there and waits for the kernels (not capturable in a graph).
+ * flate_hip_deflater_reset (host array `which`) starts a new stream (a new gzip / zlib member) on the listed streams.
+ */
+typedef struct flate_hip_deflater* flate_hip_deflater_t;
+enum { FLATE_HIP_FEED_MORE = 0, FLATE_HIP_FEED_FLUSH = 1, FLATE_HIP_FEED_FINISH = 2 };
+int flate_hip_deflater_create(flate_hip_handle h, uint32_t n_streams, int container, int mode, uint32_t flags,
+                              flate_hip_deflater_t* d);
+int flate_hip_deflater_destroy(flate_hip_handle h, flate_hip_deflater_t d);
+int flate_hip_deflater_reset(flate_hip_handle h, flate_hip_deflater_t d, const uint32_t* which, uint32_t n_which);
+int flate_hip_deflater_feed(flate_hip_handle h, flate_hip_deflater_t d, const uint8_t* in, const uint64_t* in_off,
+                            const uint8_t* op, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                            uint64_t* consumed, int32_t* status, int memkind);
+/* test seam: device bytes the handle's deflaters hold (state, buffers, feed workspace, pending output) */
+int flate_hip_debug_device_bytes(flate_hip_handle h, uint64_t* bytes);
+
 /* The containers' checksums on their own (container.zig:168-206: std.hash.Crc32 / Adler32 over the raw
  * input): container 1 = CRC-32, 2 = Adler-32 of a host buffer, computed by the checksum kernels; and the
  * checksum of a concatenation from the checksums of its parts (value_b over len_b bytes follows value_a).
