@@ -27,6 +27,7 @@
 #include "kernels_parse.h"
 #include "kernels_walk.h"
 #include "kernels_stream.h"
+#include "pass_plan.h"
 #include "stream_tables.h"
 
 namespace {
@@ -149,6 +150,8 @@ struct flate_hip_ctx {
     bool ms_pending = false;
     bool ck_pending = false;
     uint64_t dfl_bytes = 0;  // device memory the handle's deflaters hold (flate_hip_debug_device_bytes)
+    uint64_t ws_bytes = 0;   // device memory ensure() holds for the handle (flate_hip_debug_workspace_bytes)
+    bool ws_fixed = false;   // the two-stream passes are being enqueued: ensure() may not grow a buffer (compress_impl)
     // last level 4..9 call, for the debug seam
     uint32_t dbg_pass_chunks = 0;
     uint32_t dbg_first_chunk = 0;
@@ -180,24 +183,34 @@ namespace {
 
 int ensure(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
     if (bytes <= b.cap) return FLATE_HIP_OK;
+    if (h->ws_fixed) {
+        // (the buffers may be slices of themselves and the second compute stream may still use them: never freed here)
+        h->last_error = "workspace of the two-stream passes too small: " + std::to_string(bytes) + " bytes asked, " +
+                        std::to_string(b.cap) + " held";
+        return FLATE_HIP_E_LAUNCH;
+    }
     if (b.p) {
         (void)hipStreamSynchronize(h->stream);
         (void)hipFree(b.p);
+        h->ws_bytes -= b.cap;
         b.p = nullptr;
         b.cap = 0;
     }
     size_t want = bytes + bytes / 8 + 256;
     hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess) {
+        (void)hipGetLastError();  // (the failure is answered here: a later HIP_OK(hipGetLastError()) must not see it)
         want = bytes;
         e = hipMalloc(&b.p, want);
     }
     if (e != hipSuccess) {
+        (void)hipGetLastError();
         h->last_error = std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e);
         b.p = nullptr;
         return FLATE_HIP_E_ALLOC;
     }
     b.cap = want;
+    h->ws_bytes += want;
     return FLATE_HIP_OK;
 }
 
@@ -710,20 +723,26 @@ int fetch_offsets(flate_hip_ctx* h, const uint64_t* off, uint32_t n, int memkind
 
 
 // workspace of a chunk-path pass of nc chunks (levels 4..9)
+// (pass_plan.h: the bytes per chunk of every buffer)
 int ensure_lz_workspace(flate_hip_ctx* h, uint32_t nc, uint32_t chain) {
     int rc;
-    const size_t per = (size_t)nc * FL_CHUNK_STRIDE;
-    if (chain >= FL_BULK_MIN_CHAIN) {
-        if ((rc = ensure(h, h->links, per * 4 * sizeof(uint16_t)))) return rc;  // per chunk [L4 | L6 | L8 | RK] (kernels_walk.h)
-    } else {
-        if ((rc = ensure(h, h->S, per * sizeof(uint16_t)))) return rc;          // chain links (kernels_parse.h)
-    }
-    if ((rc = ensure(h, h->desc, per * sizeof(uint32_t)))) return rc;   // anchor descriptors
-    if ((rc = ensure(h, h->marks, per / 8))) return rc;                 // true anchors, one bit per position
-    if ((rc = ensure(h, h->tokens, per * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(h, h->ntok, sizeof(uint32_t) * nc))) return rc;
-    if ((rc = ensure(h, h->cflag, sizeof(uint32_t) * nc))) return rc;
+    const bool bulk = chain >= FL_BULK_MIN_CHAIN;
+    const fl_lz_sizes z = fl_lz_chunk_sizes(bulk);
+    if ((rc = ensure(h, bulk ? h->links : h->S, z.links * nc))) return rc;  // [L4 | L6 | L8 | RK] a chunk (kernels_walk.h) / chain links (kernels_parse.h)
+    if ((rc = ensure(h, h->desc, z.desc * nc))) return rc;                 // anchor descriptors
+    if ((rc = ensure(h, h->marks, z.marks * nc))) return rc;               // true anchors, one bit per position
+    if ((rc = ensure(h, h->tokens, z.tokens * nc))) return rc;
+    if ((rc = ensure(h, h->ntok, z.ntok * nc))) return rc;
+    if ((rc = ensure(h, h->cflag, z.cflag * nc))) return rc;
     return FLATE_HIP_OK;
+}
+// plans, histograms and checksum words of a chunk-path pass of nb block slots (pass_plan.h)
+int ensure_block_workspace(flate_hip_ctx* h, uint64_t nb) {
+    int rc;
+    const fl_blk_sizes b = fl_block_slot_sizes();
+    if ((rc = ensure(h, h->plans, b.plan * nb))) return rc;
+    if ((rc = ensure(h, h->hist, b.hist * nb))) return rc;
+    return ensure(h, h->cks, b.cks * nb);
 }
 
 // shared back end of every pass: block planner, offset scan, bit packer
@@ -835,7 +854,7 @@ int enqueue_pass(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t n
     if (mode >= 4) {
         if ((rc = ensure_lz_workspace(h, nc, prm.chain))) return rc;
         if (prm.chain >= FL_BULK_MIN_CHAIN) {
-            HIP_OK(h, hipMemsetAsync(h->marks.p, 0, (size_t)nc * FL_CHUNK_STRIDE / 8, st));  // k_lz_walk stores the anchors in (k_lz_chain clears its chunk's itself)
+            HIP_OK(h, hipMemsetAsync(h->marks.p, 0, fl_lz_chunk_sizes(true).marks * nc, st));  // k_lz_walk stores the anchors in (k_lz_chain clears its chunk's itself)
             // levels 8 and 9 (chains of 1024 / 4096 candidates): the reference's chain and two sparser ones in global
             // memory, the automaton over them (kernels_walk.h): a walk is 1.4 steps per byte instead of 14
             {
@@ -1381,6 +1400,7 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->sblocks, &h->st_in, &h->st_out, &h->st_inoff, &h->st_outlen, &h->st_status,
                       &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot})
         if (b->p) (void)hipFree(b->p);
+    h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->xfer_events) (void)hipEventDestroy(e);
     if (h->c2_ev0) (void)hipEventDestroy(h->c2_ev0);
@@ -1667,7 +1687,15 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
 
     // A pass is a run of consecutive chunks of one kind: at levels 4..9 inputs of up to 65535 bytes
     // take the chunk path (kernels_lz.h), longer ones the whole-stream path (kernels_stream.h).
-    const size_t pass_limit = (pin_in || pin_out) ? std::min(pass_chunk_limit(h), host_pass_chunk_limit(h)) : pass_chunk_limit(h);
+    // (pass_plan.h: the sub-batch size, the merged tail, the ramp)
+    fl_pass_cfg pcfg;
+    pcfg.n_chunks = n_chunks;
+    pcfg.host_pass_chunks = host_pass_chunk_limit(h);
+    pcfg.max_pass_chunks = pass_chunk_limit(h);
+    pcfg.pinned = pin_in || pin_out;  // (never with a plan: planned batches are device memory)
+    pcfg.ramp = !h->knobs.no_ramp;
+    pcfg.planned = pl != nullptr;
+    const size_t pass_limit = fl_pass_limit(pcfg);
     const uint64_t stream_pass_bytes = stream_pass_byte_limit(h);
     if (pin_out) HIP_OK(h, hipStreamSynchronize(h->s_out));  // (nothing of an earlier call may still read st_out)
     // Pinned output: the link is shared by both directions (57 GB/s one way, 28.6 each way at once: tools/pcie_probe.py),
@@ -1722,7 +1750,8 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     std::deque<std::vector<uint32_t>> keep_blk;
     std::deque<std::vector<fl_sblock>> keep_sb;
     // On the pinned path the passes are enqueued without a host wait in between and the copies on the input stream read the
-    // vectors above: whichever way this function is left (an error in the middle included), they are outlived by the copies.
+    // vectors above: whichever way this function is left (an error in the middle included), they are outlived by the copies,
+    // and on two compute streams (set below) no kernel of the second one still writes the caller's output.
     struct PassGuard {
         flate_hip_ctx* h;
         bool on;
@@ -1738,18 +1767,14 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     // Round 6: TWO compute streams.  A sub-batch's six kernels each end in a tail that fills the chip less and less (1024 chunks are
     // four per CU: 2.15 ms a sub-batch where a quarter of the whole batch's 6.6 ms would be 1.65) and the next sub-batch's first
     // kernel waits behind the last one's tail.  The sub-batches alternate between the caller's stream and a second one -- every
-    // per-pass buffer is a slice of a batch-wide workspace, so two passes never touch the same bytes -- and the kernels of sub-batch
+    // per-pass buffer has a slice per stream, so two passes that may run at once never touch the same bytes -- and the kernels of sub-batch
     // k + 1 start as soon as its input is there and run into the tails of k's: 10.3 -> 10.0 ms per 256 MiB in one process, 11.7 ->
-    // 10.1 in another (bench e2e_host).  Levels 4-7, every input on the chunk path.  What lost (profiles/r06_host_path.txt): the
+    // 10.1 in another (bench e2e_host).  Levels 4-9, every input on the chunk path.  What lost (profiles/r06_host_path.txt): the
     // tokenizers of all sub-batches in a row on one stream with the chains and the back ends on streams of higher priority beside
     // them, 11.0 ms -- k_lz_parse takes a CU's whole LDS, a single small workgroup on a CU keeps the next tokenizer workgroup off it,
     // and every kernel ran a quarter to a half longer than alone.
     // (planned device batches of more than one pass take the same way: flate_hip_compress_planned)
     const bool planned_run = pl && pl->ready;
-    if (planned_run) {
-        blk_total = 0;
-        for (const flate_hip_plan::Pass& pp : pl->passes) blk_total += pp.nb;
-    }
     bool two = ((pinned_passes && (size_t)n_chunks > pass_limit) || (planned_run && pl->passes.size() > 1)) && mode >= 4 && !fs && !h->knobs.one_stream;
     for (uint32_t i = 0; two && i < n_chunks; i++) two = chunks[i].in_len <= FLATE_HIP_MAX_LZ_CHUNK;
     if (two && !h->s_c2) {
@@ -1768,18 +1793,58 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
             two = false;
         }
     }
+    // The two streams' workspace is TWO slices of every per-pass buffer, each as large as the largest pass (pass_plan.h: the
+    // merged tail, not the sub-batch size); pass k runs on stream k & 1 in slice k & 1.  Passes k and k + 2 run in order on one
+    // stream, so pass k + 2 reuses pass k's bytes only after pass k's last kernel.  The other streams that touch a slice:
+    // - s_ck (k_checksum of containers 1 and 2 at levels 4..7, launch_checksum_side) writes the pass's `cks` slice behind an
+    //   event recorded on the pass's stream after the pass's own k_lz_chain -- after pass k's back end, which reads that slice;
+    // - s_in writes the batch-wide tables and input only (a slice of their own per pass), never the workspace.
+    // Everything is sized HERE, before the first pass is enqueued: ensure() synchronises only h->stream, which enqueue_sliced
+    // swaps, and would free a buffer the other stream still uses.  Until every pass is enqueued ensure() refuses to grow a
+    // buffer (h->ws_fixed): enqueue_pass's ensure_lz_workspace on the slice is a check, never a reallocation of a shifted buffer.
+    // Slices that cannot be had: the passes one after the other on the caller's stream (round 5's way).
+    std::vector<fl_pass> sched;  // the passes of the two-stream path
+    uint64_t slice_nc = 0, slice_nb = 0;
+    auto size_two_slices = [&](uint64_t nc_, uint64_t nb_) -> int {
+        int r;
+        if ((r = ensure_lz_workspace(h, (uint32_t)(2 * nc_), prm.chain))) return r;
+        return ensure_block_workspace(h, 2 * nb_);
+    };
     if (two) {
-        // the batch-wide workspace (the passes' slices: c0 chunks / the blocks before the pass into every buffer)
-        if ((rc = ensure_lz_workspace(h, n_chunks, prm.chain))) return rc;
-        if ((rc = ensure(h, h->plans, sizeof(fl_block_plan) * (size_t)blk_total))) return rc;
-        if ((rc = ensure(h, h->hist, sizeof(uint32_t) * 320 * (size_t)blk_total))) return rc;
-        if ((rc = ensure(h, h->cks, sizeof(uint32_t) * 2 * (size_t)blk_total))) return rc;
+        if (planned_run) {
+            for (size_t k = 0; k < pl->passes.size(); k++) {
+                fl_pass p;
+                p.c0 = sched.empty() ? 0 : sched.back().c0 + sched.back().nc;
+                p.nc = pl->passes[k].nc;
+                p.stream = (uint32_t)(k & 1u);
+                sched.push_back(p);
+                slice_nc = std::max<uint64_t>(slice_nc, pl->passes[k].nc);
+                slice_nb = std::max<uint64_t>(slice_nb, pl->passes[k].nb);
+            }
+        } else {
+            slice_nc = fl_pass_schedule(pcfg, sched);
+            slice_nb = 2 * slice_nc;  // (levels 4..9 on the chunk path: two block slots per chunk)
+            // (up to 1.5 x the limit the merged tail is ONE pass: a second slice would never be used)
+            if (sched.size() < 2) two = false;
+        }
+        if (two && size_two_slices(slice_nc, slice_nb)) {
+            (void)hipGetLastError();
+            two = false;
+        }
+    }
+    pass_guard.on = pinned_passes || two;
+    struct WsFixed {
+        flate_hip_ctx* h;
+        ~WsFixed() { h->ws_fixed = false; }
+    } ws_fixed{h};
+    h->ws_fixed = two;
+    if (two) {
         // the second stream behind what the caller's stream holds so far (the cleared lengths and statuses)
         HIP_OK(h, hipEventRecord(h->c2_ev0, st));
         HIP_OK(h, hipStreamWaitEvent(h->s_c2, h->c2_ev0, 0));
         if (h->ms_pending) HIP_OK(h, hipStreamWaitEvent(h->s_c2, h->ms_ev1, 0));  // ... and behind the clearing of the slots
     }
-    struct WsShift {  // a pass's view of the batch-wide workspace: every buffer from its slice on (undone when the pass is enqueued)
+    struct WsShift {  // a pass's view of the two-slice workspace: every buffer from its slice on (undone when the pass is enqueued)
         std::vector<std::pair<DevBuf*, size_t>> undo;
         void add(DevBuf& b, size_t bytes) {
             b.p = (uint8_t*)b.p + bytes;
@@ -1793,20 +1858,30 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
             }
         }
     };
-    // a pass over its slice of every per-pass buffer (c0 chunks / b0 blocks into the batch-wide workspace), its kernels on `sq`
-    auto enqueue_sliced = [&](hipStream_t sq, uint32_t nc_, uint32_t nb_, uint32_t c0_, size_t b0, const fl_chunk* dch_, const uint32_t* dbc_,
+    // a pass over slice k & 1 of every per-pass buffer, its kernels on that stream
+    auto enqueue_sliced = [&](size_t k, uint32_t nc_, uint32_t nb_, uint32_t c0_, const fl_chunk* dch_, const uint32_t* dbc_,
                               const fl_sblock* dsb_) -> int {
+        if (k >= sched.size() || sched[k].c0 != c0_ || sched[k].nc != nc_ || nc_ > slice_nc || nb_ > slice_nb) {
+            h->last_error = "two-stream pass " + std::to_string(k) + " (" + std::to_string(c0_) + " + " + std::to_string(nc_) +
+                            " chunks) is not the scheduled one";
+            return FLATE_HIP_E_LAUNCH;
+        }
+        const uint32_t slice = sched[k].stream;
+        hipStream_t sq = slice ? h->s_c2 : st;
         WsShift ws;
-        const size_t pos0 = (size_t)c0_ * FL_CHUNK_STRIDE;
-        ws.add(h->plans, sizeof(fl_block_plan) * b0);
-        ws.add(h->hist, sizeof(uint32_t) * 320 * b0);
-        ws.add(h->cks, sizeof(uint32_t) * 2 * b0);
-        if (prm.chain >= FL_BULK_MIN_CHAIN) ws.add(h->links, pos0 * 4 * sizeof(uint16_t)); else ws.add(h->S, pos0 * sizeof(uint16_t));
-        ws.add(h->desc, pos0 * sizeof(uint32_t));
-        ws.add(h->marks, pos0 / 8);
-        ws.add(h->tokens, pos0 * sizeof(uint32_t));
-        ws.add(h->ntok, sizeof(uint32_t) * c0_);
-        ws.add(h->cflag, sizeof(uint32_t) * c0_);
+        const size_t c_sl = (size_t)slice * slice_nc, b0 = (size_t)slice * slice_nb;
+        const bool bulk = prm.chain >= FL_BULK_MIN_CHAIN;
+        const fl_lz_sizes z = fl_lz_chunk_sizes(bulk);
+        const fl_blk_sizes bs = fl_block_slot_sizes();
+        ws.add(h->plans, bs.plan * b0);
+        ws.add(h->hist, bs.hist * b0);
+        ws.add(h->cks, bs.cks * b0);
+        ws.add(bulk ? h->links : h->S, z.links * c_sl);
+        ws.add(h->desc, z.desc * c_sl);
+        ws.add(h->marks, z.marks * c_sl);
+        ws.add(h->tokens, z.tokens * c_sl);
+        ws.add(h->ntok, z.ntok * c_sl);
+        ws.add(h->cflag, z.cflag * c_sl);
         hipStream_t saved = h->stream;
         h->stream = sq;
         const int r = enqueue_pass(h, prm, nc_, nb_, c0_, dch_, dbc_, dsb_, d_in, d_out, d_outlen, d_status);
@@ -1832,11 +1907,8 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
         uint64_t pass_bytes = 0;
         // (a sub-batch of the pinned path costs about 0.9 ms whatever it holds: a tail of less than half a sub-batch
         // goes with the one before it)
-        size_t limit = pass_limit;
-        if (pinned_passes && (size_t)(n_chunks - c0) < pass_limit + pass_limit / 2) limit = std::min(pass_chunk_limit(h), (size_t)(n_chunks - c0));
         // (the GPU idles until the first sub-batch has crossed the link: the first two are a quarter and a half)
-        const bool ramp = !h->knobs.no_ramp;
-        if (ramp && pinned_passes && n_chunks >= 3 * pass_limit && pass_count < 2) limit = std::min(pass_limit, std::max<size_t>(64, pass_limit >> (2 - pass_count)));  // (never above the configured bound: FLATE_HIP_MAX_PASS_CHUNKS)
+        const size_t limit = (size_t)fl_pass_cap(pcfg, c0, pass_count);
         for (nc = 0; c0 + nc < n_chunks; nc++) {
             const fl_chunk& c = chunks[c0 + nc];
             if ((mode >= 4 && (fs || c.in_len > FLATE_HIP_MAX_LZ_CHUNK)) != stream) break;
@@ -1863,14 +1935,12 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
             prm.n_chunks = nc;
             prm.n_blocks = nb;
             prm.stream = 0;
-            if ((rc = ensure(h, h->plans, sizeof(fl_block_plan) * (size_t)nb))) return rc;
-            if ((rc = ensure(h, h->hist, sizeof(uint32_t) * 320 * (size_t)nb))) return rc;
-            if ((rc = ensure(h, h->cks, sizeof(uint32_t) * 2 * (size_t)nb))) return rc;
-            if (two) {
-                hipStream_t stq = (pass_index & 1u) ? h->s_c2 : st;
-                if ((rc = enqueue_sliced(stq, nc, nb, c0, (size_t)blk_base, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr))) return rc;
-                blk_base += nb;
-            } else if ((rc = enqueue_pass(h, prm, nc, nb, c0, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr,
+            if (two) {  // (sized before the first pass)
+                if ((rc = enqueue_sliced(pass_index, nc, nb, c0, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr))) return rc;
+                continue;
+            }
+            if ((rc = ensure_block_workspace(h, nb))) return rc;
+            if ((rc = enqueue_pass(h, prm, nc, nb, c0, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr,
                                           d_in, d_out, d_outlen, d_status))) {
                 return rc;
             }
@@ -1920,9 +1990,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
             if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * nc))) return rc;
             if ((rc = ensure(h, h->blk_chunk, sizeof(uint32_t) * nb))) return rc;
         }
-        if ((rc = ensure(h, h->plans, sizeof(fl_block_plan) * (size_t)nb))) return rc;
-        if ((rc = ensure(h, h->hist, sizeof(uint32_t) * 320 * (size_t)nb))) return rc;
-        if ((rc = ensure(h, h->cks, sizeof(uint32_t) * 2 * (size_t)nb))) return rc;
+        if (!two && (rc = ensure_block_workspace(h, nb))) return rc;  // (the two-stream path's are sized before the first pass)
         fl_chunk* tab_chunks = (fl_chunk*)h->chunks.p + (sliced ? c0 : 0u);
         uint32_t* tab_blk = (uint32_t*)h->blk_chunk.p + (sliced ? blk_base : 0u);
         if (sliced) {
@@ -1953,7 +2021,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
         }
         // the host vectors must outlive the async copies
         if (!(pin_in || pin_out) || stream || planning) HIP_OK(h, hipStreamSynchronize(st));
-        const bool alt = two && (pass_index & 1u) != 0;  // every other sub-batch on the second compute stream
+        const bool alt = two && pass_index < sched.size() && sched[pass_index].stream != 0;  // every other sub-batch on the second compute stream
         hipStream_t stp = alt ? h->s_c2 : st;
         if (ev_in) HIP_OK(h, hipStreamWaitEvent(stp, ev_in, 0));
         if (planning) {
@@ -1999,7 +2067,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
                 HIP_OK(h, hipStreamWaitEvent(h->s_in, ev_tab, 0));
             }
         } else if (two) {
-            if ((rc = enqueue_sliced(stp, nc, nb, c0, (size_t)(blk_base - nb), dch, dbc, dsb))) return rc;
+            if ((rc = enqueue_sliced(pass_index, nc, nb, c0, dch, dbc, dsb))) return rc;
         } else {
             if ((rc = enqueue_pass(h, prm, nc, nb, c0, dch, dbc, dsb, d_in, d_out, d_outlen, d_status))) return rc;
         }
@@ -2060,6 +2128,21 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     if (two) {  // the caller's stream behind the second one
         HIP_OK(h, hipEventRecord(h->c2_ev1, h->s_c2));
         HIP_OK(h, hipStreamWaitEvent(st, h->c2_ev1, 0));
+        // the caller's stream is behind the second one: from here on nothing of s_c2 outlives the call unseen, and a planned
+        // call only enqueues (flate_hip_compress_planned) -- the host waits below only where it did without two streams
+        pass_guard.on = pinned_passes;
+    }
+    // every pass is enqueued and the caller's stream is behind both: the buffers may grow again (copy_out_host below packs
+    // a pageable caller's output in a buffer of its own)
+    h->ws_fixed = false;
+    if (planning && mode >= 4 && pl->passes.size() > 1 && !h->knobs.one_stream) {
+        // the planned calls will take two streams: their slices now too (if they cannot be had, the calls take one stream)
+        uint64_t snc = 0, snb = 0;
+        for (const flate_hip_plan::Pass& pp : pl->passes) {
+            snc = std::max<uint64_t>(snc, pp.nc);
+            snb = std::max<uint64_t>(snb, pp.nb);
+        }
+        if (size_two_slices(snc, snb)) (void)hipGetLastError();
     }
     if (landing) {
         // everything is enqueued: take the passes' output out of the mirror as they land
@@ -2191,6 +2274,7 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
         if (h->sp_pool.cap > (2ull << 30)) {
             (void)hipStreamSynchronize(st);
             (void)hipFree(h->sp_pool.p);
+            h->ws_bytes -= h->sp_pool.cap;
             h->sp_pool.p = nullptr;
             h->sp_pool.cap = 0;
         }
@@ -3171,6 +3255,18 @@ int flate_hip_deflater_feed(flate_hip_handle h, flate_hip_deflater_t d, const ui
 int flate_hip_debug_device_bytes(flate_hip_handle h, uint64_t* bytes) {
     if (!h || !bytes) return FLATE_HIP_E_INVALID_ARG;
     *bytes = h->dfl_bytes;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_debug_workspace_bytes(flate_hip_handle h, uint64_t* bytes) {
+    if (!h || !bytes) return FLATE_HIP_E_INVALID_ARG;
+    // what ensure() holds, less the buffers that hold the batch itself: the staged copies of a host call's data and the
+    // batch's chunk and block tables grow with the batch by design, the passes' workspace must not
+    uint64_t batch = 0;
+    for (const DevBuf* b : {&h->st_in, &h->st_out, &h->st_inoff, &h->st_outlen, &h->st_status, &h->st_consumed, &h->st_pack,
+                            &h->st_packoff, &h->st_slot, &h->chunks, &h->blk_chunk})
+        batch += b->cap;
+    *bytes = h->ws_bytes - batch;
     return FLATE_HIP_OK;
 }
 

@@ -235,6 +235,13 @@ class Engine:
         self._check(self._L.flate_hip_debug_device_bytes(self._h, C.byref(v)), "flate_hip_debug_device_bytes")
         return int(v.value)
 
+    def workspace_bytes(self):
+        """Device bytes the handle keeps as workspace of its passes (not the staged copies of a batch's data, not its chunk
+        tables, not the deflaters')."""
+        v = C.c_uint64(0)
+        self._check(self._L.flate_hip_debug_workspace_bytes(self._h, C.byref(v)), "flate_hip_debug_workspace_bytes")
+        return int(v.value)
+
     def gather_streams_device(self, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr, dst_off_ptr):
         """Pack the produced streams back to back in device memory (dst_off gets n_chunks + 1 entries)."""
         rc = self._L.flate_hip_gather_streams(self._h, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr,

@@ -320,6 +320,11 @@ int flate_hip_deflater_feed(flate_hip_handle h, flate_hip_deflater_t d, const ui
                             uint64_t* consumed, int32_t* status, int memkind);
 /* test seam: device bytes the handle's deflaters hold (state, buffers, feed workspace, pending output) */
 int flate_hip_debug_device_bytes(flate_hip_handle h, uint64_t* bytes);
+/* test seam: device bytes the handle holds as workspace of its passes (the buffers it grows on demand and keeps across
+ * calls), not counting the buffers that hold a batch itself -- the staged copies of a host call's input, output, lengths
+ * and statuses, and the batch's chunk and block tables -- and not the deflaters' (flate_hip_debug_device_bytes).  A
+ * chunk-path batch on two compute streams keeps two slices of its largest pass, whatever the number of passes. */
+int flate_hip_debug_workspace_bytes(flate_hip_handle h, uint64_t* bytes);
 
 /* The containers' checksums on their own (container.zig:168-206: std.hash.Crc32 / Adler32 over the raw
  * input): container 1 = CRC-32, 2 = Adler-32 of a host buffer, computed by the checksum kernels; and the
