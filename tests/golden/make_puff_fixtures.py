@@ -23,6 +23,7 @@ def streams():
     import test_gpu_compress as gc
     import test_gpu_inflate as gi
     import test_oracle_inflate_pins as pins
+    import _deflate_synth as synth
     from _inflate_edge_cases import CASES
 
     def golden(*parts):
@@ -37,6 +38,10 @@ def streams():
             yield O.compress(data, O.RAW, mode), len(data) + 16
     for _, s in sorted(CASES.items()):
         yield s, 80000
+    for _, (s, want) in sorted(synth.CASES.items()):  # test_synth_directed_cases_agree_with_every_reference
+        yield s, pins.synth_cap(want)
+    for s, want in synth.random_streams(pins.SYNTH_SEED, pins.SYNTH_STORED):  # (the sweep's other seeds: only where puff.c is built)
+        yield s, pins.synth_cap(want)
     for c in gi.puff_mutants()[1]:
         yield c, 1 << 17
     for level in (4, 6, 9):  # test_q1_streams_are_reported_and_repairable: the repaired raw streams

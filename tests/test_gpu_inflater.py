@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import _big_member as B
+import _deflate_synth as S
 import _inflate_edge_cases as E
 import _oracle as O
 from conftest import golden
@@ -84,6 +85,43 @@ def test_every_split_point_edge_cases(name):
     st = run_two_feeds(eng, data, 0)
     want_st, _, _ = O.decompress(data, 0)
     assert O.STATUS[st] == want_st
+
+
+@pytest.mark.parametrize("name", S.SMALL)
+def test_every_split_point_synth_cases(name):
+    """tests/_deflate_synth.py, the cases of at most 12000 bytes (splits() is exhaustive): codes at the tables' edges, 48-bit
+    tokens, degenerate trees, header fields at their limits -- the split points inside the longest header among them --, tiny
+    blocks, and the streams cut inside headers and long tokens.  The status is the oracle's, by the name written next to the
+    case; the bytes are the generator's."""
+    eng = engine()
+    data, want = S.CASES[name]
+    assert len(data) <= 12000
+    st = run_two_feeds(eng, data, 0)
+    assert O.STATUS[st] == (S.INFO[name]["error"] or "Ok")
+    if want is not None:
+        assert one_shot(eng, [data], 0)[0][0] == want
+
+
+@pytest.mark.parametrize("flags", [0, 1])
+def test_synth_long_streams_in_random_pieces(flags):
+    """Families 5 (thousands of tiny blocks) and 8 (big random streams), and the random sweep: 8 copies of every long stream and
+    one of every random stream, each in four pieces cut at random places, into slots of random sizes.  Reference-strict
+    (flags = 1): the streams with a repeat across the two length lists end with InvalidDynamicBlockHeader, as the oracle says."""
+    eng = engine()
+    info = []
+    items = [(n,) + S.CASES[n] + (S.INFO[n]["q6"],) for n in S.LARGE + ["tiny_blocks_60"] for _ in range(8)]
+    items += [("seed %d" % (6000 + k), s, want, q6) for k, ((s, want), (q6, _)) in
+              enumerate(zip(S.random_streams(6000, 100, info), info))]
+    outs, st, used = feed_random_pieces(eng, [it[1] for it in items], random.Random(11 + flags), flags=flags)
+    n_q6 = 0
+    for (name, stream, want, q6), o, s_, u in zip(items, outs, st, used):
+        wname = O.decompress(stream, 0, flags, cap=len(want) + 8)[0]
+        assert wname == ("InvalidDynamicBlockHeader" if flags and q6 else "Ok"), name
+        assert O.STATUS.get(s_, s_) == wname, (name, s_, wname)
+        if wname == "Ok":
+            assert o == want and u == len(stream), name
+        n_q6 += wname != "Ok"
+    assert (n_q6 > 0) == (flags == 1)
 
 
 @pytest.mark.parametrize("flags", [0, 1])
@@ -213,37 +251,45 @@ def _config2(eng):
     return chunks, comp
 
 
-def test_scale_config2_four_random_pieces():
-    eng = engine()
-    chunks, comp = _config2(eng)
-    n = len(chunks)
-    rng = random.Random(7)
-    cuts = [sorted(rng.randint(0, len(c)) for _ in range(3)) for c in comp]
-    pieces = [[c[a:b] for a, b in zip([0] + k, k + [len(c)])] for c, k in zip(comp, cuts)]
-    inf = eng.inflater(n, 0)
+def feed_random_pieces(eng, comp, rng, cuts=3, container=0, flags=0):
+    """every stream in cuts + 1 pieces cut at random places, into output slots of random sizes: a piece that is absorbed gives way
+    to the next, the last one is final.  Returns (outputs, statuses, consumed bytes in all)."""
+    n = len(comp)
+    where = [sorted(rng.randint(0, len(c)) for _ in range(cuts)) for c in comp]
+    pieces = [[c[a:b] for a, b in zip([0] + k, k + [len(c)])] for c, k in zip(comp, where)]
+    inf = eng.inflater(n, container, flags)
     outs = [[] for _ in range(n)]
     which, rest = [0] * n, [p[0] for p in pieces]
-    st = [NEED_INPUT] * n
+    st, used = [NEED_INPUT] * n, [0] * n
     try:
         while any(s in (NEED_INPUT, NEED_OUTPUT) for s in st):
             for i in range(n):  # a piece that is absorbed gives way to the next
-                if st[i] == NEED_INPUT and not rest[i] and which[i] < 3:
+                if st[i] == NEED_INPUT and not rest[i] and which[i] < cuts:
                     which[i] += 1
                     rest[i] = pieces[i][which[i]]
             live = [s in (NEED_INPUT, NEED_OUTPUT) for s in st]
-            fin = [which[i] == 3 for i in range(n)]
+            fin = [which[i] == cuts for i in range(n)]
             caps = [rng.randint(258, 70000) for _ in range(n)]
             o, s, c = inf.feed([rest[i] if live[i] else None for i in range(n)], final=fin, caps=caps)
             for i in range(n):
                 if live[i]:
                     outs[i].append(o[i])
                     rest[i] = rest[i][c[i]:]
+                    used[i] += c[i]
                     st[i] = s[i]
     finally:
         inf.close()
+    return [b"".join(o) for o in outs], st, used
+
+
+def test_scale_config2_four_random_pieces():
+    eng = engine()
+    chunks, comp = _config2(eng)
+    n = len(chunks)
+    outs, st, _ = feed_random_pieces(eng, comp, random.Random(7))
     assert st == [0] * n
     for i in range(n):
-        assert b"".join(outs[i]) == chunks[i], i
+        assert outs[i] == chunks[i], i
 
 
 def test_scale_config2_device_memory():

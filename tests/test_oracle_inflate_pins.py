@@ -214,3 +214,100 @@ def test_directed_edge_streams_agree_with_puff():
         assert (name == "Ok") == (rc == 0), (n, name, rc)
         if rc == 0:
             assert pout == O.digest(out), n
+
+
+# ---- synthesized streams (tests/_deflate_synth.py): dynamic blocks no encoder emits.  The generator's own expansion of its token
+# list is the reference for every valid stream; the oracle, puff.c and zlib are checked against it here, on every case.
+SYNTH_SEED, SYNTH_SWEEP, SYNTH_STORED = 0, 400, 100  # random streams: the seeds; how many of them have a stored puff.c verdict
+
+
+def synth_cap(want):
+    return len(want) + 16 if want is not None else 1 << 18
+
+
+def _synth_agrees(name, stream, want, q6, stored_verdict=True):
+    cap = synth_cap(want)
+    st, out, used = O.decompress(stream, O.RAW, 0, cap=cap)
+    assert (st, used) == ("Ok", len(stream)) and out == want, (name, st, used, len(stream))
+    assert pyzlib.decompress(stream, -15) == want, name
+    if stored_verdict or O.puff_available():  # (the rest of the sweep: puff.c itself, where oracle/_ref is built)
+        rc, pout = O.puff_verdict(stream, cap) if stored_verdict else O.puff(stream, cap)
+        assert rc == 0 and (pout if stored_verdict else O.digest(pout)) == O.digest(want), (name, rc)
+    # reference-strict: refused if and only if a code-length repeat crosses from the literal into the distance lengths (Q6)
+    assert O.decompress(stream, O.RAW, 1, cap=cap)[0] == ("InvalidDynamicBlockHeader" if q6 else "Ok"), name
+
+
+def test_synth_directed_cases_agree_with_every_reference():
+    import _deflate_synth as S
+    assert len(S.VALID) >= 25 and len(S.INVALID) >= 25
+    for name in S.VALID:
+        _synth_agrees(name, *S.CASES[name], S.INFO[name]["q6"])
+    for name in S.INVALID:
+        stream = S.CASES[name][0]
+        for flags in (0, 1):
+            st = O.decompress(stream, O.RAW, flags, cap=synth_cap(None))[0]
+            assert st != "Ok", (name, flags)
+            if flags == 0:
+                assert st == S.INFO[name]["error"], (name, st)  # the name written next to the case
+        assert O.puff_verdict(stream, synth_cap(None))[0] != 0, name
+        with pytest.raises(pyzlib.error):
+            pyzlib.decompress(stream, -15)
+
+
+def test_synth_random_sweep_agrees_with_every_reference():
+    import _deflate_synth as S
+    info = []
+    streams = S.random_streams(SYNTH_SEED, SYNTH_SWEEP, info)
+    for k, ((stream, want), (q6, _)) in enumerate(zip(streams, info)):
+        _synth_agrees("seed %d" % (SYNTH_SEED + k), stream, want, q6, stored_verdict=k < SYNTH_STORED)
+    assert 0 < sum(q6 for q6, _ in info) < SYNTH_SWEEP // 4  # some cross (refused with flags = 1), most do not
+
+
+# what each directed family must hold, counted from the generator's own records: a family that drifts, or is deleted, fails here
+SYNTH_FAMILIES = {
+    "lut_edge": ["ll_bits_10", "ll_bits_11", "d_bits_8", "d_bits_9", "d_bits_10", "tok_bits_37", "hdr_with_16", "hdr_with_17",
+                 "hdr_with_18"],
+    "deep15": ["ll_bits_15", "d_bits_15", "tok_bits_48", "tok48_pairs", "dist_eq_written", "error_InvalidMatch"],
+    "degenerate_trees": ["blocks_0_tokens", "error_InvalidCode", "error_IncompleteHuffmanTree"],
+    "header_fields": ["error_InvalidDynamicBlockHeader", "error_MissingEndOfBlockCode", "error_OversubscribedHuffmanTree",
+                      "error_IncompleteHuffmanTree", "error_InvalidBlockType", "hdr_with_16", "hdr_with_17", "hdr_with_18"],
+    "tiny_blocks": ["blocks_0_tokens", "stored_blocks", "fixed_blocks", "hdr_without_16", "hdr_without_17", "hdr_without_18"],
+    "long_header": ["hdr_without_16", "hdr_without_17", "hdr_without_18", "ll_bits_15"],
+    "truncated": ["error_EndOfStream"],
+    "big_random": ["dynamic_blocks", "stored_blocks", "fixed_blocks", "hdr_with_16", "hdr_with_17", "hdr_with_18"],
+}
+
+
+def test_synth_census():
+    """The classes the GPU tests of the synthesized streams rely on, none of them empty -- in the directed cases alone, and per
+    family.  (-s prints the counts, and the bit length of the longest header.)"""
+    import _deflate_synth as S
+    total = S.census()
+    for cls in S.CENSUS_CLASSES:
+        print("%-36s %d" % (cls, total[cls]))
+        assert total[cls] > 0, cls
+    for fam, classes in sorted(SYNTH_FAMILIES.items()):
+        names = [n for n in S.CASES if n.startswith(fam + "_")]
+        assert names, fam
+        c = S.census(names)
+        for cls in classes:
+            print("%-18s %-36s %d" % (fam, cls, c[cls]))
+            assert c[cls] > 0, (fam, cls)
+    assert all(any(n.startswith(fam + "_") for fam in SYNTH_FAMILIES) for n in S.CASES)
+    # Q6 by each of 16, 17, 18, and a 16 that stands at the first distance length
+    assert sum(S.INFO[n]["q6"] for n in S.CASES) >= 4
+    # at least 2000 consecutive tiny blocks in more than 128 KiB; the long streams; the longest header
+    tiny = [n for n in S.LARGE if n.startswith("tiny_blocks_")]
+    assert tiny and S.INFO[tiny[0]]["census"]["dynamic_blocks"] >= 2000
+    assert sum(n.startswith("big_random_") for n in S.LARGE) >= 3
+    assert all(len(S.CASES[n][1]) > 2 << 20 for n in S.LARGE if n.startswith("big_random_"))
+    (longest,) = [n for n in S.CASES if n.startswith("long_header_")]
+    print(longest, S.INFO[longest]["header_bits"], "bits")
+    assert longest == "long_header_%d_bits" % S.INFO[longest]["header_bits"] and S.INFO[longest]["header_bits"] >= 2286
+    # every split point of families 1-4, 6 and 7 is tried by test_gpu_inflater: they fit
+    assert all(n in S.SMALL for n in S.CASES if not n.startswith(("tiny_blocks_2200", "big_random_")))
+    assert sum(n.startswith("truncated_deep15_") for n in S.CASES) == sum(n.startswith("truncated_tiny_blocks_") for n in S.CASES) == 64
+    # the random sweep adds to the classes, it is not needed for any
+    sweep = S.census([], range(SYNTH_SEED, SYNTH_SEED + 40))
+    for cls in ("ll_bits_15", "d_bits_15", "blocks_0_tokens", "stored_blocks", "fixed_blocks", "hdr_with_16", "hdr_with_18"):
+        assert sweep[cls] > 0, cls
