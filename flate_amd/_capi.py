@@ -35,6 +35,7 @@ SYMBOLS = [
     "flate_hip_inflater_create", "flate_hip_inflater_destroy", "flate_hip_inflater_reset", "flate_hip_inflater_feed",
     "flate_hip_deflater_create", "flate_hip_deflater_destroy", "flate_hip_deflater_reset", "flate_hip_deflater_feed",
     "flate_hip_debug_device_bytes", "flate_hip_debug_workspace_bytes",
+    "flate_hip_debug_inflate_paths",
 ]
 
 
@@ -147,6 +148,8 @@ def lib():
     L.flate_hip_debug_device_bytes.restype = C.c_int
     L.flate_hip_debug_workspace_bytes.argtypes = [vp, vp]
     L.flate_hip_debug_workspace_bytes.restype = C.c_int
+    L.flate_hip_debug_inflate_paths.argtypes = [vp, u64p]
+    L.flate_hip_debug_inflate_paths.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.flate_hip_debug_tokens.restype = C.c_int64
     _lib = L

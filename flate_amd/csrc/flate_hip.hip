@@ -151,6 +151,10 @@ struct flate_hip_ctx {
     bool ck_pending = false;
     uint64_t dfl_bytes = 0;  // device memory the handle's deflaters hold (flate_hip_debug_device_bytes)
     uint64_t ws_bytes = 0;   // device memory ensure() holds for the handle (flate_hip_debug_workspace_bytes)
+    // last flate_hip_decompress_batch call, for flate_hip_debug_inflate_paths: streams the span path took / finished,
+    // streams k_inflate_par was launched for, and (counted on the device by k_inflate) those it handed on
+    uint64_t dbg_span_taken = 0, dbg_span_done = 0, dbg_par_taken = 0;
+    DevBuf dbg_par_handed;
     bool ws_fixed = false;   // the two-stream passes are being enqueued: ensure() may not grow a buffer (compress_impl)
     // last level 4..9 call, for the debug seam
     uint32_t dbg_pass_chunks = 0;
@@ -954,6 +958,7 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     for (uint32_t i = 0; i < n_chunks; i++)
         if (chunks[i].in_len >= elig_bytes) elig.push_back(i);
     if (elig.empty() || elig.size() > 256) return 0;
+    h->dbg_span_taken = elig.size();  // (what does not come out whole below is handed on)
     int rc;
     // ---- where spans may start
     std::vector<fl_scan_point> points;
@@ -1319,6 +1324,7 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
         if (hipStreamSynchronize(st) != hipSuccess) return -1;  // (the source is on this stack)
     }
     if (dbg) fprintf(stderr, "[spans] %.3f ms: return\n", since());
+    h->dbg_span_done = (uint64_t)done;
     return done;
 }
 
@@ -1398,7 +1404,7 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->tokens, &h->ntok, &h->cflag, &h->links, &h->wchunks, &h->swins, &h->wexit, &h->shard_sz, &h->tiles, &h->segs, &h->pieces, &h->fpts, &h->zones, &h->nsorted, &h->jmp,
                       &h->exitmap, &h->entry, &h->segtok, &h->tokbase, &h->bound, &h->sgroups, &h->sgroup0, &h->gmap, &h->gentry,
                       &h->sblocks, &h->st_in, &h->st_out, &h->st_inoff, &h->st_outlen, &h->st_status,
-                      &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot})
+                      &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed})
         if (b->p) (void)hipFree(b->p);
     h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
@@ -2267,6 +2273,7 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
     // (what goes back to the caller beyond out_len[i] is zeros, never bytes of an earlier call; the copies of the
     // call before are done: it waited for them)
     if (memkind == FLATE_HIP_MEM_HOST && out_hi > out_lo) HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, out_hi - out_lo, st));
+    h->dbg_span_taken = h->dbg_span_done = h->dbg_par_taken = 0;
     // A few long streams: each by many workgroups at once (spans); what comes out whole is skipped below.
     if (!pin_io) {
         const int done = try_span_inflate(h, st, d_in, chunks, container, flags, d_out, d_outlen, d_status, d_consumed);
@@ -2298,6 +2305,11 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
             n_big += (chunks[i].in_len >= min_bytes || chunks[i].out_cap >= 16ull * min_bytes) ? 1u : 0u;
         use_par = min_bytes && n_big && n_big <= 2048u && !(flags & 1);
         par_min_bytes = min_bytes;
+    }
+    if (use_par) {
+        if ((rc = ensure(h, h->dbg_par_handed, sizeof(uint32_t)))) return rc;
+        HIP_OK(h, hipMemsetAsync(h->dbg_par_handed.p, 0, sizeof(uint32_t), st));
+        for (uint32_t i = 0; i < n_chunks; i++) h->dbg_par_taken += chunks[i].skip ? 0u : 1u;
     }
     // few streams: the latency of one stream decides, give each the large LDS ring (3 per CU);
     // many streams: the small ring keeps 20 per CU in flight
@@ -2352,11 +2364,11 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
             if (large)
                 hipLaunchKernelGGL(k_inflate<FL_INF_RING_LARGE>, dim3(nc), dim3(64), 0, st, d_in, dch, container, flags,
                                    h->crc, d_out, d_outlen + c0, d_status + c0,
-                                   d_consumed ? d_consumed + c0 : nullptr, redo_only);
+                                   d_consumed ? d_consumed + c0 : nullptr, redo_only, (uint32_t*)h->dbg_par_handed.p);
             else
                 hipLaunchKernelGGL(k_inflate<FL_INF_RING_SMALL>, dim3(nc), dim3(64), 0, st, d_in, dch, container, flags,
                                    h->crc, d_out, d_outlen + c0, d_status + c0,
-                                   d_consumed ? d_consumed + c0 : nullptr, redo_only);
+                                   d_consumed ? d_consumed + c0 : nullptr, redo_only, (uint32_t*)h->dbg_par_handed.p);
         }
         HIP_OK(h, hipGetLastError());
         if (pin_io) {  // this sub-batch's output slots go home while the next sub-batch is decoded
@@ -3267,6 +3279,21 @@ int flate_hip_debug_workspace_bytes(flate_hip_handle h, uint64_t* bytes) {
                             &h->st_packoff, &h->st_slot, &h->chunks, &h->blk_chunk})
         batch += b->cap;
     *bytes = h->ws_bytes - batch;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_debug_inflate_paths(flate_hip_handle h, uint64_t counts[4]) {
+    if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    uint32_t handed = 0;
+    if (h->dbg_par_taken) {
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        HIP_OK(h, hipMemcpy(&handed, h->dbg_par_handed.p, sizeof handed, hipMemcpyDeviceToHost));
+    }
+    counts[0] = h->dbg_span_done;
+    counts[1] = h->dbg_span_taken - h->dbg_span_done;
+    counts[2] = h->dbg_par_taken - handed;
+    counts[3] = handed;
     return FLATE_HIP_OK;
 }
 

@@ -89,11 +89,12 @@ __device__ __host__ inline uint32_t fl_crc_mulmod(uint32_t a, uint32_t b) {
     }
     return p;
 }
-// x^(8*n) mod P using the table of x^(8*2^j)
+// x^(8*n) mod P using the table of x^(8*2^j), j < 32, for every 64-bit n: x has order 2^32 - 1 modulo P, so
+// x^(8 * 2^(j + 32)) = x^(8 * 2^j) and bit j + 32 of n takes entry j again
 __device__ __host__ inline uint32_t fl_crc_xpow8n(const uint32_t* xpow8, uint64_t n) {
     uint32_t p = 0x80000000u;
     for (int j = 0; n; j++, n >>= 1)
-        if (n & 1) p = fl_crc_mulmod(xpow8[j], p);
+        if (n & 1) p = fl_crc_mulmod(xpow8[j & 31], p);
     return p;
 }
 

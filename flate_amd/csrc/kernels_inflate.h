@@ -1111,7 +1111,8 @@ __global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1))
                                                 int container, int flags, fl_crc_consts cc,
                                                 uint8_t* __restrict__ out, uint64_t* __restrict__ out_len,
                                                 int32_t* __restrict__ status, uint64_t* __restrict__ consumed,
-                                                const int32_t* redo_only /* non-null: only streams marked -1 */) {
+                                                const int32_t* redo_only /* non-null: only streams marked -1 */,
+                                                uint32_t* handed_on /* with redo_only: counts the streams taken here */) {
     __shared__ fl_inflate_ws16 ws_mem;
     __shared__ alignas(8) uint8_t ring_mem[RING];
 #ifdef FL_INF_PAD  // tuning build: fewer streams per CU
@@ -1127,6 +1128,7 @@ __global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1))
     const uint32_t lane = threadIdx.x;
     if (ck.skip) return;
     if (redo_only && redo_only[c] != -1) return;  // k_inflate_par has decoded this stream
+    if (redo_only && lane == 0) atomicAdd(handed_on, 1u);  // (flate_hip_debug_inflate_paths)
     fl_bitr r;
     r.data = in + ck.in_off;
     r.nbytes = ck.in_len;

@@ -242,6 +242,13 @@ class Engine:
         self._check(self._L.flate_hip_debug_workspace_bytes(self._h, C.byref(v)), "flate_hip_debug_workspace_bytes")
         return int(v.value)
 
+    def inflate_paths(self):
+        """Which path finished the streams of the last decompress call: {"span_done", "span_handed_on", "par_done",
+        "par_handed_on"} (flate_hip_debug_inflate_paths); every stream in neither *_done was decoded by k_inflate."""
+        v = np.zeros(4, dtype=np.uint64)
+        self._check(self._L.flate_hip_debug_inflate_paths(self._h, v.ctypes.data), "flate_hip_debug_inflate_paths")
+        return dict(zip(("span_done", "span_handed_on", "par_done", "par_handed_on"), (int(x) for x in v)))
+
     def gather_streams_device(self, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr, dst_off_ptr):
         """Pack the produced streams back to back in device memory (dst_off gets n_chunks + 1 entries)."""
         rc = self._L.flate_hip_gather_streams(self._h, out_ptr, out_off_ptr, out_len_ptr, n_chunks, dst_ptr,

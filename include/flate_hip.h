@@ -325,6 +325,13 @@ int flate_hip_debug_device_bytes(flate_hip_handle h, uint64_t* bytes);
  * and statuses, and the batch's chunk and block tables -- and not the deflaters' (flate_hip_debug_device_bytes).  A
  * chunk-path batch on two compute streams keeps two slices of its largest pass, whatever the number of passes. */
 int flate_hip_debug_workspace_bytes(flate_hip_handle h, uint64_t* bytes);
+/* test seam: which path finished the streams of the handle's last flate_hip_decompress_batch call.  counts[0]: streams
+ * the span path decoded whole; counts[1]: streams it took (cut, decoded, summed) and then left to the kernels that
+ * follow -- a chain that did not close, a checksum or size that did not match the footer; counts[2]: streams the
+ * workgroup-per-stream kernel finished; counts[3]: streams it was launched for and handed on to the wave-per-stream
+ * kernel (too short by its rule, irregular, or a checksum that did not match).  Every stream not counted in [0] or
+ * [2] was decoded by the wave-per-stream kernel.  Waits for the handle's stream. */
+int flate_hip_debug_inflate_paths(flate_hip_handle h, uint64_t counts[4]);
 
 /* The containers' checksums on their own (container.zig:168-206: std.hash.Crc32 / Adler32 over the raw
  * input): container 1 = CRC-32, 2 = Adler-32 of a host buffer, computed by the checksum kernels; and the
