@@ -821,7 +821,7 @@ int enqueue_back_end(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32
         // (whole-stream passes: a block holds 32768 tokens and most slots are empty -- 256 streams of 1 MiB have 3072 blocks in 8448
         // slots: four waves a block are faster than one until the blocks are many)
         if (mode >= 4 && nb >= (prm.stream ? FL_ENC_WAVE_MIN_SLOTS_STREAM : 8192u))
-            hipLaunchKernelGGL(k_encode_wave<true>, dim3((nb + FL_ENC_WAVES - 1) / FL_ENC_WAVES), dim3(64 * FL_ENC_WAVES), 0, st,
+            hipLaunchKernelGGL(k_encode_wave, dim3((nb + FL_ENC_WAVES - 1) / FL_ENC_WAVES), dim3(64 * FL_ENC_WAVES), 0, st,
                                d_in, dch, dbc, (const fl_block_plan*)dpl, (const uint32_t*)h->tokens.p, (uint32_t*)d_out, nb,
                                (prm.stream || (nb & 1u)) ? 0u : 1u);
         else if (mode >= 4)
@@ -2513,7 +2513,8 @@ int flate_hip_debug_write_block(flate_hip_handle h, const uint32_t* tokens, uint
     if (in_len) HIP_OK(h, hipMemcpyAsync(h->st_in.p, input, in_len, hipMemcpyHostToDevice, st));
     HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, cap4 + 16, st));
     HIP_OK(h, hipStreamSynchronize(st));  // the host structs must outlive the async copies
-    hipLaunchKernelGGL(k_dbg_token_hist, dim3(1), dim3(256), 0, st, (const uint32_t*)h->tokens.p, n_tokens,
+    hipLaunchKernelGGL(k_dbg_token_hist, dim3(1), dim3(256), 0, st, (const uint32_t*)h->tokens.p,
+                       (const fl_chunk*)h->chunks.p, (const uint32_t*)h->blk_chunk.p, (const fl_block_plan*)h->plans.p,
                        (uint32_t*)h->hist.p);
     hipLaunchKernelGGL(k_plan, dim3(1), dim3(64 * FL_PLAN_WAVES), 0, st, (const fl_chunk*)h->chunks.p,
                        (const uint32_t*)h->blk_chunk.p, (const fl_sblock*)nullptr, prm, (const uint32_t*)h->hist.p,
@@ -2531,6 +2532,98 @@ int flate_hip_debug_write_block(flate_hip_handle h, const uint32_t* tokens, uint
     HIP_OK(h, hipStreamSynchronize(st));
     if (status != 0) return FLATE_HIP_E_INVALID_ARG;  // out_cap too small
     if (*out_len) HIP_OK(h, hipMemcpy(out, h->st_out.p, *out_len, hipMemcpyDeviceToHost));
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_debug_write_blocks(flate_hip_handle h, uint32_t n, const uint32_t* tokens, const uint64_t* tok_off,
+                                 const uint8_t* input, const uint64_t* in_off, const uint8_t* has_input,
+                                 const uint8_t* eof, int dynamic_only, int encoder, int paired, uint8_t* out,
+                                 uint64_t out_cap, const uint64_t* slot_off, const uint64_t* slot_cap,
+                                 uint64_t* out_len) {
+    if (!h || !n || n > 65536u || !tok_off || !in_off || !has_input || !eof || !out || !slot_off || !slot_cap || !out_len)
+        return FLATE_HIP_E_INVALID_ARG;
+    if ((encoder != 0 && encoder != 1) || (out_cap & 3) || ((uintptr_t)out & 3)) return FLATE_HIP_E_INVALID_ARG;
+    if ((tok_off[n] && !tokens) || (in_off[n] && !input)) return FLATE_HIP_E_INVALID_ARG;
+    for (uint32_t i = 0; i < n; i++) {
+        if (tok_off[i + 1] < tok_off[i] || tok_off[i + 1] - tok_off[i] > FL_MAX_TOKENS) return FLATE_HIP_E_INVALID_ARG;
+        if (in_off[i + 1] < in_off[i] || in_off[i + 1] - in_off[i] > 0xfffffff0u) return FLATE_HIP_E_INVALID_ARG;
+        if (slot_cap[i] > out_cap || slot_off[i] > out_cap - slot_cap[i]) return FLATE_HIP_E_INVALID_ARG;
+    }
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    int rc;
+    const uint32_t per = paired ? 2u : 1u, nb = n * per;
+    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n))) return rc;
+    if ((rc = ensure(h, h->blk_chunk, sizeof(uint32_t) * nb))) return rc;
+    if ((rc = ensure(h, h->plans, sizeof(fl_block_plan) * nb))) return rc;
+    if ((rc = ensure(h, h->hist, sizeof(uint32_t) * 320 * nb))) return rc;
+    if ((rc = ensure(h, h->cks, sizeof(uint32_t) * 2 * nb))) return rc;
+    if ((rc = ensure(h, h->tokens, sizeof(uint32_t) * ((size_t)tok_off[n] + 1)))) return rc;
+    if ((rc = ensure(h, h->st_in, (size_t)in_off[n] + 16))) return rc;
+    if ((rc = ensure(h, h->st_out, out_cap + 16))) return rc;
+    if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n))) return rc;
+    if ((rc = ensure(h, h->st_status, sizeof(int32_t) * n))) return rc;
+    std::vector<fl_chunk> cks(n);
+    std::vector<uint32_t> bc(nb);
+    std::vector<fl_block_plan> plans(nb);  // (value-initialised: valid = 0 in every second slot of the paired layout)
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t in_len = (uint32_t)(in_off[i + 1] - in_off[i]);
+        fl_chunk& ck = cks[i];
+        ck = fl_chunk{};
+        ck.in_off = in_off[i];
+        ck.out_off = slot_off[i];
+        ck.out_cap = slot_cap[i];
+        ck.pos_off = tok_off[i];
+        ck.in_len = in_len;
+        ck.first_block = i * per;
+        ck.n_blocks = per;
+        for (uint32_t k = 0; k < per; k++) bc[i * per + k] = i;
+        fl_block_plan& plan = plans[i * per];
+        plan.valid = 1;
+        plan.tok_count = (uint32_t)(tok_off[i + 1] - tok_off[i]);
+        plan.in_len = has_input[i] ? in_len : FL_NO_INPUT;  // Zig null: the block cannot be stored
+        plan.final_block = eof[i] ? 1u : 0u;
+    }
+    fl_params prm{};
+    level_args(6, prm);
+    prm.n_chunks = n;
+    prm.n_blocks = nb;
+    prm.container = 0;
+    prm.mode = 6;
+    prm.stream = paired ? 0u : 1u;  // paired: k_plan visits the slots in the chunk path's order; else plain numbering
+    prm.plan_dynamic_only = dynamic_only ? 1u : 0u;
+    HIP_OK(h, hipMemcpyAsync(h->chunks.p, cks.data(), sizeof(fl_chunk) * n, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->blk_chunk.p, bc.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->plans.p, plans.data(), sizeof(fl_block_plan) * nb, hipMemcpyHostToDevice, st));
+    if (tok_off[n])
+        HIP_OK(h, hipMemcpyAsync(h->tokens.p, tokens, sizeof(uint32_t) * tok_off[n], hipMemcpyHostToDevice, st));
+    if (in_off[n]) HIP_OK(h, hipMemcpyAsync(h->st_in.p, input, in_off[n], hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, out_cap + 16, st));
+    HIP_OK(h, hipStreamSynchronize(st));  // the host tables must outlive the async copies
+    const fl_chunk* dch = (const fl_chunk*)h->chunks.p;
+    const uint32_t* dbc = (const uint32_t*)h->blk_chunk.p;
+    fl_block_plan* dpl = (fl_block_plan*)h->plans.p;
+    hipLaunchKernelGGL(k_dbg_token_hist, dim3(nb), dim3(256), 0, st, (const uint32_t*)h->tokens.p, dch, dbc,
+                       (const fl_block_plan*)dpl, (uint32_t*)h->hist.p);
+    hipLaunchKernelGGL(k_plan, dim3((nb + FL_PLAN_WAVES - 1) / FL_PLAN_WAVES), dim3(64 * FL_PLAN_WAVES), 0, st, dch, dbc,
+                       (const fl_sblock*)nullptr, prm, (const uint32_t*)h->hist.p, dpl);
+    hipLaunchKernelGGL(k_offsets, dim3(n), dim3(64), 0, st, dch, prm, h->crc, dpl, (const uint32_t*)h->cks.p,
+                       (uint8_t*)h->st_out.p, (uint64_t*)h->st_outlen.p, (int32_t*)h->st_status.p);
+    if (encoder == 1)
+        hipLaunchKernelGGL(k_encode_wave, dim3((nb + FL_ENC_WAVES - 1) / FL_ENC_WAVES), dim3(64 * FL_ENC_WAVES), 0, st,
+                           (const uint8_t*)h->st_in.p, dch, dbc, (const fl_block_plan*)dpl, (const uint32_t*)h->tokens.p,
+                           (uint32_t*)h->st_out.p, nb, paired ? 1u : 0u);
+    else
+        hipLaunchKernelGGL(k_encode<true>, dim3(nb), dim3(64 * FL_ENC_WAVES), 0, st, (const uint8_t*)h->st_in.p, dch, dbc,
+                           (const fl_block_plan*)dpl, (const uint32_t*)h->tokens.p, (uint32_t*)h->st_out.p);
+    HIP_OK(h, hipGetLastError());
+    std::vector<int32_t> status(n);
+    HIP_OK(h, hipMemcpyAsync(out_len, h->st_outlen.p, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(status.data(), h->st_status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(out, h->st_out.p, out_cap, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n; i++)
+        if (status[i] != 0) return FLATE_HIP_E_INVALID_ARG;  // a slot too small
     return FLATE_HIP_OK;
 }
 

@@ -117,15 +117,22 @@ __global__ __launch_bounds__(256) void k_byte_hist(const uint8_t* __restrict__ i
     hist[(uint64_t)b * 320 + tid] = v;
 }
 
-// debug seam (flate_hip_debug_write_block): histogram of a caller-supplied token list, as the
-// tokenizer's emit kernels build it (block_writer.zig:444-462)
-__global__ __launch_bounds__(256) void k_dbg_token_hist(const uint32_t* __restrict__ tokens, uint32_t n,
-                                                        uint32_t* __restrict__ hist /* [320] */) {
+// debug seams (flate_hip_debug_write_block / _write_blocks): histogram of every valid plan slot's caller-supplied
+// token list, as the tokenizer's emit kernels build it (block_writer.zig:444-462).  One workgroup per plan slot.
+__global__ __launch_bounds__(256) void k_dbg_token_hist(const uint32_t* __restrict__ tokens,
+                                                        const fl_chunk* __restrict__ chunks,
+                                                        const uint32_t* __restrict__ blk_chunk,
+                                                        const fl_block_plan* __restrict__ plans,
+                                                        uint32_t* __restrict__ hist /* [n_blocks][320] */) {
     __shared__ uint32_t sh[320];
+    const uint32_t b = blockIdx.x;
+    if (plans[b].valid != 1) return;  // (the same verdict in every thread)
+    const uint32_t* toks = tokens + chunks[blk_chunk[b]].pos_off + plans[b].tok_start;
+    const uint32_t n = plans[b].tok_count;
     for (uint32_t i = threadIdx.x; i < 320; i += 256) sh[i] = 0;
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n; i += 256) {
-        const uint32_t t = tokens[i];
+        const uint32_t t = toks[i];
         if (FL_TOK_IS_MATCH(t)) {
             atomicAdd(&sh[257 + fl_len_index(FL_TOK_LENLIT(t))], 1u);
             atomicAdd(&sh[286 + fl_dist_code(FL_TOK_DIST0(t))], 1u);
@@ -134,7 +141,7 @@ __global__ __launch_bounds__(256) void k_dbg_token_hist(const uint32_t* __restri
         }
     }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < 320; i += 256) hist[i] = sh[i];
+    for (uint32_t i = threadIdx.x; i < 320; i += 256) hist[(uint64_t)b * 320 + i] = sh[i];
 }
 
 // ------------------------------------------------------------------ checksums
@@ -806,8 +813,8 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode(const uint8_t* __r
 
 // The same, one WAVE per block (batches of many blocks: the chunk path): no split of a block among waves, so no
 // first pass over the tokens to find out where each wave's bits start -- half the instructions.  A wave's chain is
-// four times as long, four times as many blocks are in flight.
-template <bool TOKENS>
+// four times as long, four times as many blocks are in flight.  Token blocks only: huffman-only batches never had
+// a launch site for it (enqueue_back_end, the deflater's feed), so the kernel holds no byte-item path.
 __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t* __restrict__ in,
                                                               const fl_chunk* __restrict__ chunks,
                                                               const uint32_t* __restrict__ blk_chunk,
@@ -859,12 +866,9 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t
     const uint32_t hdr_nbits = plan->hdr_nbits;
     const uint32_t n_hdr = (hdr_nbits + 7) >> 3;
     const uint32_t n_sym = plan->tok_count;
-    const uint32_t n_items = n_hdr + FL_ENC_UNITS(TOKENS, n_sym) + 1;
-    const uint8_t* bytes = src + plan->tok_start;
-    const uint32_t* toks = TOKENS ? tokens + ck.pos_off + plan->tok_start : nullptr;
+    const uint32_t* toks = tokens + ck.pos_off + plan->tok_start;
     const uint8_t* hdr = plan->hdr;
 
-    (void)n_items;
     uint64_t cur = bit_off;
 
     // pack 64 items (one a lane, it.n = 0: none) behind `cur`: prefix sum of the lengths, ds_or into the staging window, whole
@@ -906,75 +910,64 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t
         fl_lds_order();
         cur = end;
     };
-    if (!TOKENS) {
-        // (huffman-only blocks of a batch this large: the generic items, 64 at a time)
-        for (uint32_t ib = 0; ib < n_items; ib += 64) {
-            fl_item it;
-            it.v = 0;
-            it.n = 0;
-            if (ib + lane < n_items) it = fl_block_item<TOKENS>(ib + lane, n_hdr, hdr_nbits, n_sym, hdr, bytes, toks, lit_lds, dist_lds);
-            pack(it);
+    // Round 6: three loops instead of one over "items" -- the header's bytes, the tokens, the end-of-block code -- so that the
+    // tokens' loop carries no branch for the other two, and a group's tokens are requested while the group before is packed
+    // (the load sat in the loop with its own wait: 1.08 -> see profiles/r06_config2_kernel_stats.csv).
+    for (uint32_t ib = 0; ib < n_hdr; ib += 64) {
+        fl_item it;
+        it.v = 0;
+        it.n = 0;
+        const uint32_t i = ib + lane;
+        if (i < n_hdr) {
+            const uint32_t rem = hdr_nbits - 8 * i;
+            it.n = rem < 8 ? rem : 8;
+            it.v = hdr[i] & ((1u << it.n) - 1);
         }
-    } else {
-        // Round 6: three loops instead of one over "items" -- the header's bytes, the tokens, the end-of-block code -- so that the
-        // tokens' loop carries no branch for the other two, and a group's tokens are requested while the group before is packed
-        // (the load sat in the loop with its own wait: 1.08 -> see profiles/r06_config2_kernel_stats.csv).
-        for (uint32_t ib = 0; ib < n_hdr; ib += 64) {
-            fl_item it;
-            it.v = 0;
-            it.n = 0;
-            const uint32_t i = ib + lane;
-            if (i < n_hdr) {
-                const uint32_t rem = hdr_nbits - 8 * i;
-                it.n = rem < 8 ? rem : 8;
-                it.v = hdr[i] & ((1u << it.n) - 1);
+        pack(it);
+    }
+    const uint32_t eob = lit_lds[FL_EOB];
+    uint32_t t_next = lane < n_sym ? toks[lane] : 0u;
+    for (uint32_t k0 = 0; k0 < n_sym; k0 += 64) {
+        const uint32_t t = t_next;
+        t_next = k0 + 64 + lane < n_sym ? toks[k0 + 64 + lane] : 0u;
+        fl_item it;
+        it.v = 0;
+        it.n = 0;
+        const uint32_t k = k0 + lane;
+        if (k < n_sym) {
+            if (!FL_TOK_IS_MATCH(t)) {
+                const uint32_t e = lit_lds[FL_TOK_LENLIT(t)];
+                it.v = e & 0xffff;
+                it.n = e >> 16;
+            } else {
+                const uint32_t ll = FL_TOK_LENLIT(t);
+                const uint32_t li = fl_len_index(ll);
+                const uint32_t le = lit_lds[257 + li];
+                uint64_t v = le & 0xffff;
+                uint32_t n = le >> 16;
+                v |= (uint64_t)(ll - fl_len_base_scaled(li)) << n;
+                n += fl_len_extra_bits(li);
+                const uint32_t d = FL_TOK_DIST0(t);
+                const uint32_t dc = fl_dist_code(d);
+                const uint32_t de = dist_lds[dc];
+                v |= (uint64_t)(de & 0xffff) << n;
+                n += de >> 16;
+                v |= (uint64_t)(d - fl_dist_base_scaled(dc)) << n;
+                n += fl_dist_extra_bits(dc);
+                it.v = v;
+                it.n = n;
             }
-            pack(it);
+        } else if (k == n_sym) {  // the end-of-block code rides in the last group when a lane is free
+            it.v = eob & 0xffff;
+            it.n = eob >> 16;
         }
-        const uint32_t eob = lit_lds[FL_EOB];
-        uint32_t t_next = lane < n_sym ? toks[lane] : 0u;
-        for (uint32_t k0 = 0; k0 < n_sym; k0 += 64) {
-            const uint32_t t = t_next;
-            t_next = k0 + 64 + lane < n_sym ? toks[k0 + 64 + lane] : 0u;
-            fl_item it;
-            it.v = 0;
-            it.n = 0;
-            const uint32_t k = k0 + lane;
-            if (k < n_sym) {
-                if (!FL_TOK_IS_MATCH(t)) {
-                    const uint32_t e = lit_lds[FL_TOK_LENLIT(t)];
-                    it.v = e & 0xffff;
-                    it.n = e >> 16;
-                } else {
-                    const uint32_t ll = FL_TOK_LENLIT(t);
-                    const uint32_t li = fl_len_index(ll);
-                    const uint32_t le = lit_lds[257 + li];
-                    uint64_t v = le & 0xffff;
-                    uint32_t n = le >> 16;
-                    v |= (uint64_t)(ll - fl_len_base_scaled(li)) << n;
-                    n += fl_len_extra_bits(li);
-                    const uint32_t d = FL_TOK_DIST0(t);
-                    const uint32_t dc = fl_dist_code(d);
-                    const uint32_t de = dist_lds[dc];
-                    v |= (uint64_t)(de & 0xffff) << n;
-                    n += de >> 16;
-                    v |= (uint64_t)(d - fl_dist_base_scaled(dc)) << n;
-                    n += fl_dist_extra_bits(dc);
-                    it.v = v;
-                    it.n = n;
-                }
-            } else if (k == n_sym) {  // the end-of-block code rides in the last group when a lane is free
-                it.v = eob & 0xffff;
-                it.n = eob >> 16;
-            }
-            pack(it);
-        }
-        if ((n_sym & 63u) == 0) {  // every lane of the last group held a token (or there was none): a group of its own
-            fl_item it;
-            it.v = lane == 0 ? (eob & 0xffff) : 0u;
-            it.n = lane == 0 ? (eob >> 16) : 0u;
-            pack(it);
-        }
+        pack(it);
+    }
+    if ((n_sym & 63u) == 0) {  // every lane of the last group held a token (or there was none): a group of its own
+        fl_item it;
+        it.v = lane == 0 ? (eob & 0xffff) : 0u;
+        it.n = lane == 0 ? (eob >> 16) : 0u;
+        pack(it);
     }
     if ((cur & 31) && lane == 0) {
         const uint32_t v = sw[0];

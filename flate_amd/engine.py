@@ -294,6 +294,49 @@ class Engine:
         self._check(rc, "flate_hip_debug_write_block")
         return out[: int(out_len[0])].tobytes()
 
+    @staticmethod
+    def debug_block_bound(n_tokens, input_len):
+        """Bytes that hold any block of n_tokens tokens (48 bits each at most) or its stored form, and the 8 spare
+        bytes debug_write_blocks asks for behind it."""
+        return 6 * int(n_tokens) + int(input_len) + 700
+
+    def debug_write_blocks(self, blocks, encoder=0, paired=False, dynamic_only=False, slot_starts=None):
+        """n blocks, each (tokens, input_bytes or None, eof), in ONE launch of the device planner / offset scan and
+        the bit packer `encoder` names (0: k_encode<true>, 1: k_encode_wave); paired: the chunk path's layout of two plan
+        slots a chunk (include/flate_hip.h).  slot_starts: byte offset of every block's output slot (ascending, any
+        residue mod 4, debug_block_bound apart at least); default: slot i at residue i mod 4.  Returns the blocks' bytes."""
+        n = len(blocks)
+        toks = [np.ascontiguousarray(b[0], dtype=np.uint32) for b in blocks]
+        inps = [np.zeros(0, np.uint8) if b[1] is None else np.frombuffer(bytes(b[1]), dtype=np.uint8) for b in blocks]
+        has = np.array([b[1] is not None for b in blocks], dtype=np.uint8)
+        eof = np.array([bool(b[2]) for b in blocks], dtype=np.uint8)
+        tok_off = np.zeros(n + 1, dtype=np.uint64)
+        tok_off[1:] = np.cumsum([t.size for t in toks])
+        in_off = np.zeros(n + 1, dtype=np.uint64)
+        in_off[1:] = np.cumsum([a.size for a in inps])
+        tok_all = np.concatenate(toks + [np.zeros(1, np.uint32)])
+        in_all = np.concatenate(inps + [np.zeros(1, np.uint8)])
+        caps = np.array([self.debug_block_bound(t.size, a.size) for t, a in zip(toks, inps)], dtype=np.uint64)
+        if slot_starts is None:
+            slot_starts, at = [], 0
+            for i in range(n):
+                at = (at + 3) // 4 * 4 + i % 4
+                slot_starts.append(at)
+                at += int(caps[i])
+        starts = np.array(slot_starts, dtype=np.uint64)
+        ends = starts + caps
+        if n > 1 and (starts[1:] < ends[:-1]).any():
+            raise ValueError("debug_write_blocks: output slots overlap")
+        out_cap = (int(ends.max()) + 3) // 4 * 4
+        out = np.zeros(out_cap, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint64)
+        rc = self._L.flate_hip_debug_write_blocks(
+            self._h, n, tok_all.ctypes.data, tok_off.ctypes.data, in_all.ctypes.data, in_off.ctypes.data,
+            has.ctypes.data, eof.ctypes.data, int(bool(dynamic_only)), int(encoder), int(bool(paired)),
+            out.ctypes.data, out_cap, starts.ctypes.data, caps.ctypes.data, out_len.ctypes.data)
+        self._check(rc, "flate_hip_debug_write_blocks")
+        return [out[int(s): int(s) + int(m)].tobytes() for s, m in zip(starts, out_len)]
+
     def debug_tokens(self, chunk):
         """Token list the tokenizer kernels produced for `chunk` of the last level 4..9 call."""
         buf = np.zeros(65536, dtype=np.uint32)

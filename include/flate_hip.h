@@ -373,6 +373,22 @@ int flate_hip_debug_write_block(flate_hip_handle h, const uint32_t* tokens, uint
                                 const uint8_t* input, uint32_t input_len, int eof, int dynamic_only,
                                 uint8_t* out, uint64_t out_cap, uint64_t* out_len);
 
+/* The same seam for n blocks in one call, each a chunk of its own, and with a choice of the bit packer: block i has
+ * tokens[tok_off[i] .. tok_off[i + 1]), the raw input input[in_off[i] .. in_off[i + 1]) when has_input[i] (else the
+ * Zig `null`), the final-block bit eof[i], and is written to out[slot_off[i] .. + slot_cap[i]); out_len[i] is its
+ * byte count.  tok_off and in_off have n + 1 entries.  `out` and out_cap are multiples of 4; slot starts may have
+ * any residue mod 4, slots must not overlap and are expected to leave 8 spare bytes behind a block (neighbours then
+ * share no dword).  Bytes of a slot behind out_len[i] are unspecified.
+ * encoder 0: k_encode<true>, a workgroup per block (few blocks, long streams); encoder 1: k_encode_wave, a wave per
+ * block (what a batch of 8192 or more plan slots runs).  paired = 1 lays the plan slots out as the chunk path does:
+ * two a chunk, the second one unused, visited by k_plan and k_encode_wave in their first-slots-first order; paired = 0:
+ * one slot a chunk, plain order.  Fails with FLATE_HIP_E_INVALID_ARG when a block does not fit its slot. */
+int flate_hip_debug_write_blocks(flate_hip_handle h, uint32_t n, const uint32_t* tokens, const uint64_t* tok_off,
+                                 const uint8_t* input, const uint64_t* in_off, const uint8_t* has_input,
+                                 const uint8_t* eof, int dynamic_only, int encoder, int paired, uint8_t* out,
+                                 uint64_t out_cap, const uint64_t* slot_off, const uint64_t* slot_cap,
+                                 uint64_t* out_len);
+
 /* Tuning aid: shader-clock timestamps that workgroup 0 of the tokenizer kernels took at its
  * phase boundaries during the last call (slots: sort 0-7, match 8-10, parse 16-23). */
 int flate_hip_debug_phase_cycles(flate_hip_handle h, uint64_t* out, int n);

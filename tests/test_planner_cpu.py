@@ -1,130 +1,20 @@
 """CPU check of the serial block planner (flate_amd/csrc/flate_common.h) -- the exact
 source that one GPU lane per block executes -- against the oracle and the reference's
 golden block vectors (block_writer.zig:599-706).  No GPU."""
-import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import _oracle as O
-from conftest import GOLDEN, ROOT, golden
-
-SHIM_DIR = os.path.join(ROOT, "tests", "cpu_shim")
-SHIM_SO = os.path.join(SHIM_DIR, "libplanner_shim.so")
-NO_INPUT = 0xFFFFFFFF
-
-
-class Plan(C.Structure):
-    _fields_ = [("type", C.c_uint32), ("size_bits", C.c_uint32), ("hdr_nbits", C.c_uint32),
-                ("final_block", C.c_uint32), ("in_start", C.c_uint32), ("in_len", C.c_uint32),
-                ("tok_start", C.c_uint32), ("tok_count", C.c_uint32), ("valid", C.c_uint32),
-                ("no_input", C.c_uint32), ("q1_gap", C.c_uint32), ("pad_", C.c_uint32), ("bit_off", C.c_uint64), ("hdr", C.c_uint8 * 640),
-                ("lit", C.c_uint16 * (2 * 286)), ("dist", C.c_uint16 * (2 * 30))]
+from _planner_shim import encode_block, load_shim, tables
+from conftest import GOLDEN, golden
 
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(SHIM_DIR, "planner_shim.cpp")
-    deps = [src] + [os.path.join(ROOT, "flate_amd", "csrc", h) for h in ("flate_common.h", "flate_layout.h", "stream_tables.h")]
-    if not os.path.exists(SHIM_SO) or os.path.getmtime(SHIM_SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-fsanitize=undefined", "-fno-sanitize-recover",
-                        "-fPIC", "-shared", "-o", SHIM_SO, src], check=True)
-    lib = C.CDLL(SHIM_SO)
-    lib.shim_plan_block.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-    lib.shim_huff_generate.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.shim_tables.argtypes = [C.c_void_p] * 6
-    lib.shim_set_pm.argtypes = [C.c_int]
-    assert lib.shim_plan_sizeof() == C.sizeof(Plan)
-    return lib
-
-
-class BitSink:
-    def __init__(self):
-        self.acc, self.n, self.out = 0, 0, bytearray()
-
-    def put(self, v, nb):
-        self.acc |= int(v) << self.n
-        self.n += int(nb)
-        while self.n >= 8:
-            self.out.append(self.acc & 0xFF)
-            self.acc >>= 8
-            self.n -= 8
-
-    def align(self):
-        if self.n:
-            self.out.append(self.acc & 0xFF)
-        self.acc, self.n = 0, 0
-
-
-def tables(lib):
-    li = np.zeros(256, np.uint8); le = np.zeros(29, np.uint8); lb = np.zeros(29, np.uint8)
-    dc = np.zeros(32768, np.uint8); de = np.zeros(30, np.uint8); db = np.zeros(30, np.uint16)
-    lib.shim_tables(li.ctypes.data, le.ctypes.data, lb.ctypes.data, dc.ctypes.data, de.ctypes.data, db.ctypes.data)
-    return li, le, lb, dc, de, db
-
-
-def encode_block(lib, mode, tokens, input_bytes, eof, dyn=False):
-    """Assemble the block bytes the way the encode kernel does: planner output + codes."""
-    li, le, lb, dc, de, db = tables(lib)
-    lit = np.zeros(286, np.uint16)
-    dist = np.zeros(30, np.uint16)
-    if mode == 0:
-        for t in tokens:
-            t = int(t)
-            if (t >> 23) & 1:
-                lit[257 + int(li[(t >> 15) & 0xFF])] += 1
-                dist[dc[t & 0x7FFF]] += 1
-            else:
-                lit[(t >> 15) & 0xFF] += 1
-    else:
-        h = np.bincount(np.frombuffer(input_bytes, np.uint8), minlength=256)
-        lit[:256] = h
-    in_len = NO_INPUT if input_bytes is None else len(input_bytes)
-    plan = Plan()
-    lib.shim_plan_block(2 if dyn else mode, lit.ctypes.data, dist.ctypes.data, in_len, int(eof), C.addressof(plan))
-    s = BitSink()
-    if plan.type == 0:  # stored
-        s.put(1 if eof else 0, 3)
-        s.align()
-        s.put(len(input_bytes), 16)
-        s.put((~len(input_bytes)) & 0xFFFF, 16)
-        s.out += input_bytes
-        return bytes(s.out), plan
-    hdr = bytes(plan.hdr)
-    for i in range(plan.hdr_nbits // 8):
-        s.put(hdr[i], 8)
-    if plan.hdr_nbits % 8:
-        s.put(hdr[plan.hdr_nbits // 8] & ((1 << (plan.hdr_nbits % 8)) - 1), plan.hdr_nbits % 8)
-    lc = np.array(plan.lit, np.uint16).reshape(286, 2)
-    dcodes = np.array(plan.dist, np.uint16).reshape(30, 2)
-    if mode == 0:
-        for t in tokens:
-            t = int(t)
-            if (t >> 23) & 1:
-                ll = (t >> 15) & 0xFF
-                idx = int(li[ll])
-                s.put(lc[257 + idx][0], lc[257 + idx][1])
-                if le[idx]:
-                    s.put(ll - lb[idx], le[idx])
-                d = t & 0x7FFF
-                c = int(dc[d])
-                s.put(dcodes[c][0], dcodes[c][1])
-                if de[c]:
-                    s.put(d - db[c], de[c])
-            else:
-                b = (t >> 15) & 0xFF
-                s.put(lc[b][0], lc[b][1])
-    else:
-        for b in input_bytes:
-            s.put(lc[b][0], lc[b][1])
-    s.put(lc[256][0], lc[256][1])
-    nbits = len(s.out) * 8 + s.n
-    assert nbits == plan.size_bits, (nbits, plan.size_bits)
-    s.align()
-    return bytes(s.out), plan
+    return load_shim()
 
 
 def test_tables_match_oracle(shim):
