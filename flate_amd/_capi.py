@@ -36,6 +36,7 @@ SYMBOLS = [
     "flate_hip_deflater_create", "flate_hip_deflater_destroy", "flate_hip_deflater_reset", "flate_hip_deflater_feed",
     "flate_hip_debug_device_bytes", "flate_hip_debug_workspace_bytes",
     "flate_hip_debug_inflate_paths",
+    "flate_hip_decompressed_sizes", "flate_hip_debug_size_paths",
 ]
 
 
@@ -153,6 +154,10 @@ def lib():
     L.flate_hip_debug_workspace_bytes.restype = C.c_int
     L.flate_hip_debug_inflate_paths.argtypes = [vp, u64p]
     L.flate_hip_debug_inflate_paths.restype = C.c_int
+    L.flate_hip_decompressed_sizes.argtypes = [vp, vp, u64p, C.c_uint32, C.c_int, C.c_int, u64p, i32p, u64p, C.c_int]
+    L.flate_hip_decompressed_sizes.restype = C.c_int
+    L.flate_hip_debug_size_paths.argtypes = [vp, u64p]
+    L.flate_hip_debug_size_paths.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.flate_hip_debug_tokens.restype = C.c_int64
     _lib = L

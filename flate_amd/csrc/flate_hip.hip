@@ -23,11 +23,13 @@
 #include "kernels_deflater.h"
 #include "kernels_inflate.h"
 #include "kernels_inflate_par.h"
+#include "kernels_inflate_size.h"
 #include "kernels_lz.h"
 #include "kernels_parse.h"
 #include "kernels_walk.h"
 #include "kernels_stream.h"
 #include "pass_plan.h"
+#include "size_plan.h"
 #include "stream_tables.h"
 
 namespace {
@@ -52,6 +54,8 @@ enum KernelId {
     K_INFLATE_PAR,
     K_SPAN_SCAN,
     K_INFLATE_SPAN,
+    K_INFLATE_SIZE,
+    K_INFLATE_SIZE_SPAN,
     K_GATHER,
     K_INFLATER,
     K_DEFLATER,
@@ -61,6 +65,7 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_lz_chain", "k_lz_parse", "k_lz_links", "k_lz_walk", "k_lz_emit",
                                            "k_st_parse", "k_st_emit", "k_plan",
                                            "k_offsets",  "k_encode",    "k_inflate",  "k_inflate_par", "k_span_scan", "k_inflate_span",
+                                           "k_inflate_size", "k_inflate_size_span",
                                            "k_gather", "k_inflater", "k_deflater"};
 
 struct DevBuf {
@@ -155,6 +160,10 @@ struct flate_hip_ctx {
     // streams k_inflate_par was launched for, and (counted on the device by k_inflate) those it handed on
     uint64_t dbg_span_taken = 0, dbg_span_done = 0, dbg_par_taken = 0;
     DevBuf dbg_par_handed;
+    // flate_hip_decompressed_sizes: the span table and the span records of its long streams, and for
+    // flate_hip_debug_size_paths the streams of the last call whose size came from a closed chain / from one wave
+    DevBuf sz_spans, sz_recs;
+    uint64_t dbg_size_chain = 0, dbg_size_whole = 0;
     bool ws_fixed = false;   // the two-stream passes are being enqueued: ensure() may not grow a buffer (compress_impl)
     // last level 4..9 call, for the debug seam
     uint32_t dbg_pass_chunks = 0;
@@ -1328,6 +1337,127 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     return done;
 }
 
+// flate_hip_decompressed_sizes, long streams: cut each at block starts (k_span_scan, as try_span_inflate aims it but spaced
+// by size_plan.h), count every span with a wave of its own and follow each stream's chain of span records on the host.
+// A stream whose chain closes gets its size / status / consumed here and chunks[i].skip = 1; every other stream stays for
+// the wave-per-stream launch.  Two host waits.  Returns the number of streams finished, or -1 (a HIP call failed).
+int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::vector<fl_chunk>& chunks, int container, int flags,
+                  uint64_t* d_sizes, int32_t* d_status, uint64_t* d_consumed) {
+    const uint32_t n_chunks = (uint32_t)chunks.size();
+    if (flags & 1) return 0;  // (as decompress: the scan's first two steps know the lenient header only)
+    if (h->n_cu == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || v <= 0) v = 256;
+        h->n_cu = (uint32_t)v;
+    }
+    std::vector<uint64_t> lens(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; i++) lens[i] = chunks[i].in_len;
+    std::vector<uint32_t> elig, pieces;
+    fl_size_eligible(lens.data(), n_chunks, h->knobs.span_min_bytes, h->n_cu, elig);
+    if (elig.empty()) return 0;
+    std::vector<uint64_t> elens(elig.size());
+    for (size_t k = 0; k < elig.size(); k++) elens[k] = lens[elig[k]];
+    fl_size_spacing(elens.data(), (uint32_t)elig.size(), h->n_cu, pieces);
+    // ---- where spans may start
+    std::vector<fl_scan_point> points;
+    std::vector<uint32_t> pt_first(elig.size() + 1, 0);
+    std::vector<uint64_t> fl;
+    for (size_t k = 0; k < elig.size(); k++) {
+        fl.clear();
+        fl_size_targets(elens[k], pieces[k], fl);
+        for (size_t j = 0; j + 1 < fl.size(); j += 2) {
+            fl_scan_point pt;
+            pt.from_bit = fl[j];
+            pt.limit_bit = fl[j + 1];
+            pt.stream = elig[k];
+            pt.pad = 0;
+            points.push_back(pt);
+        }
+        pt_first[k + 1] = (uint32_t)points.size();
+    }
+    const uint32_t npts = (uint32_t)points.size();
+    if (!npts) return 0;
+    if (ensure(h, h->sp_points, sizeof(fl_scan_point) * npts) || ensure(h, h->sp_found, sizeof(uint64_t) * npts)) {
+        (void)hipGetLastError();  // (no room: every stream whole)
+        return 0;
+    }
+    if (hipMemcpyAsync(h->sp_points.p, points.data(), sizeof(fl_scan_point) * npts, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    const fl_chunk* dch = (const fl_chunk*)h->chunks.p;
+    {
+        ProfScope ps(h, K_SPAN_SCAN);
+        hipLaunchKernelGGL(k_span_scan, dim3(npts), dim3(FP_THREADS), 0, st, d_in, dch, flags,
+                           (const fl_scan_point*)h->sp_points.p, (uint64_t*)h->sp_found.p);
+    }
+    std::vector<uint64_t> found(npts);
+    if (hipMemcpyAsync(found.data(), h->sp_found.p, sizeof(uint64_t) * npts, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+    if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    // ---- the spans: the stream start, then every distinct position found; a span ends where the next one starts
+    std::vector<fl_size_span> spans;
+    std::vector<uint32_t> sp_first(elig.size() + 1, 0);
+    for (size_t k = 0; k < elig.size(); k++) {
+        fl_size_span s0;
+        s0.start_bit = 0;
+        s0.stop_bit = ~0ull;
+        s0.stream = elig[k];
+        s0.first = 1;
+        spans.push_back(s0);
+        uint64_t last = 0;
+        for (uint32_t j = pt_first[k]; j < pt_first[k + 1]; j++) {
+            if (found[j] == ~0ull || found[j] <= last || found[j] >= elens[k] * 8) continue;  // (ascending: the targets are)
+            last = found[j];
+            spans.back().stop_bit = found[j];
+            fl_size_span s1 = s0;
+            s1.start_bit = found[j];
+            s1.first = 0;
+            spans.push_back(s1);
+        }
+        sp_first[k + 1] = (uint32_t)spans.size();
+    }
+    const uint32_t nsp = (uint32_t)spans.size();
+    if (nsp == (uint32_t)elig.size()) return 0;  // nothing to cut
+    if (ensure(h, h->sz_spans, sizeof(fl_size_span) * nsp) || ensure(h, h->sz_recs, sizeof(fl_size_rec) * nsp)) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (hipMemcpyAsync(h->sz_spans.p, spans.data(), sizeof(fl_size_span) * nsp, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    {
+        ProfScope ps(h, K_INFLATE_SIZE_SPAN);
+        hipLaunchKernelGGL(k_inflate_size<true>, dim3(nsp), dim3(64), 0, st, d_in, dch, container, flags, (uint64_t*)nullptr,
+                           (int32_t*)nullptr, (uint64_t*)nullptr, (const fl_size_span*)h->sz_spans.p, (fl_size_rec*)h->sz_recs.p);
+    }
+    std::vector<fl_size_rec> recs(nsp);
+    if (hipMemcpyAsync(recs.data(), h->sz_recs.p, sizeof(fl_size_rec) * nsp, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+    if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    // ---- the chains
+    std::vector<fl_span_fin> fin;
+    for (size_t k = 0; k < elig.size(); k++) {
+        const uint32_t a = sp_first[k], b = sp_first[k + 1];
+        if (b - a < 2) continue;  // not cut: the whole-stream launch counts it
+        uint64_t size = 0, used = 0;
+        int32_t stt = 0;
+        if (!fl_size_follow_chain(spans.data() + a, recs.data() + a, b - a, &size, &stt, &used)) continue;
+        fl_span_fin f;
+        f.total = size;
+        f.used = used;
+        f.chunk = elig[k];
+        f.pad = 0;
+        fin.push_back(f);
+        chunks[elig[k]].skip = 1;
+    }
+    if (!fin.empty()) {
+        if (ensure(h, h->sp_fin, sizeof(fl_span_fin) * fin.size())) {
+            (void)hipGetLastError();
+            for (const fl_span_fin& f : fin) chunks[f.chunk].skip = 0;
+            return 0;
+        }
+        if (hipMemcpyAsync(h->sp_fin.p, fin.data(), sizeof(fl_span_fin) * fin.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        hipLaunchKernelGGL(k_span_finish, dim3(((uint32_t)fin.size() + 63) / 64), dim3(64), 0, st, (const fl_span_fin*)h->sp_fin.p,
+                           (uint32_t)fin.size(), d_status, d_sizes, d_consumed);
+        if (hipStreamSynchronize(st) != hipSuccess) return -1;  // (the source is on this stack)
+    }
+    return (int)fin.size();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1398,7 +1528,7 @@ int flate_hip_destroy(flate_hip_handle h) {
     if (h->pin_out) (void)hipHostFree(h->pin_out);
     for (DevBuf* b : {&h->sp_points, &h->sp_found, &h->sp_spans, &h->sp_res, &h->sp_cand, &h->sp_candoff, &h->sp_tails,
                       &h->sp_tails_b, &h->sp_chain, &h->sp_chainoff, &h->sp_pool, &h->sp_pooltab, &h->sp_poolctl, &h->sp_items,
-                      &h->sp_part, &h->sp_footoff, &h->sp_foot, &h->sp_fin, &h->sp_chainpos, &h->sp_rs})
+                      &h->sp_part, &h->sp_footoff, &h->sp_foot, &h->sp_fin, &h->sp_chainpos, &h->sp_rs, &h->sz_spans, &h->sz_recs})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->chunks, &h->blk_chunk, &h->plans, &h->hist, &h->cks, &h->S, &h->NC, &h->rec, &h->desc, &h->marks,
                       &h->tokens, &h->ntok, &h->cflag, &h->links, &h->wchunks, &h->swins, &h->wexit, &h->shard_sz, &h->tiles, &h->segs, &h->pieces, &h->fpts, &h->zones, &h->nsorted, &h->jmp,
@@ -2395,6 +2525,87 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
     } else if (h->sync) {
         HIP_OK(h, hipStreamSynchronize(st));
     }
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
+                                 int container, int flags, uint64_t* sizes, int32_t* status, uint64_t* consumed,
+                                 int memkind) {
+    if (!h || !in_off || !sizes || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (n_chunks == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+
+    std::vector<uint64_t> hin;
+    int rc = fetch_offsets(h, in_off, n_chunks, memkind, hin);
+    if (rc) return rc;
+    const uint64_t in_lo = hin[0], in_hi = hin[n_chunks];
+    const uint8_t* d_in = in;
+    uint64_t* d_sizes = sizes;
+    int32_t* d_status = status;
+    uint64_t* d_consumed = consumed;
+    uint64_t in_shift = 0;
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16))) return rc;
+        if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_chunks))) return rc;
+        if ((rc = ensure(h, h->st_status, sizeof(int32_t) * n_chunks))) return rc;
+        if ((rc = ensure(h, h->st_consumed, sizeof(uint64_t) * n_chunks))) return rc;
+        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+        d_in = (const uint8_t*)h->st_in.p;
+        d_sizes = (uint64_t*)h->st_outlen.p;
+        d_status = (int32_t*)h->st_status.p;
+        d_consumed = (uint64_t*)h->st_consumed.p;
+        in_shift = in_lo;
+    }
+    std::vector<fl_chunk> chunks(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; i++) {
+        const uint64_t len = hin[i + 1] - hin[i];
+        if (len > 0xfffffff0ull) return FLATE_HIP_E_INVALID_ARG;
+        fl_chunk c{};
+        c.in_off = hin[i] - in_shift;
+        c.in_len = (uint32_t)len;
+        chunks[i] = c;
+    }
+    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n_chunks))) return rc;
+    HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));
+    h->dbg_size_chain = h->dbg_size_whole = 0;
+    // A few long streams: each by many waves at once; what comes out whole is skipped below.
+    const int done = size_by_spans(h, st, d_in, chunks, container, flags, d_sizes, d_status, d_consumed);
+    if (done < 0) {
+        h->last_error = std::string("size probe by spans: ") + hipGetErrorString(hipGetLastError());
+        return FLATE_HIP_E_LAUNCH;
+    }
+    if (done > 0) {
+        HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+    }
+    h->dbg_size_chain = (uint64_t)done;
+    h->dbg_size_whole = n_chunks - (uint64_t)done;
+    if ((uint32_t)done < n_chunks) {
+        ProfScope ps(h, K_INFLATE_SIZE);
+        hipLaunchKernelGGL(k_inflate_size<false>, dim3(n_chunks), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p, container,
+                           flags, d_sizes, d_status, d_consumed, (const fl_size_span*)nullptr, (fl_size_rec*)nullptr);
+    }
+    HIP_OK(h, hipGetLastError());
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        HIP_OK(h, hipMemcpyAsync(sizes, d_sizes, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_chunks, hipMemcpyDeviceToHost, st));
+        if (consumed)
+            HIP_OK(h, hipMemcpyAsync(consumed, d_consumed, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+    } else if (h->sync) {
+        HIP_OK(h, hipStreamSynchronize(st));
+    }
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]) {
+    if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
+    counts[0] = h->dbg_size_chain;
+    counts[1] = h->dbg_size_whole;
     return FLATE_HIP_OK;
 }
 

@@ -126,11 +126,47 @@ class Engine:
     def checksum_combine(self, container, a, b, len_b):
         return int(self._L.flate_hip_checksum_combine(container, a, b, len_b))
 
-    def decompress_many(self, streams, container=0, flags=0, caps=None):
+    def _host_input(self, streams):
+        """(blob, in_off) of a host batch"""
+        n = len(streams)
+        lens = np.array([len(c) for c in streams], dtype=np.uint64)
+        in_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(lens, out=in_off[1:])
+        blob = np.frombuffer(b"".join(bytes(c) for c in streams), dtype=np.uint8)
+        if blob.size == 0:
+            blob = np.zeros(1, dtype=np.uint8)
+        return blob, in_off
+
+    def decompressed_sizes(self, streams, container=0, flags=0):
+        """How many bytes each stream inflates to, without inflating it (flate_hip_decompressed_sizes): no output is
+        allocated or written.  The footer is read but not compared, so a stream with a wrong checksum reports 0.
+        Returns (list of sizes -- exact where the status is 0 --, list of status codes, list of consumed input bytes)."""
+        self._sync_env()
+        n = len(streams)
+        if n == 0:
+            return [], [], []
+        blob, in_off = self._host_input(streams)
+        sizes = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int32)
+        consumed = np.zeros(n, dtype=np.uint64)
+        rc = self._L.flate_hip_decompressed_sizes(self._h, blob.ctypes.data, in_off.ctypes.data, n, container, flags,
+                                                  sizes.ctypes.data, status.ctypes.data, consumed.ctypes.data, MEM_HOST)
+        self._check(rc, "flate_hip_decompressed_sizes")
+        return [int(x) for x in sizes], [int(x) for x in status], [int(x) for x in consumed]
+
+    def _measured_caps(self, streams, container, flags, worst):
+        """slots from the size probe: the stream's size + 8 where the probe's status is 0, the worst case elsewhere"""
+        sizes, st, _ = self.decompressed_sizes(streams, container, flags)
+        return [sizes[i] + 8 if st[i] == 0 else worst[i] for i in range(len(streams))]
+
+    def decompress_many(self, streams, container=0, flags=0, caps=None, measure=False):
         """streams: sequence of bytes-like.  caps: output capacity per stream.  Default: for gzip the ISIZE
         field of the stream's last 8 bytes (container.zig:92-96) plus slack, and whatever then reports
         OutputTooSmall (more members behind the first, a damaged footer) is decoded again with the worst
         case of 1100 output bytes per input byte; raw / zlib streams get the worst case at once.
+        measure=True (with caps=None): the slots come from the size probe instead of the worst case -- a stream's
+        exact size + 8 where the probe's status is 0; for gzip only the streams whose ISIZE guess came back
+        OutputTooSmall are probed, before their second decode.
         Returns (list of bytes, list of status codes, list of consumed input bytes)."""
         self._sync_env()
         n = len(streams)
@@ -143,7 +179,11 @@ class Engine:
             res, st, cons = self.decompress_many(streams, container, flags, guess)
             redo = [i for i in range(n) if st[i] == 100 and guess[i] < worst[i]]  # FLATE_HIP_ST_OUTPUT_TOO_SMALL
             if redo:
-                r2, s2, c2 = self.decompress_many([streams[i] for i in redo], container, flags, [worst[i] for i in redo])
+                again = [streams[i] for i in redo]
+                caps2 = [worst[i] for i in redo]
+                if measure:
+                    caps2 = self._measured_caps(again, container, flags, caps2)
+                r2, s2, c2 = self.decompress_many(again, container, flags, caps2)
                 for k, i in enumerate(redo):
                     res[i], st[i], cons[i] = r2[k], s2[k], c2[k]
             return res, st, cons
@@ -155,6 +195,8 @@ class Engine:
             blob = np.zeros(1, dtype=np.uint8)
         if caps is None:
             caps = [max(1 << 16, int(l) * 1100 + 1024) for l in lens]
+            if measure:
+                caps = self._measured_caps(streams, container, flags, caps)
         caps = np.array([(int(c) + 7) & ~7 for c in caps], dtype=np.uint64)
         out_off = np.zeros(n + 1, dtype=np.uint64)
         np.cumsum(caps, out=out_off[1:])
@@ -203,6 +245,22 @@ class Engine:
         rc = self._L.flate_hip_decompress_batch(self._h, in_ptr, in_off_ptr, n_chunks, container, flags, out_ptr,
                                                 out_off_ptr, out_len_ptr, status_ptr, consumed_ptr, MEM_DEVICE)
         self._check(rc, "flate_hip_decompress_batch")
+
+    def decompressed_sizes_device(self, in_ptr, in_off_ptr, n_chunks, container, flags, sizes_ptr, status_ptr,
+                                  consumed_ptr=None):
+        """The size probe on device memory (n + 1 offsets, n sizes / statuses / consumed): enqueued on the handle's
+        stream unless the batch has long streams that are cut (flate_hip_decompressed_sizes)."""
+        self._sync_env()
+        rc = self._L.flate_hip_decompressed_sizes(self._h, in_ptr, in_off_ptr, n_chunks, container, flags, sizes_ptr,
+                                                  status_ptr, consumed_ptr, MEM_DEVICE)
+        self._check(rc, "flate_hip_decompressed_sizes")
+
+    def size_paths(self):
+        """How the last size probe got its sizes: (streams summed over a closed chain of spans, streams counted whole
+        by one wave) (flate_hip_debug_size_paths)."""
+        v = np.zeros(2, dtype=np.uint64)
+        self._check(self._L.flate_hip_debug_size_paths(self._h, v.ctypes.data), "flate_hip_debug_size_paths")
+        return int(v[0]), int(v[1])
 
     def inflater(self, n, container, flags=0):
         """n resumable stream decoders (flate_hip_inflater_*): feed each its input piece by piece, in bounded memory."""

@@ -199,6 +199,35 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
                                uint64_t* consumed, int memkind);
 
 /*
+ * Size probe: how many bytes each of n_chunks independent streams inflates to, without inflating it.  The arguments have
+ * the shape of flate_hip_decompress_batch without `out` and `out_off`; flags bit 0 = FLATE_HIP_INFLATE_STRICT_Q6;
+ * consumed may be NULL.
+ *   status[i]    what flate_hip_decompress_batch reports for stream i with a slot that is large enough, with one
+ *                exception: the footer is read but not compared (there are no bytes to sum).  A truncated footer is
+ *                still EndOfStream; where decompress would report WrongGzipChecksum, WrongGzipSize or WrongZlibChecksum
+ *                the probe reports 0.  OutputTooSmall never occurs.  InvalidMatch is exact: a distance beyond the bytes
+ *                produced so far is refused, as are a length or distance out of range.
+ *   sizes[i]     status[i] == 0: exactly the out_len[i] decompress would produce (64-bit: a stream's output may exceed
+ *                4 GiB).  status[i] != 0: unspecified.
+ *   consumed[i]  as for decompress: header, blocks and footer of the first member, trailing bytes not counted, so a
+ *                caller can walk concatenated members.
+ * Nothing is written anywhere except sizes, status and consumed.  The handle's workspace does not grow with the output:
+ * per stream it holds the chunk table entry and, for a long stream, its scan points and span records.
+ * FLATE_HIP_MEM_HOST: the input is staged and the call is synchronous.  FLATE_HIP_MEM_DEVICE: all arrays are device
+ * memory; the offsets are read back once, as decompress does.  A batch without a stream that is cut only enqueues its
+ * kernel on the handle's stream and flate_hip_set_sync decides about the final wait.  Long streams (at least
+ * FLATE_HIP_INFLATE_SPANS bytes, 128 KiB by default; at most 256 of them, in a batch with no more long streams than the
+ * device has CUs; never with flag bit 0) are cut at block starts and counted by many waves at once: such a call WAITS
+ * ON THE HOST twice (for the block starts found, for the span records, whose chain is followed on the CPU) and once
+ * more for the results it writes itself.  A stream whose chain does not close is counted whole by one wave: always
+ * correct, only slow.  n_chunks == 0 returns FLATE_HIP_OK; argument errors as for decompress.  The counters of
+ * flate_hip_debug_inflate_paths are left untouched.
+ */
+int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
+                                 int container, int flags, uint64_t* sizes, int32_t* status, uint64_t* consumed,
+                                 int memkind);
+
+/*
  * Pack the n_chunks produced streams back to back (device memory only): copies
  * out[out_off[i] .. out_off[i] + out_len[i]) to dst[dst_off[i] ..) with
  * dst_off[i] = sum of out_len[k] for k < i; dst_off has n_chunks + 1 entries (the last
@@ -332,6 +361,9 @@ int flate_hip_debug_workspace_bytes(flate_hip_handle h, uint64_t* bytes);
  * kernel (too short by its rule, irregular, or a checksum that did not match).  Every stream not counted in [0] or
  * [2] was decoded by the wave-per-stream kernel.  Waits for the handle's stream. */
 int flate_hip_debug_inflate_paths(flate_hip_handle h, uint64_t counts[4]);
+/* test seam: for the handle's last flate_hip_decompressed_sizes call, counts[0]: streams whose size came from a closed
+ * chain of spans; counts[1]: streams counted whole by one wave. */
+int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]);
 
 /* The containers' checksums on their own (container.zig:168-206: std.hash.Crc32 / Adler32 over the raw
  * input): container 1 = CRC-32, 2 = Adler-32 of a host buffer, computed by the checksum kernels; and the
