@@ -227,6 +227,16 @@ int ensure(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
     return FLATE_HIP_OK;
 }
 
+// compute units of the device, asked once (256 where the device does not say)
+uint32_t device_cu_count(flate_hip_ctx* h) {
+    if (h->n_cu == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || v <= 0) v = 256;
+        h->n_cu = (uint32_t)v;
+    }
+    return h->n_cu;
+}
+
 hipEvent_t get_event(flate_hip_ctx* h) {
     if (!h->free_events.empty()) {
         hipEvent_t e = h->free_events.back();
@@ -427,11 +437,7 @@ int compress_stream_pass(flate_hip_ctx* h, const uint8_t* d_in, const fl_params&
     bool grouped = false;  // some stream is split into groups of windows: a fix launch follows (kernels_parse.h)
     uint32_t round_cap = 0;  // rounds of a window's stitch after which the pass is given to the tiles (0: never)
     if (windows) {
-        if (h->n_cu == 0) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || v <= 0) v = 256;
-            h->n_cu = (uint32_t)v;
-        }
+        const uint32_t n_cu = device_cu_count(h);
         uint64_t bytes = 0, total_win = 0;
         for (uint32_t i = 0; i < nc; i++) {
             bytes += hch[i].in_len;
@@ -443,7 +449,7 @@ int compress_stream_pass(flate_hip_ctx* h, const uint8_t* d_in, const fl_params&
         // per CU of at least four windows: one 1 MiB stream at level 6 cost 1.9 ms against 1.05 as 32 groups of one window, and
         // 1.34 on the sort / match tiles; one 177 MB stream at level 9 as 675 groups of 8 took 2 x 8 + 2 window times, as 491
         // groups of 11 it takes 11 + 1.  tools/small_stream_round.sh)
-        const uint64_t slots = deep_walk ? 2ull * h->n_cu : (uint64_t)h->n_cu;
+        const uint64_t slots = deep_walk ? 2ull * n_cu : (uint64_t)n_cu;
         uint32_t G = ~0u;
         if (nc < slots) G = (uint32_t)std::max<uint64_t>(1, (total_win + slots - 1) / slots);
         if (h->knobs.stream_group) G = h->knobs.stream_group;
@@ -924,6 +930,28 @@ int enqueue_pass(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t n
 }
 
 
+// k_span_scan over `points`: found[j] is the block start it found for points[j], on the host when this returns (one host
+// wait).  Returns 1, or 0 when there is no room for the scan's buffers (the caller decodes every stream whole), or -1
+// (a HIP call failed).
+int scan_block_starts(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, int flags, const std::vector<fl_scan_point>& points,
+                      std::vector<uint64_t>& found) {
+    const uint32_t npts = (uint32_t)points.size();
+    if (ensure(h, h->sp_points, sizeof(fl_scan_point) * npts) || ensure(h, h->sp_found, sizeof(uint64_t) * npts)) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (hipMemcpyAsync(h->sp_points.p, points.data(), sizeof(fl_scan_point) * npts, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    {
+        ProfScope ps(h, K_SPAN_SCAN);
+        hipLaunchKernelGGL(k_span_scan, dim3(npts), dim3(FP_THREADS), 0, st, d_in, (const fl_chunk*)h->chunks.p, flags,
+                           (const fl_scan_point*)h->sp_points.p, (uint64_t*)h->sp_found.p);
+    }
+    found.resize(npts);
+    if (hipMemcpyAsync(found.data(), h->sp_found.p, sizeof(uint64_t) * npts, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+    if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    return 1;
+}
+
 // Long streams, few of them: cut each at block starts into spans and decode the spans at once, twice
 // (kernels_inflate_par.h, "spans").  Streams that come out whole get their status / out_len / consumed here and
 // chunks[i].skip = 1 (the kernels that follow leave them alone); everything else stays as it was.
@@ -947,11 +975,7 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     std::vector<uint32_t> elig;
     uint32_t n_long = 0;
     for (uint32_t i = 0; i < n_chunks; i++) n_long += chunks[i].in_len >= 32768u ? 1u : 0u;
-    if (h->n_cu == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || v <= 0) v = 256;
-        h->n_cu = (uint32_t)v;
-    }
+    const uint32_t n_cu = device_cu_count(h);
     // More long streams than that, but fewer than CUs (config #5: 128 members on 256 CUs): every long stream is cut
     // ONCE, where about f = 2 S / (CUs + S) of it lies before the cut, and both runs of the second spans go in one launch
     // with the first spans (TWIN): the CUs the first spans leave free decode the second spans twice in the time the
@@ -961,7 +985,7 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     // are too long cost more than first spans that are: 1.5 % are added to f.
     const int etw = h->knobs.span_twin;  // FLATE_HIP_SPAN_TWIN -- -1: unset; 0: never; 2..950: where to cut, in thousandths of the stream (tuning)
     const bool sym = !h->knobs.span_two_runs;  // one decode per span, in symbols (kernels_inflate_par.h)
-    const bool twin = n_long > FL_SPAN_STREAMS && etw != 0 && (size_t)n_long * 20 <= (size_t)h->n_cu * 11;  // (40 / 64 / 96 / 160 / 200 one-MiB members: 7.9 / 7.9 / 13.0 / 13.0 / 13.0 ms a workgroup each, 6.1 / 6.1 / 9.1 / 13.3 / 13.4 this way)
+    const bool twin = n_long > FL_SPAN_STREAMS && etw != 0 && (size_t)n_long * 20 <= (size_t)n_cu * 11;  // (40 / 64 / 96 / 160 / 200 one-MiB members: 7.9 / 7.9 / 13.0 / 13.0 / 13.0 ms a workgroup each, 6.1 / 6.1 / 9.1 / 13.3 / 13.4 this way)
     if (n_long > FL_SPAN_STREAMS && !twin) return 0;
     const uint64_t elig_bytes = twin ? std::min<uint64_t>(min_bytes, 32768u) : min_bytes;
     for (uint32_t i = 0; i < n_chunks; i++)
@@ -982,8 +1006,8 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     auto weight = [&](const fl_chunk& c) { return std::max<uint64_t>(c.in_len, std::min<uint64_t>(c.out_cap, 32ull * c.in_len)); };
     uint64_t elig_w = 0;
     for (uint32_t ci : elig) elig_w += weight(chunks[ci]);
-    const uint64_t rounds = std::min<uint64_t>(4, std::max<uint64_t>(1, (elig_w + h->n_cu * 393216ull) / (h->n_cu * 786432ull)));
-    const uint64_t want = std::min<uint64_t>({(uint64_t)FL_SPAN_MAX, rounds * h->n_cu - std::min<uint32_t>(8u, h->n_cu / 2), std::max<uint64_t>(2, elig_w / (3 * FL_SPAN_BYTES))});
+    const uint64_t rounds = std::min<uint64_t>(4, std::max<uint64_t>(1, (elig_w + n_cu * 393216ull) / (n_cu * 786432ull)));
+    const uint64_t want = std::min<uint64_t>({(uint64_t)FL_SPAN_MAX, rounds * n_cu - std::min<uint32_t>(8u, n_cu / 2), std::max<uint64_t>(2, elig_w / (3 * FL_SPAN_BYTES))});
     for (size_t k = 0; k < elig.size(); k++) {
         const fl_chunk& c = chunks[elig[k]];
         const uint64_t bits = (uint64_t)c.in_len * 8;
@@ -992,8 +1016,8 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
             fl_scan_point pt;
             // (two runs: f = 2 S / (CUs + S) of the stream before the cut, + 1.5 %; one decode in symbols, 1.25 x the cost of a decode in
             // bytes: f = 1.25 S / (CUs + S / 4))
-            const uint64_t auto_f = sym ? std::min<uint64_t>(900, std::max<uint64_t>(500, 1250ull * elig.size() / (h->n_cu + elig.size() / 4) + 10))
-                                        : std::min<uint64_t>(900, std::max<uint64_t>(500, 2000ull * elig.size() / (h->n_cu + elig.size()) + 15));
+            const uint64_t auto_f = sym ? std::min<uint64_t>(900, std::max<uint64_t>(500, 1250ull * elig.size() / (n_cu + elig.size() / 4) + 10))
+                                        : std::min<uint64_t>(900, std::max<uint64_t>(500, 2000ull * elig.size() / (n_cu + elig.size()) + 15));
             pt.from_bit = twin ? bits / 1000 * (etw > 1 ? (uint64_t)std::min(950, etw) : auto_f) : bits / P * j;
             pt.limit_bit = j + 1 < P ? bits / P * (j + 1) : bits;
             pt.stream = elig[k];
@@ -1003,18 +1027,9 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
         pt_first[k + 1] = (uint32_t)points.size();
     }
     const uint32_t npts = (uint32_t)points.size();
-    if ((rc = ensure(h, h->sp_points, sizeof(fl_scan_point) * npts))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_found, sizeof(uint64_t) * npts))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if (hipMemcpyAsync(h->sp_points.p, points.data(), sizeof(fl_scan_point) * npts, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    std::vector<uint64_t> found;
+    if (const int sc = scan_block_starts(h, st, d_in, flags, points, found); sc <= 0) return sc;
     const fl_chunk* dch = (const fl_chunk*)h->chunks.p;
-    {
-        ProfScope ps(h, K_SPAN_SCAN);
-        hipLaunchKernelGGL(k_span_scan, dim3(npts), dim3(FP_THREADS), 0, st, d_in, dch, flags,
-                           (const fl_scan_point*)h->sp_points.p, (uint64_t*)h->sp_found.p);
-    }
-    std::vector<uint64_t> found(npts);
-    if (hipMemcpyAsync(found.data(), h->sp_found.p, sizeof(uint64_t) * npts, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
-    if (hipStreamSynchronize(st) != hipSuccess) return -1;
     if (dbg) fprintf(stderr, "[spans] %.3f ms: sync 1 done\n", since());
     // ---- the spans: the stream start, then every distinct position found
     std::vector<fl_span> spans;
@@ -1345,19 +1360,15 @@ int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::ve
                   uint64_t* d_sizes, int32_t* d_status, uint64_t* d_consumed) {
     const uint32_t n_chunks = (uint32_t)chunks.size();
     if (flags & 1) return 0;  // (as decompress: the scan's first two steps know the lenient header only)
-    if (h->n_cu == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || v <= 0) v = 256;
-        h->n_cu = (uint32_t)v;
-    }
+    const uint32_t n_cu = device_cu_count(h);
     std::vector<uint64_t> lens(n_chunks);
     for (uint32_t i = 0; i < n_chunks; i++) lens[i] = chunks[i].in_len;
     std::vector<uint32_t> elig, pieces;
-    fl_size_eligible(lens.data(), n_chunks, h->knobs.span_min_bytes, h->n_cu, elig);
+    fl_size_eligible(lens.data(), n_chunks, h->knobs.span_min_bytes, n_cu, elig);
     if (elig.empty()) return 0;
     std::vector<uint64_t> elens(elig.size());
     for (size_t k = 0; k < elig.size(); k++) elens[k] = lens[elig[k]];
-    fl_size_spacing(elens.data(), (uint32_t)elig.size(), h->n_cu, pieces);
+    fl_size_spacing(elens.data(), (uint32_t)elig.size(), n_cu, pieces);
     // ---- where spans may start
     std::vector<fl_scan_point> points;
     std::vector<uint32_t> pt_first(elig.size() + 1, 0);
@@ -1377,20 +1388,9 @@ int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::ve
     }
     const uint32_t npts = (uint32_t)points.size();
     if (!npts) return 0;
-    if (ensure(h, h->sp_points, sizeof(fl_scan_point) * npts) || ensure(h, h->sp_found, sizeof(uint64_t) * npts)) {
-        (void)hipGetLastError();  // (no room: every stream whole)
-        return 0;
-    }
-    if (hipMemcpyAsync(h->sp_points.p, points.data(), sizeof(fl_scan_point) * npts, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    std::vector<uint64_t> found;
+    if (const int sc = scan_block_starts(h, st, d_in, flags, points, found); sc <= 0) return sc;
     const fl_chunk* dch = (const fl_chunk*)h->chunks.p;
-    {
-        ProfScope ps(h, K_SPAN_SCAN);
-        hipLaunchKernelGGL(k_span_scan, dim3(npts), dim3(FP_THREADS), 0, st, d_in, dch, flags,
-                           (const fl_scan_point*)h->sp_points.p, (uint64_t*)h->sp_found.p);
-    }
-    std::vector<uint64_t> found(npts);
-    if (hipMemcpyAsync(found.data(), h->sp_found.p, sizeof(uint64_t) * npts, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
-    if (hipStreamSynchronize(st) != hipSuccess) return -1;
     // ---- the spans: the stream start, then every distinct position found; a span ends where the next one starts
     std::vector<fl_size_span> spans;
     std::vector<uint32_t> sp_first(elig.size() + 1, 0);

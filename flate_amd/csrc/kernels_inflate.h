@@ -442,6 +442,12 @@ __device__ __forceinline__ int fl_inf_literal(fl_inf_out& o, uint32_t byte, uint
     fl_inf_advance(o, lane);
     return 0;
 }
+// Where a decoded token goes, overloaded on the decoder's output: here the bytes are produced; the size probe's counter
+// (kernels_inflate_size.h) adds their number up.
+__device__ __forceinline__ int fl_sink_literal(fl_inf_out& o, uint32_t byte, uint32_t lane) { return fl_inf_literal(o, byte, lane); }
+__device__ __forceinline__ int fl_sink_match(fl_inf_out& o, uint32_t length, uint32_t distance, uint32_t lane) {
+    return fl_inf_match(o, length, distance, lane);
+}
 
 // (the status is pinned to a scalar register: a status that depends on something read from LDS is divergent as far as
 // the compiler knows, and every loop that ends on it would keep the stream position in vector registers)
@@ -473,73 +479,88 @@ __device__ __forceinline__ int fl_inf_distance(fl_bitr& r, uint32_t code, uint32
     return 0;
 }
 
-// inflate.zig:89-102
-__device__ __forceinline__ int fl_inf_stored(fl_bitr& r, fl_inf_out& o, uint32_t lane) {
+// inflate.zig:89-97: the header of a stored block, whose body the input must hold whole
+__device__ __forceinline__ int fl_inf_stored_header(fl_bitr& r, uint32_t& len) {
     fl_br_align(r);
-    uint32_t len, nlen;
+    uint32_t nlen;
     FL_TRY(fl_br_read(r, 16, len));
     FL_TRY(fl_br_read(r, 16, nlen));
+    len = fl_uni(len);  // (pinned for the register allocator alone: wave-uniform already, but it came through LDS)
+    nlen = fl_uni(nlen);
     if (len != ((~nlen) & 0xffff)) return 13;
     if ((int64_t)len * 8 > r.left) return 1;
-    if (o.wp + len > o.cap) return 100;
+    return 0;
+}
+// inflate.zig:98-101: n bytes of a stored block's body, which the input holds and the output has room for
+__device__ __forceinline__ void fl_inf_stored_copy(fl_bitr& r, fl_inf_out& o, uint32_t n, uint32_t lane) {
     const uint32_t src_off = (uint32_t)fl_br_consumed(r);  // byte aligned here
     const uint8_t* s = r.data + src_off;
     fl_inf_flush(o, o.wp, lane);  // what the ring still holds goes out first
-    for (uint32_t i = lane; i < len; i += 64) o.out[o.wp + i] = s[i];
+    for (uint32_t i = lane; i < n; i += 64) o.out[o.wp + i] = s[i];
     // the ring mirrors the last bytes of the output
     {
-        const uint32_t tail = len < o.rmask + 1 ? len : o.rmask + 1;
+        const uint32_t tail = n < o.rmask + 1 ? n : o.rmask + 1;
         fl_lds_order();
         for (uint32_t i = lane; i < tail; i += 64) {
-            const uint64_t off = o.wp + len - tail + i;
-            o.ring[((uint32_t)off + o.bias) & o.rmask] = s[len - tail + i];
+            const uint64_t off = o.wp + n - tail + i;
+            o.ring[((uint32_t)off + o.bias) & o.rmask] = s[n - tail + i];
         }
         fl_lds_order();
     }
-    o.wp += len;
+    o.wp += n;
     o.flushed = o.wp;
-    r.left -= (int64_t)len * 8;
-    fl_br_seek(r, src_off + len);
+    r.left -= (int64_t)n * 8;
+    fl_br_seek(r, src_off + n);
+}
+// inflate.zig:89-102
+__device__ __forceinline__ int fl_inf_stored(fl_bitr& r, fl_inf_out& o, uint32_t lane) {
+    uint32_t len;
+    FL_TRY(fl_inf_stored_header(r, len));
+    if (o.wp + len > o.cap) return 100;
+    fl_inf_stored_copy(r, o, len, lane);
     return 0;
 }
 
-// bit_reader.zig:205-217 + inflate.zig:104-121
-__device__ __forceinline__ int fl_inf_fixed(fl_bitr& r, fl_inf_out& o, uint32_t lane) {
+// bit_reader.zig:205-217 + inflate.zig:104-121 for ONE symbol of the fixed code, which goes to the sink O (fl_sink_*);
+// -1 at the end of the block
+template <class O>
+__device__ __forceinline__ int fl_inf_fixed_symbol(fl_bitr& r, O& o, uint32_t lane) {
+    FL_TRY(fl_br_fill(r, 9));
+    const uint32_t code7 = fl_rev_bits(fl_br_peek(r, 7), 7);
+    FL_TRY(fl_br_shift(r, 7));
+    uint32_t code;
+    if (code7 <= 0x17) {
+        code = code7 + 256;
+    } else if (code7 <= 0x5f) {
+        const uint32_t e = fl_br_peek(r, 1);
+        FL_TRY(fl_br_shift(r, 1));
+        code = (code7 << 1) + e - 0x30;
+    } else if (code7 <= 0x63) {
+        const uint32_t e = fl_br_peek(r, 1);
+        FL_TRY(fl_br_shift(r, 1));
+        code = ((code7 - 0x60) << 1) + e + 280;
+    } else {
+        const uint32_t e = fl_rev_bits(fl_br_peek(r, 2), 2);
+        FL_TRY(fl_br_shift(r, 2));
+        code = ((code7 - 0x64) << 2) + e + 144;
+    }
+    if (code <= 255) return fl_sink_literal(o, code, lane);
+    if (code == 256) return -1;
+    if (code > 285) return 7;
+    FL_TRY(fl_br_fill(r, 5 + 5 + 13));
+    uint32_t length, distance;
+    FL_TRY(fl_inf_length(r, code - 257, length));
+    const uint32_t dcode = fl_rev_bits(fl_br_peek(r, 5), 5);
+    FL_TRY(fl_br_shift(r, 5));
+    FL_TRY(fl_inf_distance(r, dcode, distance));
+    return fl_sink_match(o, length, distance, lane);
+}
+template <class O>
+__device__ __forceinline__ int fl_inf_fixed(fl_bitr& r, O& o, uint32_t lane) {
     for (;;) {
-        FL_TRY(fl_br_fill(r, 9));
-        const uint32_t code7 = fl_rev_bits(fl_br_peek(r, 7), 7);
-        FL_TRY(fl_br_shift(r, 7));
-        uint32_t code;
-        if (code7 <= 0x17) {
-            code = code7 + 256;
-        } else if (code7 <= 0x5f) {
-            const uint32_t e = fl_br_peek(r, 1);
-            FL_TRY(fl_br_shift(r, 1));
-            code = (code7 << 1) + e - 0x30;
-        } else if (code7 <= 0x63) {
-            const uint32_t e = fl_br_peek(r, 1);
-            FL_TRY(fl_br_shift(r, 1));
-            code = ((code7 - 0x60) << 1) + e + 280;
-        } else {
-            const uint32_t e = fl_rev_bits(fl_br_peek(r, 2), 2);
-            FL_TRY(fl_br_shift(r, 2));
-            code = ((code7 - 0x64) << 2) + e + 144;
-        }
-        if (code <= 255) {
-            FL_TRY(fl_inf_literal(o, code, lane));
-        } else if (code == 256) {
-            return 0;
-        } else if (code <= 285) {
-            FL_TRY(fl_br_fill(r, 5 + 5 + 13));
-            uint32_t length, distance;
-            FL_TRY(fl_inf_length(r, code - 257, length));
-            const uint32_t dcode = fl_rev_bits(fl_br_peek(r, 5), 5);
-            FL_TRY(fl_br_shift(r, 5));
-            FL_TRY(fl_inf_distance(r, dcode, distance));
-            FL_TRY(fl_inf_match(o, length, distance, lane));
-        } else {
-            return 7;
-        }
+        const int rc = (int)fl_uni((uint32_t)fl_inf_fixed_symbol(r, o, lane));
+        if (rc < 0) return 0;
+        if (rc) return rc;
     }
 }
 
@@ -717,13 +738,20 @@ __device__ __forceinline__ uint32_t fl_wave_incl_max_dpp(uint32_t v) {
 // the exec mask).  The round's predicates are kept as masks and combined on the scalar side: written as lane booleans
 // the compiler turned every combination into a 0/1 vector register and compared it again.
 #define FL_INV(m) __builtin_amdgcn_inverse_ballot_w64(m)
-__device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, fl_inf_out& o, uint32_t lane) {
-    FL_T0();
-    const uint64_t left0 = fl_uni64((uint64_t)r.left);
+// What steps (1) and (2) of a round produce, for the decoder (fl_inf_fast_round) and the size probe (fl_sz_fast_round)
+struct fl_round {
+    uint32_t lsym, lcb, dist, olen, nb;       // per lane: the token that would start at "current bit + lane"
+    bool is_lit, is_match;                    // ... it is a plain literal / a plain match (m_lit, m_match as lane predicates)
+    uint64_t m_lok, m_lit, m_match, m_plain;  // lanes whose literal / length code the table holds whole; plain = lit | match
+    uint64_t S;                               // lanes that are token starts
+    uint32_t consumed;                        // bits of the stream the round takes
+    int rc;                                   // 0 = go on, 1 = end of block, 2 = the next symbol needs the slow path
+};
+// ---- (1) the token that starts at pos + lane; left0 = r.left, pinned ----
+__device__ __forceinline__ void fl_round_decode(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, uint64_t left0, uint32_t lane, fl_round& t) {
     const uint64_t pos = (uint64_t)fl_uni(r.nbytes) * 8 - left0;
     const uint32_t byte0 = (uint32_t)(pos >> 3);
     if (__builtin_expect(byte0 + 24 > fl_uni(r.in_loaded), 0)) fl_br_commit_half(r);
-    // ---- (1) the token that starts at pos + lane ----
     const uint32_t bp = ((byte0 & (FL_INF_INRING - 1)) << 3) + ((uint32_t)pos & 7) + lane;  // bit index in the ring
     const uint32_t di = bp >> 5;
     const uint32_t IM = FL_INF_INRING / 4 - 1;
@@ -731,46 +759,35 @@ __device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_w
     const uint32_t w0 = __builtin_amdgcn_alignbit(d1, d0, bp & 31);  // stream bits [pos + lane, + 32)
     const uint32_t w1 = __builtin_amdgcn_alignbit(d2, d1, bp & 31);  // ... [+ 32, + 64)
     const uint32_t le = ws->lit_lut[w0 & ((1u << FL_INF_LIT_BITS) - 1)];
-    const uint32_t lsym = le & 511, lcb = (le >> 9) & 15, leb = le >> 13;
-    const uint64_t m_lok = FL_BALLOT(le != 0) & FL_BALLOT(leb != 7);
-    const uint64_t m_lit = m_lok & FL_BALLOT(lsym < 256);
-    const uint32_t lbits = lcb + leb;  // at most 10 + 5
+    const uint32_t leb = le >> 13;
+    t.lsym = le & 511;
+    t.lcb = (le >> 9) & 15;
+    t.m_lok = FL_BALLOT(le != 0) & FL_BALLOT(leb != 7);
+    t.m_lit = t.m_lok & FL_BALLOT(t.lsym < 256);
+    const uint32_t lbits = t.lcb + leb;  // at most 10 + 5
     const uint32_t wd = __builtin_amdgcn_alignbit(w1, w0, lbits & 31);  // the 32 bits behind the length code
     const uint32_t de = ws->dst_lut[wd & ((1u << FL_INF16_DST_BITS) - 1)];
     const uint32_t dsym = de & 31, dcb = (de >> 5) & 15, deb = de >> 9;
-    const uint64_t m_match = m_lok & FL_BALLOT(lsym > 256) & FL_BALLOT(de != 0) & FL_BALLOT(deb != 15);
-    const uint64_t m_plain = m_lit | m_match;
-    const bool is_lit = FL_INV(m_lit), is_match = FL_INV(m_match);
+    t.m_match = t.m_lok & FL_BALLOT(t.lsym > 256) & FL_BALLOT(de != 0) & FL_BALLOT(deb != 15);
+    t.m_plain = t.m_lit | t.m_match;
+    t.is_lit = FL_INV(t.m_lit);
+    t.is_match = FL_INV(t.m_match);
     // base values (inflate.zig:123-140) from the code and its extra-bit count
-    const uint32_t lc = lsym - 257;
+    const uint32_t lc = t.lsym - 257;
     // (selects, not branches: written with ?: inside ?: the compiler masked lanes in and out around three instructions)
     uint32_t lbase = ((4u | (lc & 3u)) << leb) + 3u;
     lbase = FL_INV(FL_BALLOT(leb != 0)) ? lbase : lc + 3u;
     lbase = FL_INV(FL_BALLOT(lc == 28u)) ? 258u : lbase;
     uint32_t dbase = ((2u | (dsym & 1u)) << deb) + 1u;
     dbase = FL_INV(FL_BALLOT(deb != 0)) ? dbase : dsym + 1u;
-    const uint32_t length = lbase + ((w0 >> lcb) & ((1u << leb) - 1));
-    const uint32_t dist = dbase + ((wd >> dcb) & ((1u << deb) - 1));
+    const uint32_t length = lbase + ((w0 >> t.lcb) & ((1u << leb) - 1));
+    t.dist = dbase + ((wd >> dcb) & ((1u << deb) - 1));
     // anything that is not a plain literal or match ends the chain: it is the last member of S
-    const uint32_t nb = is_lit ? lcb : is_match ? lbits + dcb + deb : 64u;
-    const uint32_t olen = is_lit ? 1u : is_match ? length : 0u;
-    // The rest is wave-uniform; the compiler cannot see that for anything that came out of LDS, so the state is
-    // pinned to scalar registers explicitly.
-    const uint64_t wp0 = fl_uni64(o.wp);
-    const uint64_t cap = fl_uni64(o.cap);
-    // (32-bit halves: there is no 64-bit scalar compare, and the vector one costs a constant pair and the compare each time)
-    const uint64_t roomq = cap - wp0;
-    const uint32_t room0 = (uint32_t)(roomq >> 32) ? 0x40000000u : min((uint32_t)roomq, 0x40000000u);  // output bytes left (saturated)
-    const uint32_t hist0 = (uint32_t)(wp0 >> 32) ? 0x100000u : min((uint32_t)wp0, 0x100000u);  // bytes a match may reach back (saturated)
-    int32_t unfl0 = (int32_t)fl_uni((uint32_t)(wp0 - o.flushed));                // unflushed bytes = unfl0 + adv
-    const uint32_t bias = fl_uni(o.bias), rmask = fl_uni(o.rmask), near_max = fl_uni(o.near_max);
-    const uint32_t vp0 = (uint32_t)wp0 + bias;  // ring position of output byte wp0 (low bits)
-#ifdef FL_INF_COUNT  // tuning build only (tools/inflate_probe.py): cycles of the table lookups vs the rest
-    if (__builtin_amdgcn_readlane((int)nb, 0) == 0x7fffffff) return 5;  // wait for the lookups
-    FL_TACC(44);
-    const uint64_t t1_ = __builtin_readcyclecounter();
-#endif
-    // ---- (2) the chain of token starts ----
+    t.nb = t.is_lit ? t.lcb : t.is_match ? lbits + dcb + deb : 64u;
+    t.olen = t.is_lit ? 1u : t.is_match ? length : 0u;
+}
+// ---- (2) the chain of token starts ----
+__device__ __forceinline__ void fl_round_chain(fl_round& t) {
     // Four instructions per token, by hand (the compiler's loop has six: shift, or, readlane, add, compare, branch; with the
     // scalar pipe at 0.83 of its issue rate 17.5 -> 16.7 ms): the position is kept as p - 64 (mod 2^32), whose low six
     // bits -- all that s_bitset1 and the lane select of v_readlane look at -- are those of p, and whose sum with the
@@ -784,23 +801,52 @@ __device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_w
         "s_add_u32 %[p], %[p], %[n]\n\t"
         "s_cbranch_scc0 1b\n\t"
         : [S] "+s"(S), [p] "+s"(p), [n] "=&s"(pn)
-        : [nb] "v"(nb)
+        : [nb] "v"(t.nb)
         : "scc");
     p += 64u;
-    int rc = 0;
-    uint32_t consumed = p;
-    {
-        const uint32_t top = 63u - (uint32_t)__builtin_clzll(S);
-        if (__builtin_expect(!((m_plain >> top) & 1), 0)) {
-            if (((m_lok & FL_BALLOT(lsym == 256)) >> top) & 1) {
-                consumed = top + (uint32_t)__builtin_amdgcn_readlane((int)lcb, (int)top);
-                rc = 1;
-            } else {
-                consumed = top;
-                rc = 2;
-            }
+    t.S = S;
+    t.rc = 0;
+    t.consumed = p;
+    const uint32_t top = 63u - (uint32_t)__builtin_clzll(S);
+    if (__builtin_expect(!((t.m_plain >> top) & 1), 0)) {
+        if (((t.m_lok & FL_BALLOT(t.lsym == 256)) >> top) & 1) {
+            t.consumed = top + (uint32_t)__builtin_amdgcn_readlane((int)t.lcb, (int)top);
+            t.rc = 1;
+        } else {
+            t.consumed = top;
+            t.rc = 2;
         }
     }
+}
+
+__device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, fl_inf_out& o, uint32_t lane) {
+    FL_T0();
+    const uint64_t left0 = fl_uni64((uint64_t)r.left);
+    fl_round t;
+    fl_round_decode(r, ws, left0, lane, t);
+    // The rest is wave-uniform; the compiler cannot see that for anything that came out of LDS, so the state is
+    // pinned to scalar registers explicitly.
+    const uint64_t wp0 = fl_uni64(o.wp);
+    const uint64_t cap = fl_uni64(o.cap);
+    // (32-bit halves: there is no 64-bit scalar compare, and the vector one costs a constant pair and the compare each time)
+    const uint64_t roomq = cap - wp0;
+    const uint32_t room0 = (uint32_t)(roomq >> 32) ? 0x40000000u : min((uint32_t)roomq, 0x40000000u);  // output bytes left (saturated)
+    const uint32_t hist0 = (uint32_t)(wp0 >> 32) ? 0x100000u : min((uint32_t)wp0, 0x100000u);  // bytes a match may reach back (saturated)
+    int32_t unfl0 = (int32_t)fl_uni((uint32_t)(wp0 - o.flushed));                // unflushed bytes = unfl0 + adv
+    const uint32_t bias = fl_uni(o.bias), rmask = fl_uni(o.rmask), near_max = fl_uni(o.near_max);
+    const uint32_t vp0 = (uint32_t)wp0 + bias;  // ring position of output byte wp0 (low bits)
+#ifdef FL_INF_COUNT  // tuning build only (tools/inflate_probe.py): cycles of the table lookups vs the rest
+    if (__builtin_amdgcn_readlane((int)t.nb, 0) == 0x7fffffff) return 5;  // wait for the lookups
+    FL_TACC(44);
+    const uint64_t t1_ = __builtin_readcyclecounter();
+#endif
+    fl_round_chain(t);
+    const uint32_t lsym = t.lsym, dist = t.dist, olen = t.olen;
+    const bool is_lit = t.is_lit;
+    const uint64_t m_lit = t.m_lit, m_match = t.m_match, m_plain = t.m_plain;
+    uint64_t S = t.S;
+    uint32_t consumed = t.consumed;
+    int rc = t.rc;
     // ---- (3) where every token's bytes go; the first token that does not fit or reaches too far back ends the round ----
     const uint32_t mylen = FL_INV(S) ? olen : 0u;
     const uint32_t incl = fl_wave_incl_scan_dpp(mylen);
@@ -952,8 +998,10 @@ __device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_w
 // after the block header; longer ones (and invalid ones) take the canonical walk, which also
 // keeps the reference's order of errors: a miss in the table of the decoder is InvalidCode
 // before the bits are consumed (huffman_decoder.zig:156-175), running out of input is
-// EndOfStream at the shift (bit_reader.zig:159-163).  Returns -1 at the end of the block.
-__device__ __forceinline__ int fl_inf_dynamic_symbol(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, fl_inf_out& o, uint32_t lane) {
+// EndOfStream at the shift (bit_reader.zig:159-163).  The symbol goes to the sink O (fl_sink_*).  Returns -1 at the end
+// of the block.
+template <class O>
+__device__ __forceinline__ int fl_inf_dynamic_symbol(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, O& o, uint32_t lane) {
     FL_TRY(fl_br_fill(r, 15));
     uint32_t sym, cb;
     {
@@ -970,7 +1018,7 @@ __device__ __forceinline__ int fl_inf_dynamic_symbol(fl_bitr& r, FL_LDS fl_infla
     }
     FL_TRY(fl_br_shift(r, cb));
     if (sym < 256) {
-        FL_TRY(fl_inf_literal(o, sym, lane));
+        FL_TRY(fl_sink_literal(o, sym, lane));
     } else if (sym == 256) {
         return -1;
     } else {
@@ -990,7 +1038,7 @@ __device__ __forceinline__ int fl_inf_dynamic_symbol(fl_bitr& r, FL_LDS fl_infla
         }
         FL_TRY(fl_br_shift(r, cb));
         FL_TRY(fl_inf_distance(r, dsym, distance));
-        FL_TRY(fl_inf_match(o, length, distance, lane));
+        FL_TRY(fl_sink_match(o, length, distance, lane));
     }
     return 0;
 }
@@ -1253,39 +1301,6 @@ __device__ __forceinline__ bool fl_rs_byte(fl_bitr& r, uint32_t& v) {
     return true;
 }
 
-// inflate.zig:104-121 for ONE symbol (fl_inf_fixed's loop body); -1 at the end of the block
-__device__ __forceinline__ int fl_rs_fixed_symbol(fl_bitr& r, fl_inf_out& o, uint32_t lane) {
-    FL_TRY(fl_br_fill(r, 9));
-    const uint32_t code7 = fl_rev_bits(fl_br_peek(r, 7), 7);
-    FL_TRY(fl_br_shift(r, 7));
-    uint32_t code;
-    if (code7 <= 0x17) {
-        code = code7 + 256;
-    } else if (code7 <= 0x5f) {
-        const uint32_t e = fl_br_peek(r, 1);
-        FL_TRY(fl_br_shift(r, 1));
-        code = (code7 << 1) + e - 0x30;
-    } else if (code7 <= 0x63) {
-        const uint32_t e = fl_br_peek(r, 1);
-        FL_TRY(fl_br_shift(r, 1));
-        code = ((code7 - 0x60) << 1) + e + 280;
-    } else {
-        const uint32_t e = fl_rev_bits(fl_br_peek(r, 2), 2);
-        FL_TRY(fl_br_shift(r, 2));
-        code = ((code7 - 0x64) << 2) + e + 144;
-    }
-    if (code <= 255) return fl_inf_literal(o, code, lane);
-    if (code == 256) return -1;
-    if (code > 285) return 7;
-    FL_TRY(fl_br_fill(r, 5 + 5 + 13));
-    uint32_t length, distance;
-    FL_TRY(fl_inf_length(r, code - 257, length));
-    const uint32_t dcode = fl_rev_bits(fl_br_peek(r, 5), 5);
-    FL_TRY(fl_br_shift(r, 5));
-    FL_TRY(fl_inf_distance(r, dcode, distance));
-    return fl_inf_match(o, length, distance, lane);
-}
-
 // the decoders of the current dynamic block again, from the code lengths the header left (tables are not saved)
 __device__ __forceinline__ void fl_rs_rebuild(FL_LDS fl_inflate_ws16* ws, const fl_rs_state* S, uint32_t lane) {
     fl_wave_lds_sync();
@@ -1420,19 +1435,7 @@ __device__ __forceinline__ int fl_rs_run(fl_bitr& r, FL_LDS fl_inflate_ws16* ws,
                         if (avail == 0) FL_RS_SHORT();
                         return FL_RS_STOP_OUT;
                     }
-                    const uint32_t src_off = (uint32_t)fl_br_consumed(r);
-                    const uint8_t* src = r.data + src_off;
-                    fl_inf_flush(o, o.wp, lane);
-                    for (uint32_t i = lane; i < n; i += 64) o.out[o.wp + i] = src[i];
-                    const uint32_t tail = n < o.rmask + 1 ? n : o.rmask + 1;
-                    fl_lds_order();
-                    for (uint32_t i = lane; i < tail; i += 64)
-                        o.ring[((uint32_t)(o.wp + n - tail + i) + o.bias) & o.rmask] = src[n - tail + i];
-                    fl_lds_order();
-                    o.wp += n;
-                    o.flushed = o.wp;
-                    r.left -= (int64_t)n * 8;
-                    fl_br_seek(r, src_off + n);
+                    fl_inf_stored_copy(r, o, n, lane);
                     s.stored_left -= n;
                     if (s.stored_left) break;
                 }
@@ -1462,7 +1465,7 @@ __device__ __forceinline__ int fl_rs_run(fl_bitr& r, FL_LDS fl_inflate_ws16* ws,
                         }
                     }
                     fl_bitr r2 = r;  // the unit is kept only if it finished with the bits staged
-                    rc = (int)fl_uni((uint32_t)(dyn ? fl_inf_dynamic_symbol(r2, ws, o, lane) : fl_rs_fixed_symbol(r2, o, lane)));
+                    rc = (int)fl_uni((uint32_t)(dyn ? fl_inf_dynamic_symbol(r2, ws, o, lane) : fl_inf_fixed_symbol(r2, o, lane)));
                     if (rc == 100) {
                         safe_left = r.left;
                         return FL_RS_STOP_OUT;

@@ -80,3 +80,28 @@ for k, d in enumerate([bytes(70000), b"a" * 300 + bytes(range(256)) * 3, rng.int
         co = zlib.compressobj(9, zlib.DEFLATED, -15, 9, strat)
         cases["zlib%d_%d" % (k, strat)] = co.compress(d) + co.flush()
 
+
+_seams = []
+
+
+def fixed_seam_stream():
+    """(raw stream, its 4 MiB of text): pieces of 96 KiB (dynamic blocks) and 200 bytes (fixed blocks) in turn, each compressed on its
+    own with the 32 KiB before it as its dictionary and ended by an empty stored block.  Whatever decodes on from a dynamic or stored
+    block start -- a span -- runs through fixed blocks whose matches reach back across the seam, into bytes before the span."""
+    if not _seams:
+        from flate_amd import synth
+        text = synth.text(synth.SEED_TEXT, 4 << 20).tobytes()
+        segs, pos = [], 0
+        while pos < len(text):
+            big = len(segs) % 2 == 0
+            piece = text[pos:pos + (96 * 1024 if big else 200)]
+            co = zlib.compressobj(6, zlib.DEFLATED, -15, 9, zlib.Z_DEFAULT_STRATEGY if big else zlib.Z_FIXED,
+                                  zdict=text[max(0, pos - 32768):pos])
+            pos += len(piece)
+            segs.append(co.compress(piece) + co.flush(zlib.Z_FINISH if pos == len(text) else zlib.Z_SYNC_FLUSH))
+        assert len(segs) == 85 and all((s[0] >> 1) & 3 == 1 for s in segs[1::2])  # every small piece starts with BTYPE 01
+        stream = b"".join(segs)
+        assert len(stream) == 1623270 and zlib.decompress(stream, -15) == text
+        _seams.append((stream, text))
+    return _seams[0]
+

@@ -9,6 +9,7 @@ import zlib as pyzlib
 import numpy as np
 import pytest
 
+import _inflate_edge_cases as E
 import _oracle as O
 from gpu_util import engine
 from test_gpu_inflate import _long_streams, _mutants
@@ -82,8 +83,9 @@ def test_long_streams_of_every_kind_with_a_low_bound(monkeypatch):
     monkeypatch.setenv("FLATE_HIP_INFLATE_SPANS", "20000")
     eng = engine()
     cases = _long_streams()
+    seams, seam_text = E.fixed_seam_stream()  # spans that run through fixed blocks whose matches reach before the span
     for container in (0, 1, 2):
-        grp = [c for c in cases if c[1] == container]
+        grp = [c for c in cases + [("fixed-seams", 0, seam_text, seams)] if c[1] == container]
         outs, st, used = eng.decompress_many([c[3] for c in grp], container, caps=[len(c[2]) + 8 for c in grp])
         for c, o, s_, u in zip(grp, outs, st, used):
             assert s_ == 0 and o == c[2] and u == len(c[3]), (c[0], container, s_, len(o), u)

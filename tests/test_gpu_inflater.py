@@ -112,6 +112,7 @@ def test_synth_long_streams_in_random_pieces(flags):
     items = [(n,) + S.CASES[n] + (S.INFO[n]["q6"],) for n in S.LARGE + ["tiny_blocks_60"] for _ in range(8)]
     items += [("seed %d" % (6000 + k), s, want, q6) for k, ((s, want), (q6, _)) in
               enumerate(zip(S.random_streams(6000, 100, info), info))]
+    items.append(("fixed seams",) + E.fixed_seam_stream() + (False,))
     outs, st, used = feed_random_pieces(eng, [it[1] for it in items], random.Random(11 + flags), flags=flags)
     n_q6 = 0
     for (name, stream, want, q6), o, s_, u in zip(items, outs, st, used):

@@ -194,7 +194,9 @@ def test_long_streams_are_cut_into_spans(monkeypatch):
     batch = cut + [whole, a, b]
     want = ([len(text)] * 3 + [2 << 20, None, 4], [0, 0, 0, 0, 11, 0], [len(s) for s in batch])
     monkeypatch.setenv("FLATE_HIP_INFLATE_SPANS", "32768")
-    for s in cut:
+    seams, seam_text = E.fixed_seam_stream()  # spans that run through fixed blocks whose matches reach before the span
+    assert seam_text == text
+    for s in cut + [seams]:
         assert eng.decompressed_sizes([s], O.RAW) == ([len(text)], [0], [len(s)])
         assert eng.size_paths() == (1, 0)
     assert eng.decompressed_sizes([whole], O.RAW) == ([2 << 20], [0], [len(whole)])
@@ -211,6 +213,8 @@ def test_long_streams_are_cut_into_spans(monkeypatch):
     monkeypatch.setenv("FLATE_HIP_INFLATE_SPANS", "0")
     same = eng.decompressed_sizes(batch, O.RAW)
     assert eng.size_paths() == (0, len(batch))
+    assert eng.decompressed_sizes([seams], O.RAW) == ([len(text)], [0], [len(seams)])
+    assert eng.size_paths() == (0, 1)
     for r in (got, same):
         assert r[1] == want[1]
         assert [z for z, s_ in zip(r[0], r[1]) if s_ == 0] == [z for z in want[0] if z is not None]
