@@ -122,6 +122,19 @@ FL_HD uint32_t fl_dist_code(uint32_t d) {
     return (hb << 1) + ((d >> (hb - 1)) & 1);
 }
 
+// fl_dist_code(d) + 256 for d = distance - 1 in 0..32767, from the exponent and the top mantissa bit of (float)(2 d + 1)
+// (exact: 2 d + 1 < 2^24): four instructions on the GPU where fl_dist_code's clz form with its d < 4 case takes eight; what
+// the two instruction-bound kernels (k_lz_emit, k_encode_wave) use.  2 d + 1 has its highest bit one place above d's and
+// d's next bit below it, so the float's bits >> 22 are 254 + 2 (hb + 1) + next = 256 + the code for every d >= 1; d = 0
+// gives 254 and is lifted to 256.  tests/test_dist_code_cpu.py compares it with fl_dist_code for all 32768 distances.
+FL_HD uint32_t fl_dist_code_p256(uint32_t d) {
+    const float x = (float)((d << 1) | 1u);
+    uint32_t f;
+    __builtin_memcpy(&f, &x, 4);
+    f >>= 22;
+    return f < 256u ? 256u : f;
+}
+
 FL_HD uint16_t fl_bit_reverse(uint16_t v, uint32_t n) {  // huffman_encoder.zig:455-458
     uint32_t x = v;
     x = ((x & 0x5555u) << 1) | ((x >> 1) & 0x5555u);

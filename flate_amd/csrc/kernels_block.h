@@ -815,6 +815,19 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode(const uint8_t* __r
 // first pass over the tokens to find out where each wave's bits start -- half the instructions.  A wave's chain is
 // four times as long, four times as many blocks are in flight.  Token blocks only: huffman-only batches never had
 // a launch site for it (enqueue_back_end, the deflater's feed), so the kernel holds no byte-item path.
+//
+// The kernel is bound by vector instruction issue, so what a token costs is counted in instructions:
+//  - the wave builds the block's tables in LDS once: `tab`, by bits 15..23 of a token (a literal's byte, or 256 + a
+//    match's length - 3), holds the finished bits of that half of the item -- Huffman code, the length's extra bits above
+//    it, the bit count in the top byte (at most 15 + 5 bits) -- and `dtab`, by distance code, holds the code with its
+//    length and the code's base with its number of extra bits, read together.  A token is one load, a match two;
+//  - a lane carries TWO tokens into a round of the packer (128 a group): the prefix sum, the write-out, the clearing
+//    and the carry of the staging window are paid once for both.
+#define FL_ENCW_GROUP 128u
+struct __attribute__((packed, aligned(4))) fl_tok2 {  // a lane's two tokens (a token buffer is 4-byte aligned, no more)
+    uint32_t a, b;
+};
+#define FL_ENCW_STG_DW 200  // (128 items of 48 bits at most = 192 dwords, the carried dword, two a shifted item spills into)
 __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t* __restrict__ in,
                                                               const fl_chunk* __restrict__ chunks,
                                                               const uint32_t* __restrict__ blk_chunk,
@@ -822,11 +835,12 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t
                                                               const uint32_t* __restrict__ tokens /* [chunk][65536] */,
                                                               uint32_t* __restrict__ out32, uint32_t n_blocks,
                                                               uint32_t pair_slots) {
-    __shared__ uint32_t lit_all[FL_ENC_WAVES][FL_NUM_LIT + 2];
-    __shared__ uint32_t dist_all[FL_ENC_WAVES][FL_NUM_DIST + 2];
-    __shared__ uint32_t stg[FL_ENC_WAVES][FL_STG_DW];
+    __shared__ uint32_t tab_all[FL_ENC_WAVES][512];
+    __shared__ uint2 dtab_all[FL_ENC_WAVES][32];
+    __shared__ uint32_t stg[FL_ENC_WAVES][FL_ENCW_STG_DW];
 
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));  // (the block and its plan: in scalar registers)
     uint32_t b = blockIdx.x * FL_ENC_WAVES + wave;
     if (b >= n_blocks) return;  // (no workgroup barrier below: every wave is on its own)
     if (pair_slots) {
@@ -839,8 +853,8 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t
     if (!plan->valid) return;
     const uint32_t cidx = blk_chunk[b];
     const fl_chunk ck = chunks[cidx];
-    uint32_t* lit_lds = lit_all[wave];
-    uint32_t* dist_lds = dist_all[wave];
+    uint32_t* tab = tab_all[wave];
+    uint2* dtab = dtab_all[wave];
     const uint64_t bit_off = plan->bit_off;
     const uint8_t* src = in + ck.in_off;
 
@@ -857,10 +871,20 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t
         return;
     }
 
-    for (uint32_t i = lane; i < FL_NUM_LIT; i += 64)
-        lit_lds[i] = (uint32_t)plan->lit[i].code | ((uint32_t)plan->lit[i].len << 16);
-    if (lane < FL_NUM_DIST) dist_lds[lane] = (uint32_t)plan->dist[lane].code | ((uint32_t)plan->dist[lane].len << 16);
-    for (uint32_t i = lane; i < FL_STG_DW; i += 64) stg[wave][i] = 0;
+    // the tables: value in bits 0..23, bit count in bits 24..31
+#pragma unroll
+    for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t i = 64 * u + lane;  // a literal's byte; a match's length - 3
+        const fl_hcode lc = plan->lit[i];
+        tab[i] = (uint32_t)lc.code | ((uint32_t)lc.len << 24);
+        const uint32_t li = fl_len_index(i);
+        const fl_hcode mc = plan->lit[257 + li];
+        tab[256 + i] = ((uint32_t)mc.code | ((i - fl_len_base_scaled(li)) << mc.len)) | (((uint32_t)mc.len + fl_len_extra_bits(li)) << 24);
+    }
+    if (lane < FL_NUM_DIST)
+        dtab[lane] = make_uint2((uint32_t)plan->dist[lane].code | ((uint32_t)plan->dist[lane].len << 16),
+                                fl_dist_base_scaled(lane) | (fl_dist_extra_bits(lane) << 16));
+    for (uint32_t i = lane; i < FL_ENCW_STG_DW; i += 64) stg[wave][i] = 0;
     fl_lds_order();
 
     const uint32_t hdr_nbits = plan->hdr_nbits;
@@ -871,42 +895,59 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t
 
     uint64_t cur = bit_off;
 
-    // pack 64 items (one a lane, it.n = 0: none) behind `cur`: prefix sum of the lengths, ds_or into the staging window, whole
-    // dwords out; the block's first dword is shared with the block before it (an atomic OR into the cleared output)
+    // pack 128 items (two a lane, the lane's first one first; n = 0: none) behind `cur`: prefix sum of the lanes' lengths,
+    // ds_or into the staging window, whole dwords out; the block's first dword is shared with the block before it (an
+    // atomic OR into the cleared output)
     const uint64_t first_dw = cur >> 5;
     uint32_t* sw = stg[wave];
-    auto pack = [&](const fl_item& it) {
-        const uint32_t incl = fl_wave_incl_scan(it.n, lane);
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        const uint64_t base_dw = cur >> 5;
-        if (it.n) {
-            const uint32_t rel = (uint32_t)(cur - (base_dw << 5)) + (incl - it.n);
+    // an item of at most 48 bits at bit `rel` of the window: three dwords at most
+    auto or_item = [&](const uint32_t rel, const uint64_t v, const uint32_t n) {
+        if (n) {
             const uint32_t dw = rel >> 5, sh = rel & 31;
-            const uint64_t a = it.v << sh;
-            const uint32_t hi = sh ? (uint32_t)(it.v >> (64 - sh)) : 0u;
+            const uint64_t a = v << sh;
+            const uint32_t hi = (uint32_t)(((uint64_t)(uint32_t)(v >> 32) << sh) >> 32);  // (bits 64.. of the shifted item)
             if ((uint32_t)a) atomicOr(&sw[dw], (uint32_t)a);
             if ((uint32_t)(a >> 32)) atomicOr(&sw[dw + 1], (uint32_t)(a >> 32));
             if (hi) atomicOr(&sw[dw + 2], hi);
         }
+    };
+    auto pack = [&](const uint64_t va, const uint32_t na, const uint64_t vb, const uint32_t nb) {
+        const uint32_t nn = na + nb;
+        const uint32_t incl = fl_wave_incl_scan(nn, lane);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint64_t base_dw = cur >> 5;
+        const uint32_t rel = ((uint32_t)cur & 31u) + (incl - nn);
+        or_item(rel, va, na);
+        or_item(rel + na, vb, nb);
         fl_lds_order();
         const uint64_t end = cur + total;
-        const uint32_t nd = (uint32_t)((end >> 5) - base_dw);  // complete dwords (at most 120: two rounds of the lanes)
+        const uint32_t nd = (uint32_t)((end >> 5) - base_dw);  // complete dwords (at most 192: three rounds of the lanes)
+        uint32_t* o = out32 + base_dw;
         {
-            const uint32_t v0 = lane < nd ? sw[lane] : 0u, v1 = lane + 64u < nd ? sw[lane + 64u] : 0u;
-            if (lane < nd) {
-                if (base_dw + lane == first_dw) {
-                    if (v0) atomicOr(&out32[base_dw + lane], v0);
-                } else {
-                    out32[base_dw + lane] = v0;
+            const uint32_t v0 = lane < nd ? sw[lane] : 0u;
+            if (base_dw == first_dw) {  // (the block's first group)
+                if (lane == 0) {
+                    if (nd && v0) atomicOr(&o[0], v0);
+                } else if (lane < nd) {
+                    fl_st32_off(o, 4u * lane, v0);
                 }
+            } else if (lane < nd) {
+                fl_st32_off(o, 4u * lane, v0);
             }
-            if (lane + 64u < nd) out32[base_dw + lane + 64u] = v1;  // (never the block's first dword)
+            if (nd > 64u) {  // (never the block's first dword)
+                const uint32_t v1 = lane + 64u < nd ? sw[lane + 64u] : 0u, v2 = lane + 128u < nd ? sw[lane + 128u] : 0u;
+                if (lane + 64u < nd) fl_st32_off(o, 4u * (lane + 64u), v1);
+                if (lane + 128u < nd) fl_st32_off(o, 4u * (lane + 128u), v2);
+            }
         }
         const uint32_t carry = sw[nd];
         fl_lds_order();
         // clear the window, keep the partial dword as the new first one
         if (lane <= nd + 2) sw[lane] = lane == 0 ? carry : 0u;
-        if (lane + 64u <= nd + 2 && lane + 64u < FL_STG_DW) sw[lane + 64u] = 0u;
+        if (nd + 2 >= 64u) {
+            if (lane + 64u <= nd + 2) sw[lane + 64u] = 0u;
+            if (lane + 128u <= nd + 2 && lane + 128u < FL_ENCW_STG_DW) sw[lane + 128u] = 0u;
+        }
         fl_lds_order();
         cur = end;
     };
@@ -914,60 +955,74 @@ __global__ __launch_bounds__(64 * FL_ENC_WAVES) void k_encode_wave(const uint8_t
     // tokens' loop carries no branch for the other two, and a group's tokens are requested while the group before is packed
     // (the load sat in the loop with its own wait: 1.08 -> see profiles/r06_config2_kernel_stats.csv).
     for (uint32_t ib = 0; ib < n_hdr; ib += 64) {
-        fl_item it;
-        it.v = 0;
-        it.n = 0;
+        uint32_t v = 0, n = 0;
         const uint32_t i = ib + lane;
         if (i < n_hdr) {
             const uint32_t rem = hdr_nbits - 8 * i;
-            it.n = rem < 8 ? rem : 8;
-            it.v = hdr[i] & ((1u << it.n) - 1);
+            n = rem < 8 ? rem : 8;
+            v = hdr[i] & ((1u << n) - 1);
         }
-        pack(it);
+        pack(v, n, 0, 0);
     }
-    const uint32_t eob = lit_lds[FL_EOB];
-    uint32_t t_next = lane < n_sym ? toks[lane] : 0u;
-    for (uint32_t k0 = 0; k0 < n_sym; k0 += 64) {
-        const uint32_t t = t_next;
-        t_next = k0 + 64 + lane < n_sym ? toks[k0 + 64 + lane] : 0u;
-        fl_item it;
-        it.v = 0;
-        it.n = 0;
-        const uint32_t k = k0 + lane;
+    const fl_hcode eobc = plan->lit[FL_EOB];
+    // the bits of a token
+    auto token_bits = [&](const uint32_t t, uint64_t& v, uint32_t& n) {
+        const uint32_t e = tab[(t >> 15) & 0x1ffu];
+        v = e & 0xffffffu;
+        n = e >> 24;
+        if (FL_TOK_IS_MATCH(t)) {
+            const uint32_t d = FL_TOK_DIST0(t);
+            const uint2 de = dtab[fl_dist_code_p256(d) - 256u];
+            const uint32_t dl = de.x >> 16;
+            const uint32_t dv = (de.x & 0xffffu) | ((d - (de.y & 0xffffu)) << dl);  // (15 + 13 bits at most)
+            v |= (uint64_t)dv << n;
+            n += dl + (de.y >> 16);
+        }
+    };
+    // ... of slot k of the block's last group (k = n_sym: the end-of-block code, which rides there when a slot is free;
+    // beyond: nothing)
+    auto slot_bits = [&](const uint32_t t, const uint32_t k, uint64_t& v, uint32_t& n) {
+        v = 0;
+        n = 0;
         if (k < n_sym) {
-            if (!FL_TOK_IS_MATCH(t)) {
-                const uint32_t e = lit_lds[FL_TOK_LENLIT(t)];
-                it.v = e & 0xffff;
-                it.n = e >> 16;
-            } else {
-                const uint32_t ll = FL_TOK_LENLIT(t);
-                const uint32_t li = fl_len_index(ll);
-                const uint32_t le = lit_lds[257 + li];
-                uint64_t v = le & 0xffff;
-                uint32_t n = le >> 16;
-                v |= (uint64_t)(ll - fl_len_base_scaled(li)) << n;
-                n += fl_len_extra_bits(li);
-                const uint32_t d = FL_TOK_DIST0(t);
-                const uint32_t dc = fl_dist_code(d);
-                const uint32_t de = dist_lds[dc];
-                v |= (uint64_t)(de & 0xffff) << n;
-                n += de >> 16;
-                v |= (uint64_t)(d - fl_dist_base_scaled(dc)) << n;
-                n += fl_dist_extra_bits(dc);
-                it.v = v;
-                it.n = n;
-            }
-        } else if (k == n_sym) {  // the end-of-block code rides in the last group when a lane is free
-            it.v = eob & 0xffff;
-            it.n = eob >> 16;
+            token_bits(t, v, n);
+        } else if (k == n_sym) {
+            v = eobc.code;
+            n = eobc.len;
         }
-        pack(it);
+    };
+    // (a lane's two tokens: one 8-byte load where both exist)
+    auto load2 = [&](const uint32_t k) {
+        fl_tok2 r;
+        r.a = r.b = 0;
+        if (k + 1 < n_sym)
+            r = *(const fl_tok2*)((const char*)toks + 4u * k);
+        else if (k < n_sym)
+            r.a = *(const uint32_t*)((const char*)toks + 4u * k);
+        return r;
+    };
+    fl_tok2 t_next = load2(2 * lane);
+    uint32_t k0 = 0;
+    // (whole groups ask no slot whether it holds a token)
+    for (; k0 + FL_ENCW_GROUP <= n_sym; k0 += FL_ENCW_GROUP) {
+        const fl_tok2 t = t_next;
+        t_next = load2(k0 + FL_ENCW_GROUP + 2 * lane);
+        uint64_t va, vb;
+        uint32_t na, nb;
+        token_bits(t.a, va, na);
+        token_bits(t.b, vb, nb);
+        pack(va, na, vb, nb);
     }
-    if ((n_sym & 63u) == 0) {  // every lane of the last group held a token (or there was none): a group of its own
-        fl_item it;
-        it.v = lane == 0 ? (eob & 0xffff) : 0u;
-        it.n = lane == 0 ? (eob >> 16) : 0u;
-        pack(it);
+    if (k0 < n_sym) {
+        const uint32_t k = k0 + 2 * lane;
+        uint64_t va, vb;
+        uint32_t na, nb;
+        slot_bits(t_next.a, k, va, na);
+        slot_bits(t_next.b, k + 1, vb, nb);
+        pack(va, na, vb, nb);
+    }
+    if ((n_sym & (FL_ENCW_GROUP - 1u)) == 0) {  // every slot of the last group held a token (or there was none): a group of its own
+        pack(lane == 0 ? (uint64_t)eobc.code : 0u, lane == 0 ? (uint32_t)eobc.len : 0u, 0, 0);
     }
     if ((cur & 31) && lane == 0) {
         const uint32_t v = sw[0];

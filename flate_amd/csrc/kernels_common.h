@@ -66,6 +66,15 @@ __device__ __forceinline__ void fl_lds_order() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// A dword at a wave-uniform base plus a 32-bit byte offset of the lane: the sum is formed in the load or store itself
+// (scalar base, 32-bit vector offset), not with 64-bit vector arithmetic.  Callers keep `byte_off` below 4 GiB.
+__device__ __forceinline__ uint32_t fl_ld32_off(const uint32_t* __restrict__ base, uint32_t byte_off) {
+    return *(const uint32_t*)((const char*)base + byte_off);
+}
+__device__ __forceinline__ void fl_st32_off(uint32_t* __restrict__ base, uint32_t byte_off, uint32_t v) {
+    *(uint32_t*)((char*)base + byte_off) = v;
+}
+
 // little-endian 32-bit load from an arbitrarily aligned global address
 // (the aligned address is derived with pointer arithmetic, not an integer round trip, so the
 // compiler keeps the global address space and emits global_load rather than flat_load)

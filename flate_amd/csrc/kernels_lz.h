@@ -975,5 +975,4 @@ __device__ __forceinline__ uint32_t fl_win_byte(const uint32_t* win32, uint32_t 
 #define FL_TOK_SPAN (FL_TOK_PART / 16u)  // positions per wave per part
 #define FL_TOK_R (FL_TOK_SPAN / 64u)     // positions per lane per part
 #define FL_TOK_LOOK 256u                 // literals of an anchor may reach this far past its part (j < 256)
-#define FL_TOK_WIN_DW ((FL_TOK_PART + FL_TOK_LOOK) / 4u + 2u)
 

@@ -1577,14 +1577,18 @@ __global__ __launch_bounds__(FL_EMITZ_THREADS, 8) void k_lz_emit(const uint8_t* 
                                                                  uint32_t* __restrict__ hist_all,
                                                                  fl_block_plan* __restrict__ plans,
                                                                  uint32_t* __restrict__ ntok_all) {
-    __shared__ uint32_t winp[FL_TOK_WIN_DW];
+    constexpr uint32_t WIN_GRAN = (FL_TOK_PART + FL_TOK_LOOK + 15u + 15u) / 16u;  // granules of a part at the worst alignment
+    static_assert(WIN_GRAN <= FL_EMITZ_THREADS, "one granule a thread");
+    __shared__ uint4 win16[WIN_GRAN];
     __shared__ uint32_t hist[2][320];
     __shared__ uint32_t wtot[16];
     __shared__ uint16_t alist[16][FL_TOK_SPAN];  // per wave: the positions (in its span) of the span's anchors, ascending
     __shared__ uint32_t v1_sh, e1_sh;  // where the reference's window stands when token 32768 is added; where that token's bytes end
+    __shared__ uint8_t lent[256];      // fl_len_index of every length - 3
     const uint32_t c = blockIdx.x;
     const fl_chunk ck = chunks[c];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));  // (in scalar registers, and what hangs on it)
     fl_block_plan* plan0 = &plans[ck.first_block];
     fl_block_plan* plan1 = &plans[ck.first_block + 1];
     if (ck.skip) {
@@ -1600,8 +1604,11 @@ __global__ __launch_bounds__(FL_EMITZ_THREADS, 8) void k_lz_emit(const uint8_t* 
     const uint32_t* descg = desc_all + ck.pos_off;
     const uint32_t* trueg = true_all + (ck.pos_off >> 5);
     uint32_t* tokens = tokens_all + ck.pos_off;
+    const uint8_t* winb = (const uint8_t*)win16;  // (the staged bytes one at a time: a byte load, no shift and mask)
+    uint16_t* al = alist[wave];
 
     for (uint32_t i = tid; i < 640; i += FL_EMITZ_THREADS) (&hist[0][0])[i] = 0;
+    if (tid < 256) lent[tid] = (uint8_t)fl_len_index(tid);  // (read behind the first part's barrier)
     if (tid == 0) v1_sh = e1_sh = N;
     uint32_t run0 = 0;  // tokens of the parts before this one (same value in every thread)
     uint32_t tw_next = 0;  // the wave's 16 words of anchor bits of the next part
@@ -1625,37 +1632,36 @@ __global__ __launch_bounds__(FL_EMITZ_THREADS, 8) void k_lz_emit(const uint8_t* 
             // (the anchors below this lane: two v_mbcnt; the lane's own bit: the mask itself as the predicate -- the kernel is bound
             // by instruction issue, the shifts and masks of a 64-bit `below` were a third of this loop)
             const uint32_t below = __builtin_amdgcn_mbcnt_hi(whi, __builtin_amdgcn_mbcnt_lo(wlo, 0u));
-            if (__builtin_amdgcn_inverse_ballot_w64(m64)) alist[wave][na + below] = (uint16_t)(r * 64 + lane);
+            if (__builtin_amdgcn_inverse_ballot_w64(m64)) al[na + below] = (uint16_t)(r * 64 + lane);
             na += (uint32_t)__popcll(m64);
         }
         fl_lds_order();
+        // The part's bytes (+ lookahead for the literals of its last anchors) as the aligned 16-byte granules that hold them, a
+        // granule a thread: the literals are read a byte at a time, so the window need not start at the part's first byte --
+        // it starts `wsh` bytes before it, and nothing is shifted.  (A granule is loaded when it holds a byte of the chunk;
+        // what else it holds is never read: a literal is a byte of the input.)
+        const uint32_t wsh = (uint32_t)((uintptr_t)(src + h0) & 15u);
+        const uint32_t ngran = (min(N - h0, FL_TOK_PART + FL_TOK_LOOK) + wsh + 15u) >> 4;
+        uint4 wg = make_uint4(0, 0, 0, 0);
+        if (tid < ngran) wg = *(const uint4*)(src + h0 - wsh + (tid << 4));
         // d[k]: descriptor of anchor number 64 k + lane (0 = none): PZ_DESC_LIT = one literal, else j literals and a match
+        // (the span's descriptors behind one uniform base, a 32-bit offset a lane)
+        const uint32_t* dspan = descg + span0;
         uint32_t d[FL_TOK_R];
 #pragma unroll
         for (int k = 0; k < (int)FL_TOK_R; k++) {
             const uint32_t j = 64 * k + lane;
-            d[k] = j < na ? descg[span0 + alist[wave][j]] : 0u;
+            d[k] = j < na ? fl_ld32_off(dspan, 4u * al[j]) : 0u;
         }
-        // the part's bytes (+ lookahead for the literals of its last anchors), zero padded
-        {
-            const uint32_t nb = min(N - h0, FL_TOK_PART + FL_TOK_LOOK);
-            // (all of a thread's loads first, then the stores: one round of memory latency, not three)
-            constexpr uint32_t WR = (FL_TOK_WIN_DW + FL_EMITZ_THREADS - 1) / FL_EMITZ_THREADS;
-            uint32_t wv[WR];
-#pragma unroll
-            for (uint32_t u = 0; u < WR; u++) {
-                const uint32_t i = u * FL_EMITZ_THREADS + tid;
-                wv[u] = 4 * i < nb ? fl_load_u32_clamped(src + h0, 4 * i, nb) : 0u;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < WR; u++) {
-                const uint32_t i = u * FL_EMITZ_THREADS + tid;
-                if (i < FL_TOK_WIN_DW) winp[i] = wv[u];
-            }
-        }
+        if (tid < ngran) win16[tid] = wg;
+        // tokens of a descriptor: its literals and the match; PZ_DESC_LIT (bit 30, which a match of 128 literals or more would
+        // share with it: such a descriptor is read as PZ_DESC_LIT here and in the rounds alike) is one literal
         uint32_t cnt = 0;
 #pragma unroll
-        for (int r = 0; r < (int)FL_TOK_R; r++) cnt += d[r] ? ((d[r] & PZ_DESC_LIT) ? 1u : ((d[r] >> 23) & 0xff) + 1u) : 0u;
+        for (int r = 0; r < (int)FL_TOK_R; r++) {
+            const uint32_t dm = (d[r] & PZ_DESC_LIT) ? 0u : d[r];
+            cnt += (d[r] != 0 ? 1u : 0u) + ((dm >> 23) & 0xffu);
+        }
         cnt = fl_wave_sum(cnt);
         if (lane == 0) wtot[wave] = cnt;
         __syncthreads();
@@ -1664,43 +1670,67 @@ __global__ __launch_bounds__(FL_EMITZ_THREADS, 8) void k_lz_emit(const uint8_t* 
             if (w < wave) run += wtot[w];
             run0 += wtot[w];
         }
-#pragma unroll 1  // (rolled: the descriptors rotate through d[0])
-        for (uint32_t k0 = 0; k0 < na; k0 += 64) {
-            const uint32_t j = k0 + lane;
-            const uint32_t d0r = d[0];
-#pragma unroll
-            for (int k = 0; k + 1 < (int)FL_TOK_R; k++) d[k] = d[k + 1];
-            d[FL_TOK_R - 1] = d0r;
-            const bool mk = d0r != 0;  // (= j < na: every anchor has a descriptor)
-            const uint32_t p = span0 + (mk ? (uint32_t)alist[wave][j] : 0u);
-            const uint32_t q = p - h0;
-            const uint32_t dd = (d0r & PZ_DESC_LIT) ? 0u : d0r;
-            const uint32_t nl = mk ? (dd ? ((dd >> 23) & 0xff) : 1u) : 0u;  // literals of this anchor
-            const uint32_t nt = mk ? (dd ? nl + 1 : 1u) : 0u;
-            const uint32_t incl = fl_wave_incl_scan_dpp(nt);
-            uint32_t idx = run + incl - nt;
-            run += __builtin_amdgcn_readlane(incl, 63);
-            for (uint32_t x = 0; x < nl; x++) {
-                const uint32_t byte = fl_win_byte(winp, q + x);
-                tokens[idx] = FL_TOK_LIT(byte);
-                atomicAdd(&hist[idx >> 15][byte], 1u);
-                if (idx == FL_MAX_TOKENS - 1) v1_sh = e1_sh = p + x + 1;  // emitted at the visit of the next position
-                idx++;
-            }
-            if (mk && dd) {
-                const uint32_t ll = (dd >> 15) & 0xff, d0 = dd & 0x7fff;
-                tokens[idx] = (1u << 23) | (ll << 15) | d0;
-                atomicAdd(&hist[idx >> 15][257 + fl_len_index(ll)], 1u);
-                atomicAdd(&hist[idx >> 15][286 + fl_dist_code(d0)], 1u);
-                // a match of at least `lazy` goes out at its own visit, a shorter one at the next
-                // (deflate.zig:171-173 vs 182-184); rp at that moment decides the Q1 input slice
-                if (idx == FL_MAX_TOKENS - 1) {
-                    v1_sh = p + nl + ((ll + 3 >= prm.lazy) ? 0 : 1);
-                    e1_sh = p + nl + ll + 3;  // (Q1: the window has not advanced over the match yet, deflate.zig:193)
+        run = (uint32_t)__builtin_amdgcn_readfirstlane((int)run);
+        // One round: the tokens of anchors k0 .. k0 + 63 of the span.  CUT: token 32768 of the chunk is among them (run <= 32767
+        // < run1) -- only that round asks every token whether it is the one and which block's histogram it counts in; for every
+        // other round both are settled once for the wave.
+        auto emit_round = [&](const uint32_t dk, const uint32_t k0) {
+            const bool mk = dk != 0;  // (= k0 + lane < na: every anchor has a descriptor)
+            const uint32_t p = span0 + (mk ? (uint32_t)al[k0 + lane] : 0u);
+            const uint32_t q = p - h0 + wsh;  // (the byte at p in the window)
+            const bool one = (dk & PZ_DESC_LIT) != 0;
+            const uint32_t dd = one ? 0u : dk;
+            const uint32_t jl = (dd >> 23) & 0xffu;
+            const uint32_t nl = one ? 1u : jl;  // literals of this anchor
+            const uint32_t nt = (mk ? 1u : 0u) + jl;
+            uint32_t incl = fl_wave_incl_scan_dpp(nt);
+            asm("" : "+v"(incl));  // (opaque: taken apart into the scan's six partial sums for idx0, the scan is three instructions a step, not one)
+            const uint32_t idx0 = run + incl - nt;
+            const uint32_t run1 = run + (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            auto body = [&](auto cut_t) {
+                constexpr bool CUT = decltype(cut_t)::value;
+                uint32_t idx = idx0;
+                uint32_t* hs = hist[CUT ? 0u : (run >> 15)];
+                auto literal = [&](const uint32_t x) {
+                    const uint32_t byte = winb[q + x];
+                    fl_st32_off(tokens, 4u * idx, FL_TOK_LIT(byte));
+                    atomicAdd(CUT ? &hist[idx >> 15][byte] : &hs[byte], 1u);
+                    if (CUT && idx == FL_MAX_TOKENS - 1) v1_sh = e1_sh = p + x + 1;  // emitted at the visit of the next position
+                    idx++;
+                };
+                // (text: an anchor has one literal at most, nearly always -- no loop then)
+                if (__builtin_amdgcn_ballot_w64(nl > 1u) == 0) {
+                    if (nl) literal(0u);
+                } else {
+                    for (uint32_t x = 0; x < nl; x++) literal(x);
                 }
-            }
+                if (dd) {
+                    const uint32_t ll = (dd >> 15) & 0xff, d0 = dd & 0x7fff;
+                    fl_st32_off(tokens, 4u * idx, (1u << 23) | (dd & 0x7fffffu));  // = 1 << 23 | ll << 15 | d0
+                    uint32_t* hm = CUT ? hist[idx >> 15] : hs;
+                    atomicAdd(&hm[257 + lent[ll]], 1u);
+                    atomicAdd(&hm[286 - 256 + fl_dist_code_p256(d0)], 1u);
+                    // a match of at least `lazy` goes out at its own visit, a shorter one at the next
+                    // (deflate.zig:171-173 vs 182-184); rp at that moment decides the Q1 input slice
+                    if (CUT && idx == FL_MAX_TOKENS - 1) {
+                        v1_sh = p + nl + ((ll + 3 >= prm.lazy) ? 0 : 1);
+                        e1_sh = p + nl + ll + 3;  // (Q1: the window has not advanced over the match yet, deflate.zig:193)
+                    }
+                }
+            };
+            if (run < FL_MAX_TOKENS && run1 >= FL_MAX_TOKENS)
+                body(std::true_type());
+            else
+                body(std::false_type());
+            run = run1;
+        };
+        // (written out: d[k] by a constant index, no rotation of the eight registers a round)
+#pragma unroll
+        for (int k = 0; k < (int)FL_TOK_R; k++) {
+            if (64u * k >= na) break;
+            emit_round(d[k], 64u * k);
         }
-        __syncthreads();  // wtot and winp are reused by the next part
+        __syncthreads();  // wtot and win16 are reused by the next part
     }
     // block boundaries (deflate.zig:227-230, 268-288) and histograms
     const uint32_t total = run0;
