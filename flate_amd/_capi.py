@@ -37,6 +37,7 @@ SYMBOLS = [
     "flate_hip_debug_device_bytes", "flate_hip_debug_workspace_bytes",
     "flate_hip_debug_inflate_paths",
     "flate_hip_decompressed_sizes", "flate_hip_debug_size_paths",
+    "flate_hip_decompress_members", "flate_hip_debug_member_paths",
 ]
 
 
@@ -158,6 +159,11 @@ def lib():
     L.flate_hip_decompressed_sizes.restype = C.c_int
     L.flate_hip_debug_size_paths.argtypes = [vp, u64p]
     L.flate_hip_debug_size_paths.restype = C.c_int
+    L.flate_hip_decompress_members.argtypes = [vp, vp, u64p, C.c_uint32, C.c_int, C.c_int, vp, u64p, u64p, i32p, u64p, vp,
+                                               C.c_int]
+    L.flate_hip_decompress_members.restype = C.c_int
+    L.flate_hip_debug_member_paths.argtypes = [vp, u64p]
+    L.flate_hip_debug_member_paths.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.flate_hip_debug_tokens.restype = C.c_int64
     _lib = L

@@ -6,6 +6,7 @@ behaviour, over the C ABI of libflate_hip.so.
   Compressor / compressor(writer, opt)  flate.zig:33-40   (write / compress / finish; flush: see below)
   decompress(reader, writer)            flate.zig:10-12
   Decompressor / decompressor(reader)   flate.zig:15-22   (decompress / next / read / reader / reset / set_reader)
+  decompress_members(data)              -- (not in the reference: all concatenated members in one GPU call)
   huffman.{compress,Compressor,compressor}   flate.zig:44-56
   store.{compress,Compressor,compressor}     flate.zig:59-71
   Options(level=Level.default), Level   deflate.zig:15-32
@@ -580,6 +581,22 @@ class ContainerModule:
         return _PieceDecompressor(self._container, reader, engine, piece=piece)
 
     Decompressor = decompressor
+
+    def decompress_members(self, data, engine=None):
+        """Every concatenated member of `data` (bytes-like, or a reader that is read to its end) in one GPU call
+        (flate_hip_decompress_members): the bytes a caller collects who decodes member by member with decompressor() and
+        reset().  Raises the error of the first member that fails, as that loop would."""
+        eng = engine or default_engine()
+        data = _read_all(data)
+        cap = max(1 << 16, len(data) * 64)
+        while True:
+            outs, st, _, _ = eng.decompress_members([data], self._container, 0, caps=[cap])
+            if st[0] == 100 and cap < (1 << 34):
+                cap *= 8
+                continue
+            break
+        raise_for_status(st[0])
+        return outs[0]
 
 
 def compress_bytes(data, container=_capi.RAW, mode=6, engine=None):

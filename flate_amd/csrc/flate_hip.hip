@@ -26,9 +26,11 @@
 #include "kernels_inflate_par.h"
 #include "kernels_inflate_size.h"
 #include "kernels_lz.h"
+#include "kernels_members.h"
 #include "kernels_parse.h"
 #include "kernels_walk.h"
 #include "kernels_stream.h"
+#include "member_plan.h"
 #include "pass_plan.h"
 #include "size_plan.h"
 #include "stream_tables.h"
@@ -57,6 +59,11 @@ enum KernelId {
     K_INFLATE_SPAN,
     K_INFLATE_SIZE,
     K_INFLATE_SIZE_SPAN,
+    K_MEMBER_SCAN,
+    K_MEMBER_CHAIN,
+    K_MEMBER_WALK,
+    K_MEMBER_PACK,
+    K_MEMBER_FOLD,
     K_GATHER,
     K_INFLATER,
     K_DEFLATER,
@@ -67,6 +74,7 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_st_parse", "k_st_emit", "k_plan",
                                            "k_offsets",  "k_encode",    "k_inflate",  "k_inflate_par", "k_span_scan", "k_inflate_span",
                                            "k_inflate_size", "k_inflate_size_span",
+                                           "k_member_scan", "k_member_chain", "k_member_walk", "k_member_pack", "k_member_fold",
                                            "k_gather", "k_inflater", "k_deflater"};
 
 struct DevBuf {
@@ -111,6 +119,8 @@ struct fl_knobs {
     int rect = -1;                        // FLATE_HIP_RECT: 1 = half of every slot goes home by the DMA engine's rectangle copy (off by default: see there)
     int64_t inflate_par = -1;             // FLATE_HIP_INFLATE_PAR: -1 unset, 0 never, else the minimum stream size
     int64_t inflate_ring = -1;            // FLATE_HIP_INFLATE_RING: -1 unset
+    bool member_scan = true;              // FLATE_HIP_MEMBER_SCAN: 0 = gzip members are walked, not searched for (flate_hip_decompress_members)
+    uint32_t member_candidates = FL_MEM_CAND_DEFAULT;  // FLATE_HIP_MEMBER_CANDIDATES: a call with more candidates than this walks
 };
 
 struct flate_hip_ctx {
@@ -165,6 +175,12 @@ struct flate_hip_ctx {
     // flate_hip_debug_size_paths the streams of the last call whose size came from a closed chain / from one wave
     DevBuf sz_spans, sz_recs;
     uint64_t dbg_size_chain = 0, dbg_size_whole = 0;
+    // flate_hip_decompress_members: tile counts and their scan, the candidates with their chunks and probe results, the
+    // successor and chain tables, the streams' member tables (as written and back to back), the members' decode results;
+    // for flate_hip_debug_member_paths the last call's streams by path and its candidates that were on no chain
+    DevBuf mb_tiles, mb_tileoff, mb_cand, mb_chunks, mb_psize, mb_pstatus, mb_pcons, mb_succ, mb_chain, mb_taboff, mb_tabn, mb_non,
+        mb_tabstart, mb_tabsize, mb_denseoff, mb_dstart, mb_dsize, mb_outlen, mb_status, mb_cons, mb_nmem;
+    uint64_t dbg_member[3] = {0, 0, 0};
     bool ws_fixed = false;   // the two-stream passes are being enqueued: ensure() may not grow a buffer (compress_impl)
     // last level 4..9 call, for the debug seam
     uint32_t dbg_pass_chunks = 0;
@@ -328,6 +344,8 @@ void read_knobs(fl_knobs& k, uint64_t span_default) {
     if ((e = getenv("FLATE_HIP_STREAM_GROUP")) && atoi(e) > 0) k.stream_group = (uint32_t)atoi(e);
     if ((e = getenv("FLATE_HIP_INFLATE_PAR"))) k.inflate_par = atoll(e);
     if ((e = getenv("FLATE_HIP_INFLATE_RING"))) k.inflate_ring = atoll(e);
+    if ((e = getenv("FLATE_HIP_MEMBER_SCAN"))) k.member_scan = atoi(e) != 0;
+    if ((e = getenv("FLATE_HIP_MEMBER_CANDIDATES")) && atoll(e) >= 0 && atoll(e) <= 0x7fffffffll) k.member_candidates = (uint32_t)atoll(e);
 }
 size_t pass_chunk_limit(const flate_hip_ctx* h) { return h->knobs.max_pass_chunks; }
 // host-buffer calls whose buffers are pinned run in sub-batches of this many chunks, so that the H2D copy of
@@ -725,6 +743,10 @@ int copy_out_host(flate_hip_ctx* h, const uint8_t* d_out, const uint64_t* d_outl
     }
     return FLATE_HIP_OK;
 }
+
+int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint64_t>& hin, uint32_t n_chunks, int container,
+                    int flags, uint8_t* out, const std::vector<uint64_t>& hout, uint64_t* out_len, int32_t* status,
+                    uint64_t* consumed, int memkind);
 
 // Fetch the n+1 offsets to the host (the block tables are built there).
 int fetch_offsets(flate_hip_ctx* h, const uint64_t* off, uint32_t n, int memkind, std::vector<uint64_t>& host) {
@@ -1530,6 +1552,10 @@ int flate_hip_destroy(flate_hip_handle h) {
     for (DevBuf* b : {&h->sp_points, &h->sp_found, &h->sp_spans, &h->sp_res, &h->sp_cand, &h->sp_candoff, &h->sp_tails,
                       &h->sp_tails_b, &h->sp_chain, &h->sp_chainoff, &h->sp_pool, &h->sp_pooltab, &h->sp_poolctl, &h->sp_items,
                       &h->sp_part, &h->sp_footoff, &h->sp_foot, &h->sp_fin, &h->sp_chainpos, &h->sp_rs, &h->sz_spans, &h->sz_recs})
+        if (b->p) (void)hipFree(b->p);
+    for (DevBuf* b : {&h->mb_tiles, &h->mb_tileoff, &h->mb_cand, &h->mb_chunks, &h->mb_psize, &h->mb_pstatus, &h->mb_pcons,
+                      &h->mb_succ, &h->mb_chain, &h->mb_taboff, &h->mb_tabn, &h->mb_non, &h->mb_tabstart, &h->mb_tabsize,
+                      &h->mb_denseoff, &h->mb_dstart, &h->mb_dsize, &h->mb_outlen, &h->mb_status, &h->mb_cons, &h->mb_nmem})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->chunks, &h->blk_chunk, &h->plans, &h->hist, &h->cks, &h->S, &h->NC, &h->rec, &h->desc, &h->marks,
                       &h->tokens, &h->ntok, &h->cflag, &h->links, &h->wchunks, &h->swins, &h->wexit, &h->shard_sz, &h->tiles, &h->segs, &h->pieces, &h->fpts, &h->zones, &h->nsorted, &h->jmp,
@@ -2344,13 +2370,25 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
     if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
     if (n_chunks == 0) return FLATE_HIP_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
-    hipStream_t st = h->stream;
-
     std::vector<uint64_t> hin, hout;
     int rc = fetch_offsets(h, in_off, n_chunks, memkind, hin);
     if (rc) return rc;
     rc = fetch_offsets(h, out_off, n_chunks, memkind, hout);
     if (rc) return rc;
+    return decompress_core(h, in, hin, n_chunks, container, flags, out, hout, out_len, status, consumed, memkind);
+}
+
+}  // extern "C"
+
+namespace {
+
+// flate_hip_decompress_batch behind its offsets: hin / hout are the n_chunks + 1 offsets on the host, everything else is
+// as the entry point got it.  flate_hip_decompress_members runs it over the members it found (device memory).
+int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint64_t>& hin, uint32_t n_chunks, int container,
+                    int flags, uint8_t* out, const std::vector<uint64_t>& hout, uint64_t* out_len, int32_t* status,
+                    uint64_t* consumed, int memkind) {
+    hipStream_t st = h->stream;
+    int rc;
     const uint64_t in_lo = hin[0], in_hi = hin[n_chunks];
     const uint64_t out_lo = hout[0], out_hi = hout[n_chunks];
 
@@ -2529,6 +2567,10 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
     return FLATE_HIP_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
                                  int container, int flags, uint64_t* sizes, int32_t* status, uint64_t* consumed,
                                  int memkind) {
@@ -2607,6 +2649,239 @@ int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]) {
     if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
     counts[0] = h->dbg_size_chain;
     counts[1] = h->dbg_size_whole;
+    return FLATE_HIP_OK;
+}
+
+// The members of every stream, found on the device (kernels_members.h), decoded by decompress_core as streams of their own
+// and folded back.  The host waits for the offsets, for the candidate count (scan) or the member count (walk), and for
+// the member table; then decompress_core waits as it does for any batch on device memory.
+int flate_hip_decompress_members(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                                 int container, int flags, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                                 int32_t* status, uint64_t* consumed, uint32_t* n_members, int memkind) {
+    if (!h || !in_off || !out_off || !out_len || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (n_streams == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    const uint32_t n = n_streams;
+
+    std::vector<uint64_t> hin, hout;
+    int rc = fetch_offsets(h, in_off, n, memkind, hin);
+    if (rc) return rc;
+    if ((rc = fetch_offsets(h, out_off, n, memkind, hout))) return rc;
+    for (uint32_t i = 0; i < n; i++)
+        if (hin[i + 1] - hin[i] > 0xfffffff0ull) return FLATE_HIP_E_INVALID_ARG;
+    const uint64_t in_lo = hin[0], in_hi = hin[n], out_lo = hout[0], out_hi = hout[n];
+
+    // host memory: the whole call runs on staged copies whose offsets start at 0
+    const bool host = memkind == FLATE_HIP_MEM_HOST;
+    const uint8_t* d_in = in;
+    uint8_t* d_out = out;
+    const uint64_t* d_inoff = in_off;
+    uint64_t* d_outlen = out_len;
+    int32_t* d_status = status;
+    uint64_t* d_consumed = consumed;
+    uint32_t* d_nmem = n_members;
+    std::vector<uint64_t> vin(hin), vout(hout);  // the offsets the kernels and decompress_core see
+    if (host) {
+        for (uint32_t i = 0; i <= n; i++) {
+            vin[i] -= in_lo;
+            vout[i] -= out_lo;
+        }
+        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16))) return rc;
+        if ((rc = ensure(h, h->st_out, (out_hi - out_lo) + 16))) return rc;
+        if ((rc = ensure(h, h->st_inoff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+        if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n))) return rc;
+        if ((rc = ensure(h, h->st_status, sizeof(int32_t) * n))) return rc;
+        if ((rc = ensure(h, h->st_consumed, sizeof(uint64_t) * n))) return rc;
+        if ((rc = ensure(h, h->mb_nmem, sizeof(uint32_t) * n))) return rc;
+        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipMemcpyAsync(h->st_inoff.p, vin.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+        // (what goes back to the caller beyond out_len[i] is zeros, never bytes of an earlier call)
+        if (out_hi > out_lo) HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, out_hi - out_lo, st));
+        d_in = (const uint8_t*)h->st_in.p;
+        d_out = (uint8_t*)h->st_out.p;
+        d_inoff = (const uint64_t*)h->st_inoff.p;
+        d_outlen = (uint64_t*)h->st_outlen.p;
+        d_status = (int32_t*)h->st_status.p;
+        d_consumed = consumed ? (uint64_t*)h->st_consumed.p : nullptr;
+        d_nmem = n_members ? (uint32_t*)h->mb_nmem.p : nullptr;
+    }
+    const uint64_t lo = vin[0], hi = vin[n];
+
+    h->dbg_member[0] = h->dbg_member[1] = h->dbg_member[2] = 0;
+    if ((rc = ensure(h, h->mb_taboff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if ((rc = ensure(h, h->mb_tabn, sizeof(uint64_t) * n))) return rc;
+    if ((rc = ensure(h, h->mb_non, sizeof(uint64_t) * n))) return rc;
+    if ((rc = ensure(h, h->mb_denseoff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+
+    // ---- scan: count the candidates; too many, and the call walks ----
+    bool scan = container == 1 && h->knobs.member_scan;
+    uint64_t n_cand = 0;
+    int64_t rel0 = 0;
+    uint64_t n_tiles = 0;
+    if (scan && hi > lo) {
+        const uintptr_t first = (uintptr_t)(d_in + lo);
+        rel0 = (int64_t)lo - (int64_t)(first & 15);
+        n_tiles = (uint64_t)((int64_t)hi - rel0 + FL_MEM_SCAN_TILE - 1) / FL_MEM_SCAN_TILE;
+        if (n_tiles > 0x7fffffffull) return FLATE_HIP_E_INVALID_ARG;
+        if ((rc = ensure(h, h->mb_tiles, sizeof(uint64_t) * (n_tiles + 1)))) return rc;
+        if ((rc = ensure(h, h->mb_tileoff, sizeof(uint64_t) * (n_tiles + 1)))) return rc;
+        {
+            ProfScope ps(h, K_MEMBER_SCAN);
+            hipLaunchKernelGGL(k_member_scan<false>, dim3((uint32_t)n_tiles), dim3(64), 0, st, d_in, rel0, lo, hi, d_inoff, n,
+                               (uint64_t*)h->mb_tiles.p, (uint64_t*)nullptr, (fl_chunk*)nullptr, (uint64_t)0);
+            hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, st, (const uint64_t*)h->mb_tiles.p, (uint32_t)n_tiles,
+                               (uint64_t*)h->mb_tileoff.p);
+        }
+        HIP_OK(h, hipGetLastError());
+        HIP_OK(h, hipMemcpyAsync(&n_cand, (const uint64_t*)h->mb_tileoff.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+        if (n_cand > h->knobs.member_candidates) scan = false;
+    }
+
+    // ---- the member tables ----
+    uint64_t cap = 0;  // entries of all tables together, at most
+    if (scan) {
+        cap = n_cand + n;
+        const size_t nc1 = (size_t)std::max<uint64_t>(n_cand, 1);
+        if ((rc = ensure(h, h->mb_cand, sizeof(uint64_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_chunks, sizeof(fl_chunk) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_psize, sizeof(uint64_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_pstatus, sizeof(int32_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_pcons, sizeof(uint64_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_succ, sizeof(uint32_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_chain, sizeof(uint32_t) * nc1))) return rc;
+    } else {
+        const uint32_t least = fl_member_least_bytes(container);
+        std::vector<uint64_t> toff((size_t)n + 1);
+        for (uint32_t i = 0; i < n; i++) {
+            toff[i] = cap;
+            cap += (hin[i + 1] - hin[i]) / least + 2;
+        }
+        toff[n] = cap;
+        HIP_OK(h, hipMemcpyAsync(h->mb_taboff.p, toff.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipStreamSynchronize(st));  // (toff leaves scope)
+    }
+    if ((rc = ensure(h, h->mb_tabstart, sizeof(uint32_t) * cap))) return rc;
+    if ((rc = ensure(h, h->mb_tabsize, sizeof(uint64_t) * cap))) return rc;
+    if (scan) {
+        if (n_cand) {
+            {
+                ProfScope ps(h, K_MEMBER_SCAN);
+                hipLaunchKernelGGL(k_member_scan<true>, dim3((uint32_t)n_tiles), dim3(64), 0, st, d_in, rel0, lo, hi, d_inoff, n,
+                                   (uint64_t*)h->mb_tileoff.p, (uint64_t*)h->mb_cand.p, (fl_chunk*)h->mb_chunks.p, n_cand);
+            }
+            ProfScope ps(h, K_INFLATE_SIZE);
+            hipLaunchKernelGGL(k_inflate_size<false>, dim3((uint32_t)n_cand), dim3(64), 0, st, d_in, (const fl_chunk*)h->mb_chunks.p,
+                               container, flags, (uint64_t*)h->mb_psize.p, (int32_t*)h->mb_pstatus.p, (uint64_t*)h->mb_pcons.p,
+                               (const fl_size_span*)nullptr, (fl_size_rec*)nullptr);
+        }
+        ProfScope ps(h, K_MEMBER_CHAIN);
+        hipLaunchKernelGGL(k_member_chain, dim3(n), dim3(64), 0, st, d_inoff, (const uint64_t*)h->mb_cand.p, (uint32_t)n_cand,
+                           (const int32_t*)h->mb_pstatus.p, (const uint64_t*)h->mb_pcons.p, (const uint64_t*)h->mb_psize.p,
+                           (uint32_t*)h->mb_succ.p, (uint32_t*)h->mb_chain.p, (uint64_t*)h->mb_taboff.p, (uint64_t*)h->mb_tabn.p,
+                           (uint32_t*)h->mb_tabstart.p, (uint64_t*)h->mb_tabsize.p, (uint64_t*)h->mb_non.p);
+    } else {
+        ProfScope ps(h, K_MEMBER_WALK);
+        hipLaunchKernelGGL(k_member_walk, dim3(n), dim3(64), 0, st, d_in, d_inoff, container, flags, (const uint64_t*)h->mb_taboff.p,
+                           (uint64_t*)h->mb_tabn.p, (uint32_t*)h->mb_tabstart.p, (uint64_t*)h->mb_tabsize.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    // back to back, and home: with the candidates counted the table's size is bounded and it comes with its offsets
+    std::vector<uint64_t> doff((size_t)n + 1), non;
+    std::vector<uint32_t> mstart;
+    std::vector<uint64_t> msize;
+    if ((rc = ensure(h, h->mb_dstart, sizeof(uint32_t) * cap))) return rc;
+    if ((rc = ensure(h, h->mb_dsize, sizeof(uint64_t) * cap))) return rc;
+    {
+        ProfScope ps(h, K_MEMBER_PACK);
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, st, (const uint64_t*)h->mb_tabn.p, n, (uint64_t*)h->mb_denseoff.p);
+        hipLaunchKernelGGL(k_member_pack, dim3(n), dim3(64), 0, st, (const uint64_t*)h->mb_taboff.p, (const uint64_t*)h->mb_tabn.p,
+                           (const uint32_t*)h->mb_tabstart.p, (const uint64_t*)h->mb_tabsize.p, (const uint64_t*)h->mb_denseoff.p,
+                           (uint32_t*)h->mb_dstart.p, (uint64_t*)h->mb_dsize.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipMemcpyAsync(doff.data(), h->mb_denseoff.p, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
+    if (scan) {
+        non.resize(n);
+        mstart.resize(cap);
+        msize.resize(cap);
+        HIP_OK(h, hipMemcpyAsync(non.data(), h->mb_non.p, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(mstart.data(), h->mb_dstart.p, sizeof(uint32_t) * cap, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(msize.data(), h->mb_dsize.p, sizeof(uint64_t) * cap, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(h, hipStreamSynchronize(st));
+    const uint64_t M = doff[n];
+    if (M < n || M > cap || M > 0xfffffff0ull) {
+        h->last_error = "member table: " + std::to_string(M) + " members of " + std::to_string(n) + " streams";
+        return FLATE_HIP_E_LAUNCH;
+    }
+    if (!scan) {
+        mstart.resize(M);
+        msize.resize(M);
+        HIP_OK(h, hipMemcpyAsync(mstart.data(), h->mb_dstart.p, sizeof(uint32_t) * M, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(msize.data(), h->mb_dsize.p, sizeof(uint64_t) * M, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+    }
+    if (scan) {
+        uint64_t on = 0;
+        for (uint32_t i = 0; i < n; i++) on += non[i];
+        h->dbg_member[0] = n;
+        h->dbg_member[2] = n_cand - on;
+    } else {
+        h->dbg_member[1] = n;
+    }
+
+    // ---- the members as a batch of their own: a contiguous partition of the input and of the slots ----
+    std::vector<uint64_t> min_((size_t)M + 1), mout((size_t)M + 1);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t m0 = doff[i], m = doff[i + 1] - m0;
+        if (m == 0 || mstart[m0] != 0) {
+            h->last_error = "member table: stream " + std::to_string(i) + " does not start with a member";
+            return FLATE_HIP_E_LAUNCH;
+        }
+        for (uint64_t k = 0; k < m; k++) {
+            min_[m0 + k] = vin[i] + mstart[m0 + k];
+            if (min_[m0 + k] > vin[i + 1] || (k && mstart[m0 + k] < mstart[m0 + k - 1])) {
+                h->last_error = "member table: stream " + std::to_string(i) + " is out of order";
+                return FLATE_HIP_E_LAUNCH;
+            }
+        }
+        fl_member_slots(msize.data() + m0, (uint32_t)m, vout[i], vout[i + 1], mout.data() + m0);
+    }
+    min_[M] = vin[n];
+    mout[M] = vout[n];
+    if ((rc = ensure(h, h->mb_outlen, sizeof(uint64_t) * M))) return rc;
+    if ((rc = ensure(h, h->mb_status, sizeof(int32_t) * M))) return rc;
+    if ((rc = ensure(h, h->mb_cons, sizeof(uint64_t) * M))) return rc;
+    if ((rc = decompress_core(h, d_in, min_, (uint32_t)M, container, flags, d_out, mout, (uint64_t*)h->mb_outlen.p,
+                              (int32_t*)h->mb_status.p, (uint64_t*)h->mb_cons.p, FLATE_HIP_MEM_DEVICE)))
+        return rc;
+    {
+        ProfScope ps(h, K_MEMBER_FOLD);
+        hipLaunchKernelGGL(k_member_fold, dim3(n), dim3(64), 0, st, (const uint64_t*)h->mb_denseoff.p,
+                           (const uint64_t*)h->mb_outlen.p, (const int32_t*)h->mb_status.p, (const uint64_t*)h->mb_cons.p, d_outlen,
+                           d_status, d_consumed, d_nmem);
+    }
+    HIP_OK(h, hipGetLastError());
+    if (host) {
+        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        if (consumed) HIP_OK(h, hipMemcpyAsync(consumed, d_consumed, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
+        if (n_members) HIP_OK(h, hipMemcpyAsync(n_members, d_nmem, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+        if ((rc = copy_out_host(h, d_out, d_outlen, n, hout, out_lo, out, out_len))) return rc;
+    } else if (h->sync) {
+        HIP_OK(h, hipStreamSynchronize(st));
+    }
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_debug_member_paths(flate_hip_handle h, uint64_t counts[3]) {
+    if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
+    for (int i = 0; i < 3; i++) counts[i] = h->dbg_member[i];
     return FLATE_HIP_OK;
 }
 

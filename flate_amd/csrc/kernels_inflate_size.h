@@ -115,6 +115,54 @@ __device__ __forceinline__ int fl_sz_dynamic(fl_bitr& r, FL_LDS fl_inflate_ws16*
     }
 }
 
+// One member from where the reader stands: the container's header (first), the blocks up to the one with BFINAL (SPAN: or
+// up to the first block that starts at or behind stop_bit) and the footer, which is read, not compared.  Returns the
+// status; cnt has the bytes, end_bit / final_seen what a span's record wants.  k_inflate_size counts one member with it,
+// k_member_walk (kernels_members.h) one after the other.
+template <bool SPAN>
+__device__ __forceinline__ int fl_sz_member(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, int container, int flags, uint32_t lane,
+                                            bool first, uint64_t stop_bit, uint64_t total_bits, fl_sz_count<SPAN>& cnt,
+                                            uint32_t& final_seen, uint64_t& end_bit) {
+    int rc = first ? (int)fl_uni((uint32_t)fl_inf_header(r, container)) : 0;
+    while (rc == 0) {  // inflate.zig:251-280
+        if (SPAN) {
+            end_bit = total_bits - (uint64_t)r.left;  // a block starts here
+            if (end_bit >= stop_bit) break;
+        }
+        uint32_t bfinal, btype;
+        if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 1, bfinal)))) break;
+        if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 2, btype)))) break;
+        bfinal = fl_uni(bfinal);
+        btype = fl_uni(btype);
+        if (btype == 2) {
+            if ((rc = (int)fl_uni((uint32_t)fl_inf_dynamic_header(r, ws, flags, lane)))) break;
+            rc = (int)fl_uni((uint32_t)fl_sz_dynamic<SPAN>(r, ws, cnt, lane));
+        } else if (btype == 0) {
+            rc = (int)fl_uni((uint32_t)fl_sz_stored<SPAN>(r, cnt));
+        } else if (btype == 1) {
+            rc = (int)fl_uni((uint32_t)fl_inf_fixed(r, cnt, lane));
+        } else {
+            rc = 12;  // InvalidBlockType
+        }
+        if (rc) break;
+        if (bfinal) {
+            fl_br_align(r);
+            end_bit = total_bits - (uint64_t)r.left;
+            // container.zig:154-166: the footer is read, not compared
+            uint32_t v;
+            if (container == 1) {
+                if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 32, v)))) break;
+                if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 32, v)))) break;
+            } else if (container == 2) {
+                if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 32, v)))) break;
+            }
+            final_seen = 1;
+            break;
+        }
+    }
+    return rc;
+}
+
 // One wave per stream (SPAN = false: workgroup i counts stream i, unless chunks[i].skip says the host has its size
 // already) or per span (SPAN = true: workgroup j counts spans[j] and writes recs[j]).
 #ifndef FL_SZ_WAVES
@@ -156,44 +204,7 @@ __global__ __launch_bounds__(64, FL_SZ_WAVES) void k_inflate_size(const uint8_t*
     cnt.need = 0;
     uint32_t final_seen = 0;
     uint64_t end_bit = 0;
-
-    int rc = first ? (int)fl_uni((uint32_t)fl_inf_header(r, container)) : 0;
-    while (rc == 0) {  // inflate.zig:251-280
-        if (SPAN) {
-            end_bit = total_bits - (uint64_t)r.left;  // a block starts here
-            if (end_bit >= stop_bit) break;
-        }
-        uint32_t bfinal, btype;
-        if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 1, bfinal)))) break;
-        if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 2, btype)))) break;
-        bfinal = fl_uni(bfinal);
-        btype = fl_uni(btype);
-        if (btype == 2) {
-            if ((rc = (int)fl_uni((uint32_t)fl_inf_dynamic_header(r, ws, flags, lane)))) break;
-            rc = (int)fl_uni((uint32_t)fl_sz_dynamic<SPAN>(r, ws, cnt, lane));
-        } else if (btype == 0) {
-            rc = (int)fl_uni((uint32_t)fl_sz_stored<SPAN>(r, cnt));
-        } else if (btype == 1) {
-            rc = (int)fl_uni((uint32_t)fl_inf_fixed(r, cnt, lane));
-        } else {
-            rc = 12;  // InvalidBlockType
-        }
-        if (rc) break;
-        if (bfinal) {
-            fl_br_align(r);
-            end_bit = total_bits - (uint64_t)r.left;
-            // container.zig:154-166: the footer is read, not compared
-            uint32_t v;
-            if (container == 1) {
-                if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 32, v)))) break;
-                if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 32, v)))) break;
-            } else if (container == 2) {
-                if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 32, v)))) break;
-            }
-            final_seen = 1;
-            break;
-        }
-    }
+    const int rc = fl_sz_member<SPAN>(r, ws, container, flags, lane, first, stop_bit, total_bits, cnt, final_seen, end_bit);
     if (lane == 0) {
         if (SPAN) {
             fl_size_rec rec;

@@ -48,7 +48,8 @@ class Engine:
     # ---- configuration ----
     _KNOBS = ("FLATE_HIP_MAX_PASS_CHUNKS", "FLATE_HIP_HOST_PASS_CHUNKS", "FLATE_HIP_MAX_STREAM_PASS_MIB",
               "FLATE_HIP_INFLATE_SPANS", "FLATE_HIP_SPAN_DEBUG", "FLATE_HIP_SPAN_TWIN", "FLATE_HIP_NO_PIN_MIRROR",
-              "FLATE_HIP_NO_RAMP", "FLATE_HIP_INFLATE_PAR", "FLATE_HIP_INFLATE_RING", "FLATE_HIP_RECT", "FLATE_HIP_STREAM_WINDOWS", "FLATE_HIP_SIMPLE_CK_INLINE", "FLATE_HIP_STREAM_GROUP", "FLATE_HIP_SPAN_TWO_RUNS", "FLATE_HIP_MEMSET_INLINE", "FLATE_HIP_ONE_COMPUTE_STREAM")
+              "FLATE_HIP_NO_RAMP", "FLATE_HIP_INFLATE_PAR", "FLATE_HIP_INFLATE_RING", "FLATE_HIP_RECT", "FLATE_HIP_STREAM_WINDOWS", "FLATE_HIP_SIMPLE_CK_INLINE", "FLATE_HIP_STREAM_GROUP", "FLATE_HIP_SPAN_TWO_RUNS", "FLATE_HIP_MEMSET_INLINE", "FLATE_HIP_ONE_COMPUTE_STREAM",
+              "FLATE_HIP_MEMBER_SCAN", "FLATE_HIP_MEMBER_CANDIDATES")
 
     def _sync_env(self):
         """The library reads its FLATE_HIP_* tuning variables once, when the handle is made.  Tests and probes change them
@@ -153,6 +154,50 @@ class Engine:
                                                   sizes.ctypes.data, status.ctypes.data, consumed.ctypes.data, MEM_HOST)
         self._check(rc, "flate_hip_decompressed_sizes")
         return [int(x) for x in sizes], [int(x) for x in status], [int(x) for x in consumed]
+
+    def decompress_members(self, streams, container=0, flags=0, caps=None):
+        """Every member of each stream, concatenated (flate_hip_decompress_members): what a caller gets who decodes a
+        stream member by member with decompress_many and its consumed count, in one call.  caps: output capacity per
+        stream (default: 1100 output bytes per input byte).
+        Returns (list of bytes -- the members in front of the first failing one --, list of status codes, list of
+        consumed input bytes, list of member counts)."""
+        self._sync_env()
+        n = len(streams)
+        if n == 0:
+            return [], [], [], []
+        blob, in_off = self._host_input(streams)
+        if caps is None:
+            caps = [max(1 << 16, len(c) * 1100 + 1024) for c in streams]
+        caps = np.array([int(c) for c in caps], dtype=np.uint64)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(caps, out=out_off[1:])
+        out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int32)
+        consumed = np.zeros(n, dtype=np.uint64)
+        members = np.zeros(n, dtype=np.uint32)
+        rc = self._L.flate_hip_decompress_members(self._h, blob.ctypes.data, in_off.ctypes.data, n, container, flags,
+                                                  out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                                  status.ctypes.data, consumed.ctypes.data, members.ctypes.data, MEM_HOST)
+        self._check(rc, "flate_hip_decompress_members")
+        res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
+        return res, [int(s) for s in status], [int(c) for c in consumed], [int(m) for m in members]
+
+    def decompress_members_device(self, in_ptr, in_off_ptr, n_streams, container, flags, out_ptr, out_off_ptr, out_len_ptr,
+                                  status_ptr, consumed_ptr=None, n_members_ptr=None):
+        """flate_hip_decompress_members on device memory (n + 1 offsets; n lengths / statuses / consumed / member counts)."""
+        self._sync_env()
+        rc = self._L.flate_hip_decompress_members(self._h, in_ptr, in_off_ptr, n_streams, container, flags, out_ptr,
+                                                  out_off_ptr, out_len_ptr, status_ptr, consumed_ptr, n_members_ptr,
+                                                  MEM_DEVICE)
+        self._check(rc, "flate_hip_decompress_members")
+
+    def member_paths(self):
+        """How the last decompress_members call found its members: (streams by the scan for candidates, streams walked,
+        candidates probed that lie on no chain) (flate_hip_debug_member_paths)."""
+        v = np.zeros(3, dtype=np.uint64)
+        self._check(self._L.flate_hip_debug_member_paths(self._h, v.ctypes.data), "flate_hip_debug_member_paths")
+        return int(v[0]), int(v[1]), int(v[2])
 
     def _measured_caps(self, streams, container, flags, worst):
         """slots from the size probe: the stream's size + 8 where the probe's status is 0, the worst case elsewhere"""

@@ -9,5 +9,6 @@ Compressor = _m.Compressor
 decompress = _m.decompress
 decompressor = _m.decompressor
 Decompressor = _m.Decompressor
+decompress_members = _m.decompress_members
 huffman = _m.huffman
 store = _m.store

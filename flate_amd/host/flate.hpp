@@ -10,6 +10,7 @@
 //   Compressor<Writer> / compressor(writer, opt)  flate.zig:33-40   write / compress / finish
 //   decompress(reader, writer)                    flate.zig:10-12
 //   Decompressor<Reader> / decompressor(reader)   flate.zig:15-22   decompress / next / read / reset
+//   decompress_members(reader, writer)            -- (not in the reference: all concatenated members in one GPU call)
 //   huffman::{compress,Compressor,compressor}     flate.zig:44-56
 //   store::{compress,Compressor,compressor}       flate.zig:59-71
 //
@@ -135,6 +136,30 @@ class Engine {
             if (status) throw Error(status);
             out.resize(out_len);
             return consumed;
+        }
+    }
+    // every concatenated member of `in` in one call (flate_hip_decompress_members); returns how many there were
+    uint32_t decompress_members(const uint8_t* in, size_t n, int container, std::vector<uint8_t>& out) {
+        size_t cap = n * 8 + (1 << 16);
+        for (;;) {
+            const uint64_t in_off[2] = {0, n};
+            const uint64_t out_off[2] = {0, cap};
+            out.assign(cap + 8, 0);
+            uint64_t out_len = 0;
+            uint32_t members = 0;
+            int32_t status = 0;
+            const uint8_t dummy = 0;
+            const int rc = flate_hip_decompress_members(h_, n ? in : &dummy, in_off, 1, container, 0, out.data(), out_off,
+                                                        &out_len, &status, nullptr, &members, FLATE_HIP_MEM_HOST);
+            if (rc != FLATE_HIP_OK)
+                throw Error(rc, std::string("flate_hip_decompress_members: ") + flate_hip_last_error(h_));
+            if (status == FLATE_HIP_ST_OUTPUT_TOO_SMALL && cap < (size_t(1) << 36)) {
+                cap *= 8;
+                continue;
+            }
+            if (status) throw Error(status);
+            out.resize(out_len);
+            return members;
         }
     }
 
@@ -383,6 +408,15 @@ class DecompressorImpl {
     template <class Reader, class Writer>                                                                    \
     void decompress(Reader& r, Writer& w) {                                                                  \
         decompressor(r).decompress(w);                                                                       \
+    }                                                                                                        \
+    /* every concatenated member of the reader's bytes in one GPU call; throws the first failing member's error */ \
+    template <class Reader, class Writer>                                                                    \
+    uint32_t decompress_members(Reader& r, Writer& w) {                                                      \
+        std::vector<uint8_t> in, out;                                                                        \
+        detail::read_all(r, in);                                                                             \
+        const uint32_t m = Engine::instance().decompress_members(in.data(), in.size(), TAG, out);            \
+        w.write(out.data(), out.size());                                                                     \
+        return m;                                                                                            \
     }                                                                                                        \
     namespace huffman {                                                                                      \
     template <class Writer>                                                                                  \

@@ -228,6 +228,47 @@ int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const ui
                                  int memkind);
 
 /*
+ * Every member of concatenated gzip / zlib / raw streams, in one call.  The arguments have the shape of
+ * flate_hip_decompress_batch; consumed and n_members may be NULL.  The meaning is exactly the loop a caller of
+ * flate_hip_decompress_batch writes: for stream i with bytes S = in[in_off[i] .. in_off[i+1]) and slot O,
+ *
+ *     pos = 0; produced = 0; members = 0
+ *     repeat
+ *         decode ONE member from S[pos:] into O[produced:]   (what flate_hip_decompress_batch does, same flags)
+ *         if its status != 0: status[i] = that status; stop
+ *         produced += its out_len; pos += its consumed; members += 1
+ *     until pos == len(S)
+ *     status[i] = 0
+ *
+ * and out_len[i] = produced, consumed[i] = pos, n_members[i] = members: all three count only the members in front of
+ * the first failing one, whose bytes are in the slot; slot bytes beyond out_len[i] are unspecified.  The first member is
+ * always attempted, so an empty stream is EndOfStream (1) in all three containers.  Trailing bytes are a further member:
+ * behind a gzip member they give BadGzipHeader (2) when 10 or more are left and the magic or the method is wrong,
+ * EndOfStream (1) when fewer than 10 are left.  A member that does not fit the rest of the slot gives
+ * FLATE_HIP_ST_OUTPUT_TOO_SMALL (100) for the stream.  A stream may be at most 0xfffffff0 bytes; n_streams == 0 returns
+ * FLATE_HIP_OK.  flate_hip_debug_inflate_paths afterwards describes the decode of the members.
+ *
+ * How the members are found.  gzip: every position of 1f 8b 08 inside a stream is a candidate, every candidate is probed
+ * as flate_hip_decompressed_sizes probes a stream (a wave each, no output), and each stream's chain of candidates is
+ * followed on the device from its first byte; a candidate no chain reaches -- the magic inside compressed bits, a stored
+ * block, a file name -- costs its probe and nothing else.  zlib and raw members cannot be told from their bytes; their
+ * streams are walked member by member by one wave each, and so are gzip streams when FLATE_HIP_MEMBER_SCAN=0 or when a
+ * call has more candidates than FLATE_HIP_MEMBER_CANDIDATES (4194304 by default).  The walk is always correct, only slow:
+ * one long file is walked by one wave.  A long member is likewise counted by one wave before it is decoded.  The members
+ * are then decoded as a batch of their own by the kernels of flate_hip_decompress_batch (long members by spans or a
+ * workgroup each), which compare the footers; the probe does not.  The walk's member table takes 12 bytes for every 20
+ * (gzip), 8 (zlib) or 2 (raw) bytes of input.
+ *
+ * FLATE_HIP_MEM_HOST: input and slots are staged and the call is synchronous.  FLATE_HIP_MEM_DEVICE: all arrays are device
+ * memory.  Either way the call WAITS ON THE HOST three times beyond what the decode of the members waits for as any
+ * batch on device memory does: for the offsets, for the number of candidates (walk: of members), and for the member
+ * table.  It cannot be captured in a graph.
+ */
+int flate_hip_decompress_members(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                                 int container, int flags, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                                 int32_t* status, uint64_t* consumed, uint32_t* n_members, int memkind);
+
+/*
  * Pack the n_chunks produced streams back to back (device memory only): copies
  * out[out_off[i] .. out_off[i] + out_len[i]) to dst[dst_off[i] ..) with
  * dst_off[i] = sum of out_len[k] for k < i; dst_off has n_chunks + 1 entries (the last
@@ -364,6 +405,9 @@ int flate_hip_debug_inflate_paths(flate_hip_handle h, uint64_t counts[4]);
 /* test seam: for the handle's last flate_hip_decompressed_sizes call, counts[0]: streams whose size came from a closed
  * chain of spans; counts[1]: streams counted whole by one wave. */
 int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]);
+/* test seam: for the handle's last flate_hip_decompress_members call, counts[0]: streams whose members were found by the
+ * scan for candidates; counts[1]: streams that were walked; counts[2]: candidates that were probed and lie on no chain. */
+int flate_hip_debug_member_paths(flate_hip_handle h, uint64_t counts[3]);
 
 /* The containers' checksums on their own (container.zig:168-206: std.hash.Crc32 / Adler32 over the raw
  * input): container 1 = CRC-32, 2 = Adler-32 of a host buffer, computed by the checksum kernels; and the

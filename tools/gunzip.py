@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""gunzip [--piece N] <file>.gz: writes <file> with the MI355X engine -- the reference's bin/gunzip.zig:25-27
+"""gunzip [--piece N | --members] <file>.gz: writes <file> with the MI355X engine -- the reference's bin/gunzip.zig:25-27
 (`gzip.decompress(br.reader(), output_file.writer())`; refuses names without the .gz suffix, :15-19).
 Concatenated members are decoded one after the other (Inflate.reset, inflate.zig:301-309).  With --piece N the file is
-read N bytes at a time and decoded by the resumable inflater: memory stays bounded whatever the file's size."""
+read N bytes at a time and decoded by the resumable inflater: memory stays bounded whatever the file's size.  With
+--members the file is read whole and all its members are found and decoded in one GPU call (gzip.decompress_members)."""
 import os
 os.environ.setdefault("FLATE_HIP_PRELOAD_TORCH_HIP", "1")  # one HIP runtime per process: torch, imported later, brings its own (flate_amd/_capi.py)
 import sys
@@ -15,8 +16,11 @@ def main(argv=None):
     piece = None
     if len(argv) == 3 and argv[0] == "--piece" and argv[1].isdigit() and int(argv[1]) > 0:
         piece, argv = int(argv[1]), argv[2:]
+    members = False
+    if len(argv) == 2 and argv[0] == "--members":
+        members, argv = True, argv[1:]
     if len(argv) != 1:
-        print("usage: gunzip.py [--piece N] <file>.gz", file=sys.stderr)
+        print("usage: gunzip.py [--piece N | --members] <file>.gz", file=sys.stderr)
         return 2
     name = argv[0]
     if not name.endswith(".gz"):
@@ -28,11 +32,14 @@ def main(argv=None):
     out_name, tmp_name = name[:-3], name[:-3] + ".gunzip-tmp"
     try:
         with open(name, "rb") as src, open(tmp_name, "wb") as dst:
-            d = gzip.decompressor(src) if piece is None else gzip.decompressor(src, piece=piece)
-            d.decompress(dst)
-            while d.more_input():  # further members of the same file
-                d.reset()
+            if members:
+                dst.write(gzip.decompress_members(src))
+            else:
+                d = gzip.decompressor(src) if piece is None else gzip.decompressor(src, piece=piece)
                 d.decompress(dst)
+                while d.more_input():  # further members of the same file
+                    d.reset()
+                    d.decompress(dst)
         os.replace(tmp_name, out_name)
     except BaseException:
         if os.path.exists(tmp_name):
