@@ -92,6 +92,26 @@ struct fl_hcode {
     uint16_t len;
 };
 
+// ---- CRC-32 (IEEE, reflected) polynomial arithmetic, as zlib's multmodp ----
+#define FL_CRC_POLY 0xEDB88320u
+FL_HD uint32_t fl_crc_mulmod(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 0; i < 32; i++) {
+        if (a & 0x80000000u) p ^= b;
+        a <<= 1;
+        b = (b & 1) ? ((b >> 1) ^ FL_CRC_POLY) : (b >> 1);
+    }
+    return p;
+}
+// x^(8*n) mod P using the table of x^(8*2^j), j < 32, for every 64-bit n: x has order 2^32 - 1 modulo P, so
+// x^(8 * 2^(j + 32)) = x^(8 * 2^j) and bit j + 32 of n takes entry j again
+FL_HD uint32_t fl_crc_xpow8n(const uint32_t* xpow8, uint64_t n) {
+    uint32_t p = 0x80000000u;
+    for (int j = 0; n; j++, n >>= 1)
+        if (n & 1) p = fl_crc_mulmod(xpow8[j & 31], p);
+    return p;
+}
+
 // ---- RFC 1951 3.2.5 tables (Token.zig:143-276) ----
 FL_HD uint32_t fl_len_extra_bits(uint32_t idx) {  // idx = length code - 257
     return idx < 8 ? 0u : (idx == 28 ? 0u : (idx - 4) >> 2);

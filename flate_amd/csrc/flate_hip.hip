@@ -33,6 +33,7 @@
 #include "member_plan.h"
 #include "pass_plan.h"
 #include "size_plan.h"
+#include "span_plan.h"
 #include "stream_tables.h"
 
 namespace {
@@ -242,6 +243,31 @@ int ensure(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
     b.cap = want;
     h->ws_bytes += want;
     return FLATE_HIP_OK;
+}
+
+// ensure() for callers that have another way to go when there is no room: false, and the failure is not this call's
+bool room(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
+    if (ensure(h, b, bytes) == FLATE_HIP_OK) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// A side stream and the two events that tie it to the caller's stream: all three or none
+bool side_stream(hipStream_t& s, hipEvent_t& ev0, hipEvent_t& ev1) {
+    hipStream_t s_new = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipStreamCreateWithFlags(&s_new, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e0, hipEventDisableTiming) == hipSuccess &&
+        hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess) {
+        s = s_new;
+        ev0 = e0;
+        ev1 = e1;
+        return true;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (s_new) (void)hipStreamDestroy(s_new);
+    (void)hipGetLastError();
+    return false;
 }
 
 // compute units of the device, asked once (256 where the device does not say)
@@ -959,10 +985,7 @@ int enqueue_pass(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t n
 int scan_block_starts(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, int flags, const std::vector<fl_scan_point>& points,
                       std::vector<uint64_t>& found) {
     const uint32_t npts = (uint32_t)points.size();
-    if (ensure(h, h->sp_points, sizeof(fl_scan_point) * npts) || ensure(h, h->sp_found, sizeof(uint64_t) * npts)) {
-        (void)hipGetLastError();
-        return 0;
-    }
+    if (!room(h, h->sp_points, sizeof(fl_scan_point) * npts) || !room(h, h->sp_found, sizeof(uint64_t) * npts)) return 0;
     if (hipMemcpyAsync(h->sp_points.p, points.data(), sizeof(fl_scan_point) * npts, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     {
         ProfScope ps(h, K_SPAN_SCAN);
@@ -975,80 +998,46 @@ int scan_block_starts(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, int
     return 1;
 }
 
+// FLATE_HIP_SPAN_DEBUG: what the walk over one stream's records (span_plan.h, fl_span_follow_chain) saw and made of them
+void span_debug_chain(const fl_span_chain& pl, uint32_t stream, const std::vector<fl_span>& spans, const std::vector<fl_span_res>& r1,
+                      uint32_t a, uint32_t b) {
+    std::vector<uint32_t> seen = pl.chain;
+    if (seen.empty() || seen.back() != pl.last) seen.push_back(pl.last);  // (the span whose record ended the walk before it joined)
+    for (size_t g = 0; g < seen.size() && g < 6; g++) {
+        const fl_span_res& r = r1[seen[g]];
+        fprintf(stderr, "[spans] pass 1 span %u: start %llu status %u end %llu out %llu final %u\n", seen[g], (unsigned long long)spans[seen[g]].start_bit, r.status, (unsigned long long)r.end_bit, (unsigned long long)r.out_len, r.final_seen);
+    }
+    fprintf(stderr, "[spans] stream %u: chain of %zu spans, %llu bytes, ok=%d\n", stream, pl.chain.size(), (unsigned long long)pl.total, (int)pl.ok);
+    for (uint32_t j = a; j < b; j++)
+        fprintf(stderr, "[spans]    span %u: start %llu status %u (0: decoded; else why it gave up) end %llu out %llu final %u blocks / pieces %u\n", j,
+                (unsigned long long)spans[j].start_bit, r1[j].status, (unsigned long long)r1[j].end_bit, (unsigned long long)r1[j].out_len, r1[j].final_seen, r1[j].n_pieces);
+}
+
 // Long streams, few of them: cut each at block starts into spans and decode the spans at once, twice
 // (kernels_inflate_par.h, "spans").  Streams that come out whole get their status / out_len / consumed here and
 // chunks[i].skip = 1 (the kernels that follow leave them alone); everything else stays as it was.
-// Returns the number of streams finished, or a negative FLATE_HIP_E_*.
-#define FL_SPAN_MIN_BYTES (128u * 1024u)   // streams shorter than this are not cut (8-32 members of 1 MiB, 130-1000 KB each: 7.0-8.0 -> 5.1-6.2 ms)
-#define FL_SPAN_BYTES (64u * 1024u)        // compressed bytes per span, at least
-#define FL_SPAN_MAX 1024u                  // spans per call
-#ifndef FL_SPAN_STREAMS
-#define FL_SPAN_STREAMS 32u
-#endif
+// Every decision is span_plan.h's; this is plan, upload, launch, read back, three times (three host waits).
+// No room for a buffer: 0, the old way.  Returns the number of streams finished, or a negative FLATE_HIP_E_*.
 int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::vector<fl_chunk>& chunks, int container,
                      int flags, uint8_t* d_out, uint64_t* d_outlen, int32_t* d_status, uint64_t* d_consumed) {
     const uint32_t n_chunks = (uint32_t)chunks.size();
     const uint64_t min_bytes = h->knobs.span_min_bytes;  // FLATE_HIP_INFLATE_SPANS -- 0: never; else the minimum stream size in bytes
-    if (!min_bytes || (flags & 1)) return 0;
     const bool dbg = h->knobs.span_debug;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
-    // Worth it (every span is decoded twice) when the long streams of the batch are too few to fill the chip with
-    // a workgroup each: at most FL_SPAN_STREAMS of them (-DFL_SPAN_STREAMS: tuning)
-    std::vector<uint32_t> elig;
-    uint32_t n_long = 0;
-    for (uint32_t i = 0; i < n_chunks; i++) n_long += chunks[i].in_len >= 32768u ? 1u : 0u;
     const uint32_t n_cu = device_cu_count(h);
-    // More long streams than that, but fewer than CUs (config #5: 128 members on 256 CUs): every long stream is cut
-    // ONCE, where about f = 2 S / (CUs + S) of it lies before the cut, and both runs of the second spans go in one launch
-    // with the first spans (TWIN): the CUs the first spans leave free decode the second spans twice in the time the
-    // first spans take.  (Cut in two by the rule above, the second run would have half the chip to itself.)  A stream
-    // without a place to cut at is one span, decoded in place by run A: as before, but in the same launch.  Config #5,
-    // cut at 56 / 62 / 66.6 / 72 / 78 % of the compressed bytes: 11.7 / 7.9 / 6.3 / 6.9 / 7.1 ms -- second spans that
-    // are too long cost more than first spans that are: 1.5 % are added to f.
     const int etw = h->knobs.span_twin;  // FLATE_HIP_SPAN_TWIN -- -1: unset; 0: never; 2..950: where to cut, in thousandths of the stream (tuning)
     const bool sym = !h->knobs.span_two_runs;  // one decode per span, in symbols (kernels_inflate_par.h)
-    const bool twin = n_long > FL_SPAN_STREAMS && etw != 0 && (size_t)n_long * 20 <= (size_t)n_cu * 11;  // (40 / 64 / 96 / 160 / 200 one-MiB members: 7.9 / 7.9 / 13.0 / 13.0 / 13.0 ms a workgroup each, 6.1 / 6.1 / 9.1 / 13.3 / 13.4 this way)
-    if (n_long > FL_SPAN_STREAMS && !twin) return 0;
-    const uint64_t elig_bytes = twin ? std::min<uint64_t>(min_bytes, 32768u) : min_bytes;
-    for (uint32_t i = 0; i < n_chunks; i++)
-        if (chunks[i].in_len >= elig_bytes) elig.push_back(i);
-    if (elig.empty() || elig.size() > 256) return 0;
+    const fl_span_elig taken = fl_span_eligible(chunks.data(), n_chunks, min_bytes, flags, n_cu, etw);
+    const std::vector<uint32_t>& elig = taken.elig;
+    const bool twin = taken.twin;
+    const bool both = twin || sym;  // what run B makes is there after run A's launch
+    if (elig.empty()) return 0;
     h->dbg_span_taken = elig.size();  // (what does not come out whole below is handed on)
-    int rc;
     // ---- where spans may start
     std::vector<fl_scan_point> points;
-    std::vector<uint32_t> pt_first(elig.size() + 1, 0);
-    // A span is a workgroup, a workgroup has a CU to itself: as many spans as CUs (a few less: what else runs), or
-    // a multiple of that for long inputs -- 313 spans on 256 CUs take as long as 499 (measured: 170 MiB of text as
-    // 249 / 313 / 374 / 499 / 703 spans: 12.3 / 17.5 / 16.2 / 14.3 / 16.3 ms), and every span costs k_span_scan and
-    // k_span_resolve a step.
-    // What a span costs goes with the bytes it makes; a stream's share of the spans goes with the room its caller
-    // gave it (exact for gzip members whose ISIZE was read; 32 bytes per compressed byte at most), a span has at
-    // least FL_SPAN_BYTES / 4 compressed bytes.
-    auto weight = [&](const fl_chunk& c) { return std::max<uint64_t>(c.in_len, std::min<uint64_t>(c.out_cap, 32ull * c.in_len)); };
-    uint64_t elig_w = 0;
-    for (uint32_t ci : elig) elig_w += weight(chunks[ci]);
-    const uint64_t rounds = std::min<uint64_t>(4, std::max<uint64_t>(1, (elig_w + n_cu * 393216ull) / (n_cu * 786432ull)));
-    const uint64_t want = std::min<uint64_t>({(uint64_t)FL_SPAN_MAX, rounds * n_cu - std::min<uint32_t>(8u, n_cu / 2), std::max<uint64_t>(2, elig_w / (3 * FL_SPAN_BYTES))});
-    for (size_t k = 0; k < elig.size(); k++) {
-        const fl_chunk& c = chunks[elig[k]];
-        const uint64_t bits = (uint64_t)c.in_len * 8;
-        const uint32_t P = twin ? 2u : (uint32_t)std::max<uint64_t>(2, std::min<uint64_t>(want * weight(c) / elig_w, c.in_len / (FL_SPAN_BYTES / 4)));
-        for (uint32_t j = 1; j < P; j++) {
-            fl_scan_point pt;
-            // (two runs: f = 2 S / (CUs + S) of the stream before the cut, + 1.5 %; one decode in symbols, 1.25 x the cost of a decode in
-            // bytes: f = 1.25 S / (CUs + S / 4))
-            const uint64_t auto_f = sym ? std::min<uint64_t>(900, std::max<uint64_t>(500, 1250ull * elig.size() / (n_cu + elig.size() / 4) + 10))
-                                        : std::min<uint64_t>(900, std::max<uint64_t>(500, 2000ull * elig.size() / (n_cu + elig.size()) + 15));
-            pt.from_bit = twin ? bits / 1000 * (etw > 1 ? (uint64_t)std::min(950, etw) : auto_f) : bits / P * j;
-            pt.limit_bit = j + 1 < P ? bits / P * (j + 1) : bits;
-            pt.stream = elig[k];
-            pt.pad = 0;
-            points.push_back(pt);
-        }
-        pt_first[k + 1] = (uint32_t)points.size();
-    }
+    std::vector<uint32_t> pt_first;
+    fl_span_targets(chunks.data(), elig, twin, etw, sym, n_cu, points, pt_first);
     const uint32_t npts = (uint32_t)points.size();
     std::vector<uint64_t> found;
     if (const int sc = scan_block_starts(h, st, d_in, flags, points, found); sc <= 0) return sc;
@@ -1057,80 +1046,35 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     // ---- the spans: the stream start, then every distinct position found
     std::vector<fl_span> spans;
     std::vector<uint64_t> cand;
-    std::vector<uint32_t> cand_off(n_chunks + 1, 0), sp_first(elig.size() + 1, 0);
-    {
-        size_t k = 0;
-        for (uint32_t i = 0; i < n_chunks; i++) {
-            cand_off[i] = (uint32_t)cand.size();
-            if (k < elig.size() && elig[k] == i) {
-                fl_span s0;
-                s0.start_bit = 0;
-                s0.wp = 0;
-                s0.stream = i;
-                s0.first = 1;
-                s0.prev = FP_NO_SPAN;
-                s0.live = 0;
-                spans.push_back(s0);
-                uint64_t last = 0;
-                for (uint32_t j = pt_first[k]; j < pt_first[k + 1]; j++) {
-                    if (found[j] == ~0ull || found[j] <= last) continue;  // (ascending: the targets are)
-                    last = found[j];
-                    fl_span s1 = s0;
-                    s1.start_bit = found[j];
-                    s1.first = 0;
-                    spans.push_back(s1);
-                    cand.push_back(found[j]);
-                }
-                k++;
-                sp_first[k] = (uint32_t)spans.size();
-            }
-        }
-        cand_off[n_chunks] = (uint32_t)cand.size();
-    }
+    std::vector<uint32_t> cand_off, sp_first;
+    fl_span_build(n_chunks, elig, pt_first, found.data(), spans, cand, cand_off, sp_first);
     const uint32_t nsp = (uint32_t)spans.size();
     if (dbg) fprintf(stderr, "[spans] %zu streams, %u scan points, %u spans\n", elig.size(), npts, nsp);
     if (nsp == (uint32_t)elig.size()) return 0;  // nothing to cut
-    if ((rc = ensure(h, h->sp_spans, sizeof(fl_span) * nsp))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_res, sizeof(fl_span_res) * 2 * nsp))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_cand, sizeof(uint64_t) * (cand.size() + 1)))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_candoff, sizeof(uint32_t) * (n_chunks + 1)))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_tails, (size_t)FP_TAIL * nsp))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_tails_b, (size_t)FP_TAIL * nsp))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
+    if (!room(h, h->sp_spans, sizeof(fl_span) * nsp) || !room(h, h->sp_res, sizeof(fl_span_res) * 2 * nsp) ||
+        !room(h, h->sp_cand, sizeof(uint64_t) * (cand.size() + 1)) || !room(h, h->sp_candoff, sizeof(uint32_t) * (n_chunks + 1)) ||
+        !room(h, h->sp_tails, (size_t)FP_TAIL * nsp) || !room(h, h->sp_tails_b, (size_t)FP_TAIL * nsp))
+        return 0;
     if (hipMemcpyAsync(h->sp_spans.p, spans.data(), sizeof(fl_span) * nsp, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     if (!cand.empty() && hipMemcpyAsync(h->sp_cand.p, cand.data(), sizeof(uint64_t) * cand.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     if (hipMemcpyAsync(h->sp_candoff.p, cand_off.data(), sizeof(uint32_t) * (n_chunks + 1), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    // ---- the pool run A writes to: what the streams can hold (at most 32 bytes for every compressed one: beyond
-    // that a stream goes the old way), two pieces of slack per span
-    fl_span_pool pool;
-    {
-        uint64_t bytes = 0;
-        for (uint32_t ci : elig) bytes += std::min<uint64_t>(chunks[ci].out_cap, 32ull * chunks[ci].in_len);
-        const uint64_t pieces = ((bytes >> FP_PIECE_LOG) + 2ull * nsp + 1) * ((twin || sym) ? 2 : 1);
-        // (a pool the device cannot give -- callers who reserve the worst case for gigabytes of input: the old way.  The
-        // pool is a second copy of the decoded output: it may take a quarter of what is free next to what it holds
-        // already, never more than 16 GiB, so that an allocator that shares the device -- PyTorch's -- is not starved.)
-        if (pieces * FP_PIECE > (16ull << 30)) return 0;
-        if (pieces * FP_PIECE + 16 > h->sp_pool.cap) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-                (void)hipGetLastError();
-                return 0;
-            }
-            if (pieces * FP_PIECE + 16 > h->sp_pool.cap + free_b / 4) return 0;
-        }
-        if (ensure(h, h->sp_pool, (size_t)(pieces * FP_PIECE + 16))) {
-            (void)hipGetLastError();  // (not this call's failure)
+    // ---- the pool run A writes to (span_plan.h, fl_span_pool_pieces): it may take a quarter of what is free next to what
+    // it holds already
+    const uint64_t pieces = fl_span_pool_pieces(chunks.data(), elig, nsp, both);
+    if (pieces * FP_PIECE > FL_SPAN_POOL_MAX) return 0;
+    if (pieces * FP_PIECE + 16 > h->sp_pool.cap) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+            (void)hipGetLastError();
             return 0;
         }
-        if ((rc = ensure(h, h->sp_pooltab, sizeof(uint32_t) * (size_t)FP_MAX_PIECES * nsp * 2))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-        if ((rc = ensure(h, h->sp_poolctl, 16))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-        if (hipMemsetAsync(h->sp_poolctl.p, 0, 16, st) != hipSuccess) return -1;
-        pool.base = (uint8_t*)h->sp_pool.p;
-        pool.next = (uint32_t*)h->sp_poolctl.p;
-        pool.tab = (uint32_t*)h->sp_pooltab.p;
-        pool.pieces = (uint32_t)pieces;
-        pool.pad = 0;
+        if (pieces * FP_PIECE + 16 > h->sp_pool.cap + free_b / 4) return 0;
     }
+    if (!room(h, h->sp_pool, (size_t)(pieces * FP_PIECE + 16)) || !room(h, h->sp_pooltab, sizeof(uint32_t) * (size_t)FP_MAX_PIECES * nsp * 2) ||
+        !room(h, h->sp_poolctl, 16))
+        return 0;
+    if (hipMemsetAsync(h->sp_poolctl.p, 0, 16, st) != hipSuccess) return -1;
+    const fl_span_pool pool = {(uint8_t*)h->sp_pool.p, /*next*/ (uint32_t*)h->sp_poolctl.p, /*tab*/ (uint32_t*)h->sp_pooltab.p, (uint32_t)pieces, /*pad*/ 0};
     // ---- run A
     {
         ProfScope ps(h, K_INFLATE_SPAN);
@@ -1139,7 +1083,6 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
                            (const uint32_t*)h->sp_candoff.p, (uint8_t*)h->sp_tails.p, 0u, pool, twin && !sym ? nsp : 0u,
                            (uint8_t*)h->sp_tails_b.p, sym ? nsp : 0u);
     }
-    const bool both = twin || sym;  // what run B makes is there after this launch
     std::vector<fl_span_res> r1(nsp), r2(nsp);
     if (hipMemcpyAsync(r1.data(), h->sp_res.p, sizeof(fl_span_res) * nsp, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
     if (twin && !sym && hipMemcpyAsync(r2.data(), (const fl_span_res*)h->sp_res.p + nsp, sizeof(fl_span_res) * nsp, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
@@ -1147,117 +1090,33 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     if (sym) r2 = r1;  // (one decode: what it says holds for both planes)
     if (dbg) fprintf(stderr, "[spans] %.3f ms: sync 2 done\n", since());
     // ---- the chain of every stream
-    struct StreamPlan {
-        bool ok = false;
-        std::vector<uint32_t> chain;
-        uint64_t total = 0, end_bit = 0;
-    };
-    std::vector<StreamPlan> plans(elig.size());
+    std::vector<fl_span_chain> plans(elig.size());
     bool any = false;
     for (size_t k = 0; k < elig.size(); k++) {
-        StreamPlan& pl = plans[k];
-        const fl_chunk& c = chunks[elig[k]];
-        uint32_t cur = sp_first[k];
-        uint64_t acc = 0;
-        bool ok = true;
-        for (uint32_t guard = 0; guard <= nsp; guard++) {
-            const fl_span_res& r = r1[cur];
-            if (dbg && guard < 6) fprintf(stderr, "[spans] pass 1 span %u: start %llu status %u end %llu out %llu final %u\n", cur, (unsigned long long)spans[cur].start_bit, r.status, (unsigned long long)r.end_bit, (unsigned long long)r.out_len, r.final_seen);
-            if (r.status != 0) { ok = false; break; }
-            // (run B of a twin launch does not know where its span starts: a distance that reaches before the start of
-            // the OUTPUT -- possible in the first 32 KiB only -- is the old path's to find)
-            if (both && !spans[cur].first && r.uses_hist && acc < FP_TAIL) { ok = false; break; }
-            spans[cur].live = 1;
-            spans[cur].wp = acc;
-            spans[cur].prev = pl.chain.empty() ? FP_NO_SPAN : pl.chain.back();
-            pl.chain.push_back(cur);
-            acc += r.out_len;
-            if (acc > c.out_cap) { ok = false; break; }
-            if (r.final_seen) { pl.end_bit = r.end_bit; break; }
-            // the span that starts where this one stopped
-            uint32_t lo = sp_first[k] + 1, hi = sp_first[k + 1];
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (spans[mid].start_bit < r.end_bit) lo = mid + 1; else hi = mid;
-            }
-            if (lo >= sp_first[k + 1] || spans[lo].start_bit != r.end_bit || lo <= cur) { ok = false; break; }
-            cur = lo;
-        }
-        if (ok && (pl.chain.empty() || !r1[pl.chain.back()].final_seen)) ok = false;
-        if (dbg) fprintf(stderr, "[spans] stream %u: chain of %zu spans, %llu bytes, ok=%d\n", elig[k], pl.chain.size(), (unsigned long long)acc, (int)ok);
-        if (dbg)
-            for (uint32_t j = sp_first[k]; j < sp_first[k + 1]; j++)
-                fprintf(stderr, "[spans]    span %u: start %llu status %u (0: decoded; else why it gave up) end %llu out %llu final %u blocks / pieces %u\n", j,
-                        (unsigned long long)spans[j].start_bit, r1[j].status, (unsigned long long)r1[j].end_bit, (unsigned long long)r1[j].out_len, r1[j].final_seen, r1[j].n_pieces);
-        if (!ok)
-            for (uint32_t j = sp_first[k]; j < sp_first[k + 1]; j++) spans[j].live = 0;
-        pl.ok = ok;
-        pl.total = acc;
-        any = any || ok;
+        plans[k] = fl_span_follow_chain(spans.data(), r1.data(), sp_first[k], sp_first[k + 1], chunks[elig[k]].out_cap, both);
+        if (dbg) span_debug_chain(plans[k], elig[k], spans, r1, sp_first[k], sp_first[k + 1]);
+        any = any || plans[k].ok;
     }
     if (!any) return 0;
     // ---- run B with the other filling of the history (live spans, in place), the true tails, k_span_fix
-    std::vector<uint32_t> chain_all, chain_off(1, 0);
-    for (size_t k = 0; k < elig.size(); k++) {
-        if (plans[k].ok) chain_all.insert(chain_all.end(), plans[k].chain.begin(), plans[k].chain.end());
-        chain_off.push_back((uint32_t)chain_all.size());
-    }
-    // (streams without a single copy that reaches before its span -- huffman-only, store-only ones -- need neither)
-    bool uses_hist = false;
-    for (uint32_t si : chain_all) uses_hist = uses_hist || r1[si].uses_hist != 0;
+    const fl_span_fix_plan fp = fl_span_fix_items(chunks.data(), elig, spans.data(), r1.data(), plans, nsp, both);
+    const bool uses_hist = fp.uses_hist;
     if (dbg) fprintf(stderr, "[spans] history needed: %d\n", (int)uses_hist);
-    std::vector<fl_fix_item> items;
-    std::vector<uint32_t> item_first(elig.size() + 1, 0);
-    for (size_t k = 0; k < elig.size(); k++) {
-        if (plans[k].ok) {
-            for (uint32_t si : plans[k].chain) {
-                const uint64_t n = r1[si].out_len;
-                for (uint64_t o = 0; o < n; o += FP_FIX_ITEM) {
-                    fl_fix_item it;
-                    it.dst = chunks[elig[k]].out_off + spans[si].wp + o;
-                    it.span = si;
-                    it.local = (uint32_t)o;
-                    it.len = (uint32_t)std::min<uint64_t>(FP_FIX_ITEM, n - o);
-                    it.kind = spans[si].first ? 0u : uses_hist ? (both ? 3u : 2u) : 1u;
-                    it.prev = spans[si].prev;
-                    it.pad = both ? nsp : 0u;
-                    items.push_back(it);
-                }
-                // (a workgroup of k_span_fix takes FP_FIX_WAVES items of ONE span: empty ones fill the last)
-                while (items.size() % FP_FIX_WAVES) {
-                    fl_fix_item it = items.back();
-                    it.local = 0;
-                    it.len = 0;
-                    items.push_back(it);
-                }
-            }
-        }
-        item_first[k + 1] = (uint32_t)items.size();
-    }
-    const uint32_t n_items = (uint32_t)items.size();
-    if ((rc = ensure(h, h->sp_chain, sizeof(uint32_t) * (chain_all.size() + 1)))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_chainoff, sizeof(uint32_t) * chain_off.size()))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_items, sizeof(fl_fix_item) * ((size_t)n_items + 1)))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-    if ((rc = ensure(h, h->sp_part, sizeof(uint32_t) * 2 * ((size_t)n_items + 1)))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
+    const uint32_t n_items = (uint32_t)fp.items.size();
+    if (!room(h, h->sp_chain, sizeof(uint32_t) * (fp.chain_all.size() + 1)) || !room(h, h->sp_chainoff, sizeof(uint32_t) * fp.chain_off.size()) ||
+        !room(h, h->sp_items, sizeof(fl_fix_item) * ((size_t)n_items + 1)) || !room(h, h->sp_part, sizeof(uint32_t) * 2 * ((size_t)n_items + 1)))
+        return 0;
     if (hipMemcpyAsync(h->sp_spans.p, spans.data(), sizeof(fl_span) * nsp, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    if (hipMemcpyAsync(h->sp_chain.p, chain_all.data(), sizeof(uint32_t) * chain_all.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    if (hipMemcpyAsync(h->sp_chainoff.p, chain_off.data(), sizeof(uint32_t) * chain_off.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    // (symbols) every span's place in its chain, the longest chain, room for two sets of tails in symbols; no room: span after span
-    std::vector<uint32_t> chain_pos;
-    uint32_t longest = 0;
+    if (hipMemcpyAsync(h->sp_chain.p, fp.chain_all.data(), sizeof(uint32_t) * fp.chain_all.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    if (hipMemcpyAsync(h->sp_chainoff.p, fp.chain_off.data(), sizeof(uint32_t) * fp.chain_off.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    // (symbols) every span's place in its chain, room for two sets of tails in symbols; no room: span after span
     bool rs_ok = false;
     if (sym && uses_hist) {
-        for (size_t k = 0; k < elig.size(); k++)
-            if (plans[k].ok) {
-                for (uint32_t j = 0; j < plans[k].chain.size(); j++) chain_pos.push_back(j);
-                longest = std::max<uint32_t>(longest, (uint32_t)plans[k].chain.size());
-            }
-        rs_ok = !chain_pos.empty() && ensure(h, h->sp_chainpos, sizeof(uint32_t) * chain_pos.size()) == 0 &&
-                ensure(h, h->sp_rs, 2 * chain_pos.size() * (size_t)FP_TAIL * sizeof(uint16_t)) == 0;
-        if (!rs_ok) (void)hipGetLastError();
-        if (rs_ok && hipMemcpyAsync(h->sp_chainpos.p, chain_pos.data(), sizeof(uint32_t) * chain_pos.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        rs_ok = !fp.chain_pos.empty() && room(h, h->sp_chainpos, sizeof(uint32_t) * fp.chain_pos.size()) &&
+                room(h, h->sp_rs, 2 * fp.chain_pos.size() * (size_t)FP_TAIL * sizeof(uint16_t));
+        if (rs_ok && hipMemcpyAsync(h->sp_chainpos.p, fp.chain_pos.data(), sizeof(uint32_t) * fp.chain_pos.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     }
-    if (n_items && hipMemcpyAsync(h->sp_items.p, items.data(), sizeof(fl_fix_item) * n_items, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    if (n_items && hipMemcpyAsync(h->sp_items.p, fp.items.data(), sizeof(fl_fix_item) * n_items, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     {
         ProfScope ps(h, K_INFLATE_SPAN);
         if (uses_hist) {
@@ -1267,13 +1126,13 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
                                    (const uint32_t*)h->sp_candoff.p, (uint8_t*)h->sp_tails_b.p, 1u, pool, 0u, (uint8_t*)nullptr, 0u);
             if (sym && rs_ok) {
                 // the true tails of all spans at once: log2(longest chain) steps (kernels_inflate_par.h, k_span_rs_*)
-                const uint32_t ng = (uint32_t)chain_all.size();
+                const uint32_t ng = (uint32_t)fp.chain_all.size();
                 uint16_t* S0 = (uint16_t*)h->sp_rs.p;
                 uint16_t* S1 = S0 + (size_t)ng * FP_TAIL;
                 const dim3 grid(ng, FP_TAIL / (256 * 8));
                 hipLaunchKernelGGL(k_span_rs_init, grid, dim3(256), 0, st, (const uint32_t*)h->sp_chain.p, (const uint32_t*)h->sp_chainpos.p,
                                    (const uint8_t*)h->sp_tails.p, (const uint8_t*)h->sp_tails_b.p, S0);
-                for (uint32_t D = 1; D < longest; D *= 2) {
+                for (uint32_t D = 1; D < fp.longest; D *= 2) {
                     hipLaunchKernelGGL(k_span_rs_step, grid, dim3(256), 0, st, (const uint32_t*)h->sp_chainpos.p, (const uint16_t*)S0, S1, D);
                     std::swap(S0, S1);
                 }
@@ -1288,18 +1147,14 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
                                (const uint8_t*)h->sp_tails.p, d_out, container, h->crc, (uint32_t*)h->sp_part.p);
     }
     // the footers of the streams whose chain is whole (one small gather instead of a copy per stream)
-    const uint32_t flen = container == 1 ? 8u : container == 2 ? 4u : 0u;
+    const uint32_t flen = fl_span_footer_len(container);
     const uint32_t nel = (uint32_t)elig.size();
     std::vector<uint64_t> foot_off(nel, ~0ull);
     std::vector<uint8_t> foot(8 * (size_t)nel, 0);
     if (flen) {
-        for (size_t k = 0; k < elig.size(); k++) {
-            const fl_chunk& c = chunks[elig[k]];
-            const uint64_t fb = (plans[k].end_bit + 7) >> 3;
-            if (plans[k].ok && fb + flen <= c.in_len) foot_off[k] = c.in_off + fb;
-        }
-        if ((rc = ensure(h, h->sp_footoff, sizeof(uint64_t) * nel))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
-        if ((rc = ensure(h, h->sp_foot, 8 * (size_t)nel))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
+        for (uint32_t k = 0; k < nel; k++)
+            if (const uint64_t at = fl_span_footer_at(plans[k], flen, chunks[elig[k]].in_len); at != ~0ull) foot_off[k] = chunks[elig[k]].in_off + at;
+        if (!room(h, h->sp_footoff, sizeof(uint64_t) * nel) || !room(h, h->sp_foot, 8 * (size_t)nel)) return 0;
         if (hipMemcpyAsync(h->sp_footoff.p, foot_off.data(), sizeof(uint64_t) * nel, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
         hipLaunchKernelGGL(k_span_footers, dim3((nel + 63) / 64), dim3(64), 0, st, d_in, (const uint64_t*)h->sp_footoff.p, nel, flen,
                            (uint8_t*)h->sp_foot.p);
@@ -1311,60 +1166,30 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
     if (hipStreamSynchronize(st) != hipSuccess) return -1;
     if (dbg) fprintf(stderr, "[spans] %.3f ms: sync 3 done\n", since());
     // ---- run B as run A, the checksum, the footer
-    const uint32_t pow_piece = fl_crc_xpow8n(h->crc.xpow8, FP_FIX_ITEM);
-    int done = 0;
+    const uint32_t pow_item = fl_crc_xpow8n(h->crc.xpow8, FP_FIX_ITEM);
     std::vector<fl_span_fin> fin;
-    for (size_t k = 0; k < elig.size(); k++) {
-        StreamPlan& pl = plans[k];
+    for (uint32_t k = 0; k < nel; k++) {
+        const fl_span_chain& pl = plans[k];
         if (!pl.ok) continue;
-        fl_chunk& c = chunks[elig[k]];
-        bool ok = true;
-        for (size_t j = 0; j < pl.chain.size() && ok && uses_hist; j++) {
-            const uint32_t si = pl.chain[j];
-            if (spans[si].first) continue;  // (run A was final)
+        const fl_span_verdict v = fl_span_verify(pl, spans.data(), r1.data(), r2.data(), uses_hist, part.data() + 2 * (size_t)fp.item_first[k],
+                                                 fp.item_first[k + 1] - fp.item_first[k], container, h->crc.xpow8, pow_item, &foot[8 * (size_t)k],
+                                                 chunks[elig[k]].in_len);
+        if (dbg && v.bad_b != ~0u) {
+            const uint32_t si = pl.chain[v.bad_b];
             const fl_span_res &a = r1[si], &b = r2[si];
-            if (b.status != 0 || b.out_len != a.out_len || b.end_bit != a.end_bit) ok = false;
-            if (dbg && !ok) fprintf(stderr, "[spans] span %u (chain %zu): run B status %u len %llu/%llu end %llu/%llu\n", si, j, b.status, (unsigned long long)b.out_len, (unsigned long long)a.out_len, (unsigned long long)b.end_bit, (unsigned long long)a.end_bit);
+            fprintf(stderr, "[spans] span %u (chain %zu): run B status %u len %llu/%llu end %llu/%llu\n", si, (size_t)v.bad_b, b.status, (unsigned long long)b.out_len, (unsigned long long)a.out_len, (unsigned long long)b.end_bit, (unsigned long long)a.end_bit);
         }
-        uint32_t crc = 0;
-        uint64_t adA = 0, adB = 0;  // Adler-32 with a = b = 0 start
-        for (uint32_t q = item_first[k]; q < item_first[k + 1] && ok; q++) {
-            const uint32_t pc = part[2 * (size_t)q], plen = part[2 * (size_t)q + 1];
-            if (container == 1) {
-                crc = fl_crc_mulmod(crc, plen == FP_FIX_ITEM ? pow_piece : fl_crc_xpow8n(h->crc.xpow8, plen)) ^ pc;
-            } else if (container == 2) {
-                adB = (adB + adA * plen + (pc >> 16)) % 65521u;
-                adA = (adA + (pc & 0xffff)) % 65521u;
-            }
-        }
-        const uint64_t fb = (pl.end_bit + 7) >> 3;
-        if (ok && fb + flen > c.in_len) ok = false;  // truncated: the old way names it
-        if (ok && flen) {
-            const uint8_t* f = &foot[8 * k];
-            if (container == 1) {
-                const uint32_t fcrc = (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) | ((uint32_t)f[3] << 24);
-                const uint32_t fsz = (uint32_t)f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) | ((uint32_t)f[7] << 24);
-                ok = fcrc == crc && fsz == (uint32_t)pl.total;
-            } else {
-                const uint32_t a = (uint32_t)((1 + adA) % 65521u);
-                const uint32_t b = (uint32_t)((pl.total % 65521u + adB) % 65521u);
-                const uint32_t fad = ((uint32_t)f[0] << 24) | ((uint32_t)f[1] << 16) | ((uint32_t)f[2] << 8) | (uint32_t)f[3];
-                ok = fad == ((b << 16) | a);
-            }
-        }
-        if (dbg) fprintf(stderr, "[spans] stream %u after k_span_fix: ok=%d crc %08x\n", elig[k], (int)ok, crc);
-        if (!ok) continue;  // (the bytes written so far are written again by the kernels that follow)
-        fl_span_fin fi;
-        fi.total = pl.total;
-        fi.used = fb + flen;
-        fi.chunk = elig[k];
-        fi.pad = 0;
-        fin.push_back(fi);
-        c.skip = 1;
-        done++;
+        if (dbg) fprintf(stderr, "[spans] stream %u after k_span_fix: ok=%d crc %08x\n", elig[k], (int)v.ok, v.crc);
+        if (!v.ok) continue;  // (the bytes written so far are written again by the kernels that follow)
+        fin.push_back(fl_span_fin{pl.total, v.used, /*chunk*/ elig[k], /*pad*/ 0});
+        chunks[elig[k]].skip = 1;
     }
+    const int done = (int)fin.size();
     if (done) {
-        if ((rc = ensure(h, h->sp_fin, sizeof(fl_span_fin) * fin.size()))) { (void)hipGetLastError(); return 0; }  // (no room: the old way)
+        if (!room(h, h->sp_fin, sizeof(fl_span_fin) * fin.size())) {
+            for (const fl_span_fin& f : fin) chunks[f.chunk].skip = 0;  // (nobody wrote their results: the old way does)
+            return 0;
+        }
         if (hipMemcpyAsync(h->sp_fin.p, fin.data(), sizeof(fl_span_fin) * fin.size(), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
         hipLaunchKernelGGL(k_span_finish, dim3(((uint32_t)fin.size() + 63) / 64), dim3(64), 0, st, (const fl_span_fin*)h->sp_fin.p,
                            (uint32_t)fin.size(), d_status, d_outlen, d_consumed);
@@ -1424,24 +1249,17 @@ int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::ve
         s0.stream = elig[k];
         s0.first = 1;
         spans.push_back(s0);
-        uint64_t last = 0;
-        for (uint32_t j = pt_first[k]; j < pt_first[k + 1]; j++) {
-            if (found[j] == ~0ull || found[j] <= last || found[j] >= elens[k] * 8) continue;  // (ascending: the targets are)
-            last = found[j];
-            spans.back().stop_bit = found[j];
-            fl_size_span s1 = s0;
-            s1.start_bit = found[j];
-            s1.first = 0;
-            spans.push_back(s1);
+        s0.first = 0;
+        for (uint64_t p : fl_cut_positions(found.data(), pt_first[k], pt_first[k + 1], elens[k] * 8)) {
+            spans.back().stop_bit = p;
+            s0.start_bit = p;
+            spans.push_back(s0);
         }
         sp_first[k + 1] = (uint32_t)spans.size();
     }
     const uint32_t nsp = (uint32_t)spans.size();
     if (nsp == (uint32_t)elig.size()) return 0;  // nothing to cut
-    if (ensure(h, h->sz_spans, sizeof(fl_size_span) * nsp) || ensure(h, h->sz_recs, sizeof(fl_size_rec) * nsp)) {
-        (void)hipGetLastError();
-        return 0;
-    }
+    if (!room(h, h->sz_spans, sizeof(fl_size_span) * nsp) || !room(h, h->sz_recs, sizeof(fl_size_rec) * nsp)) return 0;
     if (hipMemcpyAsync(h->sz_spans.p, spans.data(), sizeof(fl_size_span) * nsp, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     {
         ProfScope ps(h, K_INFLATE_SIZE_SPAN);
@@ -1459,17 +1277,11 @@ int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::ve
         uint64_t size = 0, used = 0;
         int32_t stt = 0;
         if (!fl_size_follow_chain(spans.data() + a, recs.data() + a, b - a, &size, &stt, &used)) continue;
-        fl_span_fin f;
-        f.total = size;
-        f.used = used;
-        f.chunk = elig[k];
-        f.pad = 0;
-        fin.push_back(f);
+        fin.push_back(fl_span_fin{size, used, /*chunk*/ elig[k], /*pad*/ 0});
         chunks[elig[k]].skip = 1;
     }
     if (!fin.empty()) {
-        if (ensure(h, h->sp_fin, sizeof(fl_span_fin) * fin.size())) {
-            (void)hipGetLastError();
+        if (!room(h, h->sp_fin, sizeof(fl_span_fin) * fin.size())) {
             for (const fl_span_fin& f : fin) chunks[f.chunk].skip = 0;
             return 0;
         }
@@ -1818,21 +1630,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
         }
     } ms_guard{h};
     if (out_hi > out_lo && !planning) {
-        if (!h->s_ms) {  // (all three or none)
-            hipStream_t s = nullptr;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e0, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess) {
-                h->s_ms = s;
-                h->ms_ev0 = e0;
-                h->ms_ev1 = e1;
-            } else {
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-                if (s) (void)hipStreamDestroy(s);
-                (void)hipGetLastError();
-            }
-        }
+        if (!h->s_ms) (void)side_stream(h->s_ms, h->ms_ev0, h->ms_ev1);
         if (h->s_ms && !h->knobs.memset_inline) {
             HIP_OK(h, hipEventRecord(h->ms_ev0, st));
             HIP_OK(h, hipStreamWaitEvent(h->s_ms, h->ms_ev0, 0));
@@ -1940,22 +1738,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     const bool planned_run = pl && pl->ready;
     bool two = ((pinned_passes && (size_t)n_chunks > pass_limit) || (planned_run && pl->passes.size() > 1)) && mode >= 4 && !fs && !h->knobs.one_stream;
     for (uint32_t i = 0; two && i < n_chunks; i++) two = chunks[i].in_len <= FLATE_HIP_MAX_LZ_CHUNK;
-    if (two && !h->s_c2) {
-        hipStream_t s2 = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e0, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess) {
-            h->s_c2 = s2;
-            h->c2_ev0 = e0;
-            h->c2_ev1 = e1;
-        } else {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            if (s2) (void)hipStreamDestroy(s2);
-            (void)hipGetLastError();
-            two = false;
-        }
-    }
+    if (two && !h->s_c2) two = side_stream(h->s_c2, h->c2_ev0, h->c2_ev1);
     // The two streams' workspace is TWO slices of every per-pass buffer, each as large as the largest pass (pass_plan.h: the
     // merged tail, not the sub-batch size); pass k runs on stream k & 1 in slice k & 1.  Passes k and k + 2 run in order on one
     // stream, so pass k + 2 reuses pass k's bytes only after pass k's last kernel.  The other streams that touch a slice:

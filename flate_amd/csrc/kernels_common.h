@@ -87,25 +87,7 @@ __device__ __forceinline__ uint32_t fl_load_u32_unaligned(const uint8_t* p) {
     return __builtin_amdgcn_alignbyte(hi, lo, sh);
 }
 
-// ---- CRC-32 (IEEE, reflected) polynomial arithmetic, as zlib's multmodp ----
-#define FL_CRC_POLY 0xEDB88320u
-__device__ __host__ inline uint32_t fl_crc_mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; i++) {
-        if (a & 0x80000000u) p ^= b;
-        a <<= 1;
-        b = (b & 1) ? ((b >> 1) ^ FL_CRC_POLY) : (b >> 1);
-    }
-    return p;
-}
-// x^(8*n) mod P using the table of x^(8*2^j), j < 32, for every 64-bit n: x has order 2^32 - 1 modulo P, so
-// x^(8 * 2^(j + 32)) = x^(8 * 2^j) and bit j + 32 of n takes entry j again
-__device__ __host__ inline uint32_t fl_crc_xpow8n(const uint32_t* xpow8, uint64_t n) {
-    uint32_t p = 0x80000000u;
-    for (int j = 0; n; j++, n >>= 1)
-        if (n & 1) p = fl_crc_mulmod(xpow8[j & 31], p);
-    return p;
-}
+// (CRC-32 polynomial arithmetic: fl_crc_mulmod / fl_crc_xpow8n, flate_common.h)
 
 // ---- OR `nbits` (<= 64-ish, value already masked) bits into the output bit stream ----
 __device__ __forceinline__ void fl_atomic_or_bits(uint32_t* out32, uint64_t bitpos, uint64_t v, uint32_t nbits) {

@@ -38,6 +38,7 @@
 #pragma once
 #include "kernels_inflate.h"
 #include "kernels_lz.h"
+#include "span_plan.h"
 
 #define FL_PAR_REDO (-1)  // status written for streams that k_inflate has to decode
 
@@ -290,29 +291,8 @@ __device__ __forceinline__ uint32_t fp_tok_len(uint32_t t) { return (t >> 31) ? 
 // The pieces are folded and the footer is checked by the host.  Anything irregular: the stream is decoded again by
 // k_inflate_par / k_inflate, as before.  inflate.zig:220-239 is serial per stream; this is the same function, with
 // the one thing a span cannot know kept symbolic until it is known.
-struct fl_span {
-    uint64_t start_bit;  // of its first block header, from the first byte of the stream (first span: unused)
-    uint64_t wp;         // run B: offset of its first output byte in the stream's output (run A: 0)
-    uint32_t stream;     // chunk index
-    uint32_t first;      // 1: starts at the stream's first byte (container header)
-    uint32_t prev;       // the span before it in the chain (its tail is this span's history), ~0u: none
-    uint32_t live;       // run B: on the chain
-};
-struct fl_span_res {
-    uint64_t end_bit;  // where it stopped: the start of another span, or the bit behind the final block
-    uint64_t out_len;
-    uint32_t status;      // 0: decoded; anything else: the stream goes the old way
-    uint32_t final_seen;  // stopped behind the final block
-    uint32_t uses_hist;   // a copy reaches before the span's first byte
-    uint32_t n_pieces;    // run A: pieces of the pool taken
-};
-#define FP_TAIL 32768u
-#define FP_NO_SPAN 0xffffffffu
-// Run A of a span that is not the first of its stream does not know where its bytes belong: they go to PIECES of a
-// pool, taken as the span grows (one atomic per 64 KiB); k_span_fix moves them to their place.
-#define FP_PIECE_LOG 16u
-#define FP_PIECE (1u << FP_PIECE_LOG)
-#define FP_MAX_PIECES 2048u  // per span: 128 MiB of output
+// The records (fl_span, fl_span_res, fl_scan_point, fl_fix_item, fl_span_fin), their constants and the host's side of
+// all this are in span_plan.h.
 struct fl_span_pool {
     uint8_t* base;    // pieces of FP_PIECE bytes
     uint32_t* next;   // [0]: pieces handed out so far
@@ -1129,10 +1109,6 @@ __device__ __forceinline__ void fp_body(const uint8_t* __restrict__ in, const fl
 // Steps 1 and 2 may refuse a header the parser would take (the span before just gets longer) but what they pass
 // is only a candidate until step 3 agrees.  A position that parses by accident inside compressed data is
 // harmless too: no span lands on it, its span is dead.
-struct fl_scan_point {
-    uint64_t from_bit, limit_bit;  // search [from_bit, limit_bit)
-    uint32_t stream, pad;
-};
 #ifndef FP_SCAN_WIN_BITS
 #define FP_SCAN_WIN_BITS 131072u  // (64 / 128 / 256 Kibit: 170 MiB of text 1.04 / 0.73 / 0.82 ms, config #4's stream 2.5 / 1.85 / 1.4: step 2 costs its slowest lane once per window)
 #endif
@@ -1521,18 +1497,6 @@ __global__ __launch_bounds__(FP_THREADS, 1) void k_inflate_span(const uint8_t* _
 struct __attribute__((aligned(4))) fl_u4a {  // four words at a word-aligned address
     uint32_t x[4];
 };
-#define FP_FIX_LANE 1024u                 // bytes per lane
-#define FP_FIX_ITEM (64u * FP_FIX_LANE)   // ... and item (a wave): a piece of the pool (16 KiB items, 256 bytes a lane: 0.84 -> 1.21 ms)
-#define FP_FIX_WAVES 4u                   // items per workgroup: of ONE span, whose history (the true tail before it) they share in LDS
-struct fl_fix_item {
-    uint64_t dst;    // of the item's first byte in the output buffer
-    uint32_t span;   // whose pieces
-    uint32_t local;  // offset of the item in the span's output (a multiple of FP_FIX_ITEM)
-    uint32_t len;    // <= FP_FIX_ITEM
-    uint32_t kind;
-    uint32_t prev;   // kind 2: the span before it in the chain
-    uint32_t pad;
-};
 __global__ __launch_bounds__(64 * FP_FIX_WAVES) void k_span_fix(const fl_fix_item* __restrict__ items, fl_span_pool pool,
                                                  const uint8_t* __restrict__ tails, uint8_t* out, int container,
                                                  fl_crc_consts cc, uint32_t* __restrict__ part /* [n_items][2] */) {
@@ -1696,10 +1660,6 @@ __global__ __launch_bounds__(64) void k_span_footers(const uint8_t* __restrict__
     if (i >= n || off[i] == ~0ull) return;
     for (uint32_t b = 0; b < flen; b++) out[8 * (uint64_t)i + b] = in[off[i] + b];
 }
-struct fl_span_fin {
-    uint64_t total, used;
-    uint32_t chunk, pad;
-};
 __global__ __launch_bounds__(64) void k_span_finish(const fl_span_fin* __restrict__ fin, uint32_t n,
                                                     int32_t* __restrict__ status, uint64_t* __restrict__ out_len,
                                                     uint64_t* __restrict__ consumed) {
