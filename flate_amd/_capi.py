@@ -19,6 +19,10 @@ DEFLATE_REPAIR_Q1 = 1          # flate_hip_set_flags
 ST_REFERENCE_Q1_STREAM = 102   # compress status: the reference's bytes, which do not inflate to the input (include/flate_hip.h)
 ST_NEED_INPUT = 104            # inflater feed: all input absorbed, member not finished
 ST_NEED_OUTPUT = 105           # inflater feed: the output slot is full
+ST_NEED_DICT = 106             # a zlib stream with FDICT set, and the stream was given no dictionary
+ST_WRONG_DICT = 107            # ... its DICTID is not the Adler-32 of the dictionary it was given
+INFLATER_NEED_DICT = 2         # inflater create flag: report ST_NEED_DICT instead of ignoring FDICT
+DICT_NONE = 0xFFFFFFFF         # dict_of entry: this stream has no dictionary
 FEED_MORE, FEED_FLUSH, FEED_FINISH = 0, 1, 2  # deflater feed ops
 
 # every symbol include/flate_hip.h declares
@@ -38,6 +42,7 @@ SYMBOLS = [
     "flate_hip_debug_inflate_paths",
     "flate_hip_decompressed_sizes", "flate_hip_debug_size_paths",
     "flate_hip_decompress_members", "flate_hip_debug_member_paths",
+    "flate_hip_decompress_batch_dict", "flate_hip_inflater_set_dictionary",
 ]
 
 
@@ -164,6 +169,11 @@ def lib():
     L.flate_hip_decompress_members.restype = C.c_int
     L.flate_hip_debug_member_paths.argtypes = [vp, u64p]
     L.flate_hip_debug_member_paths.restype = C.c_int
+    L.flate_hip_decompress_batch_dict.argtypes = [vp, vp, u64p, C.c_uint32, C.c_int, C.c_int, vp, u64p, u64p, i32p, u64p,
+                                                  C.c_int, vp, u64p, C.c_uint32, vp]
+    L.flate_hip_decompress_batch_dict.restype = C.c_int
+    L.flate_hip_inflater_set_dictionary.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_int, vp]
+    L.flate_hip_inflater_set_dictionary.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.flate_hip_debug_tokens.restype = C.c_int64
     _lib = L

@@ -76,6 +76,8 @@ InvalidDynamicBlockHeader = _mk("InvalidDynamicBlockHeader", 14)
 OutputTooSmall = _mk("OutputTooSmall", 100)
 ChunkTooLarge = _mk("ChunkTooLarge", 101)
 InvalidState = _mk("InvalidState", 103)  # inflate.zig:303 (a host-side state, no device status)
+NeedDict = _mk("NeedDict", 106)    # a zlib stream with FDICT set, decoded without zdict= (not in the reference)
+WrongDict = _mk("WrongDict", 107)  # ... its DICTID is not the Adler-32 of zdict
 
 
 class ReferenceQ1StreamWarning(UserWarning):
@@ -88,7 +90,7 @@ class ReferenceQ1StreamWarning(UserWarning):
 _ERRORS = {e.status: e for e in (
     EndOfStream, BadGzipHeader, BadZlibHeader, WrongGzipChecksum, WrongGzipSize, WrongZlibChecksum, InvalidCode,
     OversubscribedHuffmanTree, IncompleteHuffmanTree, MissingEndOfBlockCode, InvalidMatch, InvalidBlockType,
-    WrongStoredBlockNlen, InvalidDynamicBlockHeader, OutputTooSmall, ChunkTooLarge)}
+    WrongStoredBlockNlen, InvalidDynamicBlockHeader, OutputTooSmall, ChunkTooLarge, NeedDict, WrongDict)}
 
 
 def raise_for_status(code):
@@ -315,6 +317,15 @@ class _PieceCompressor:
         self._d.close()
 
 
+def _zdict_for(container, zdict):
+    """zdict= of the decompress functions: None, or the preset dictionary as bytes (raw and zlib only)"""
+    if zdict is None:
+        return None
+    if container == _capi.GZIP:
+        raise ValueError("gzip has no preset dictionaries: zdict= is for flate and zlib")
+    return bytes(zdict)
+
+
 class _Decompressor:
     """Inflate (inflate.zig:43-355) seen from the caller.  The reader is consumed as far as the current stream
     needs it, in steps that double: a decode that runs out of input (EndOfStream) while the reader still has
@@ -324,9 +335,10 @@ class _Decompressor:
     CHUNK = 65536  # the reference hands out at most its 64 KiB ring per next() (inflate.zig:322-336)
     FIRST_READ = 1 << 16
 
-    def __init__(self, container, reader, engine=None, flags=0):
+    def __init__(self, container, reader, engine=None, flags=0, zdict=None):
         self._container, self._flags = container, flags
         self._eng = engine or default_engine()
+        self._zdict = _zdict_for(container, zdict)  # a preset dictionary, for every stream of the reader
         self._set_input(reader)
         self._out = None   # decoded bytes of the current stream
         self._rp = 0
@@ -361,7 +373,11 @@ class _Decompressor:
             data = bytes(self._in[self._pos:])
             cap = max(1 << 16, len(data) * 64)
             while True:
-                outs, st, used = self._eng.decompress_many([data], self._container, self._flags, caps=[cap])
+                if self._zdict is None:
+                    outs, st, used = self._eng.decompress_many([data], self._container, self._flags, caps=[cap])
+                else:
+                    outs, st, used = self._eng.decompress_many_dict([data], [self._zdict], None, self._container,
+                                                                    self._flags, caps=[cap])
                 if st[0] == 100 and cap < (1 << 34):
                     cap *= 8
                     continue
@@ -433,15 +449,22 @@ class _PieceDecompressor:
 
     CHUNK = 65536
 
-    def __init__(self, container, reader, engine=None, flags=0, piece=1 << 20):
+    def __init__(self, container, reader, engine=None, flags=0, piece=1 << 20, zdict=None):
         if int(piece) < 1:
             raise ValueError("piece must be at least 1 byte")
         self._container, self._piece = container, int(piece)
         self._eng = engine or default_engine()
+        self._zdict = _zdict_for(container, zdict)
         self._slot = min(max(self.CHUNK, 4 * self._piece), 64 << 20)  # output of one feed (handed out 64 KiB at a time)
         self._inf = self._eng.inflater(1, container, flags)
         self._set_input(reader)
         self._clear()
+        self._give_dict()
+
+    def _give_dict(self):
+        """the preset dictionary again: the device drops it with every reset"""
+        if self._zdict is not None and not self._inf.set_dictionary([0], self._zdict)[0]:
+            raise InvalidState("the resumable inflater did not take its dictionary")
 
     def _set_input(self, reader):
         if isinstance(reader, (bytes, bytearray, memoryview)):
@@ -507,6 +530,7 @@ class _PieceDecompressor:
             raise InvalidState("reset() before the end of the stream")
         self._inf.reset([0])
         self._clear()
+        self._give_dict()
 
     def more_input(self):
         """True when input is left after the stream just decoded (a further concatenated member).  Meant for the end of
@@ -523,6 +547,7 @@ class _PieceDecompressor:
         self._set_input(new_reader)
         self._inf.reset([0])
         self._clear()
+        self._give_dict()
 
 
 class _Simple:
@@ -570,15 +595,17 @@ class ContainerModule:
 
     Compressor = compressor
 
-    def decompress(self, reader, writer, engine=None):
-        self.decompressor(reader, engine).decompress(writer)
+    def decompress(self, reader, writer, engine=None, *, zdict=None):
+        self.decompressor(reader, engine, zdict=zdict).decompress(writer)
 
-    def decompressor(self, reader, engine=None, *, piece=None):
+    def decompressor(self, reader, engine=None, *, piece=None, zdict=None):
         """piece=None: the whole-stream decompressor.  piece=N: bounded memory -- the reader is read N bytes at a time
-        and decoded by a resumable inflater as it arrives (_PieceDecompressor)."""
+        and decoded by a resumable inflater as it arrives (_PieceDecompressor).  zdict=: the preset dictionary the
+        stream was compressed against (zlib.compressobj(zdict=...)); flate and zlib only, gzip raises ValueError."""
+        zdict = _zdict_for(self._container, zdict)  # (gzip: ValueError, before an engine is made)
         if piece is None:
-            return _Decompressor(self._container, reader, engine)
-        return _PieceDecompressor(self._container, reader, engine, piece=piece)
+            return _Decompressor(self._container, reader, engine, zdict=zdict)
+        return _PieceDecompressor(self._container, reader, engine, piece=piece, zdict=zdict)
 
     Decompressor = decompressor
 

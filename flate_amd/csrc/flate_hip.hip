@@ -68,6 +68,7 @@ enum KernelId {
     K_GATHER,
     K_INFLATER,
     K_DEFLATER,
+    K_INFLATE_DICT,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
@@ -76,7 +77,7 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_offsets",  "k_encode",    "k_inflate",  "k_inflate_par", "k_span_scan", "k_inflate_span",
                                            "k_inflate_size", "k_inflate_size_span",
                                            "k_member_scan", "k_member_chain", "k_member_walk", "k_member_pack", "k_member_fold",
-                                           "k_gather", "k_inflater", "k_deflater"};
+                                           "k_gather", "k_inflater", "k_deflater", "k_inflate_dict"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -172,6 +173,8 @@ struct flate_hip_ctx {
     // streams k_inflate_par was launched for, and (counted on the device by k_inflate) those it handed on
     uint64_t dbg_span_taken = 0, dbg_span_done = 0, dbg_par_taken = 0;
     DevBuf dbg_par_handed;
+    // flate_hip_decompress_batch_dict: the table of the call's dictionaries, and for host callers their bytes and dict_of
+    DevBuf dc_tab, dc_bytes, dc_of;
     // flate_hip_decompressed_sizes: the span table and the span records of its long streams, and for
     // flate_hip_debug_size_paths the streams of the last call whose size came from a closed chain / from one wave
     DevBuf sz_spans, sz_recs;
@@ -1321,6 +1324,8 @@ const char* flate_hip_status_name(int s) {
         case 102: return "ReferenceQ1Stream";
         case 104: return "NeedInput";
         case 105: return "NeedOutput";
+        case 106: return "NeedDict";
+        case 107: return "WrongDict";
         default: return "Unknown";
     }
 }
@@ -1373,7 +1378,7 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->tokens, &h->ntok, &h->cflag, &h->links, &h->wchunks, &h->swins, &h->wexit, &h->shard_sz, &h->tiles, &h->segs, &h->pieces, &h->fpts, &h->zones, &h->nsorted, &h->jmp,
                       &h->exitmap, &h->entry, &h->segtok, &h->tokbase, &h->bound, &h->sgroups, &h->sgroup0, &h->gmap, &h->gentry,
                       &h->sblocks, &h->st_in, &h->st_out, &h->st_inoff, &h->st_outlen, &h->st_status,
-                      &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed})
+                      &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed, &h->dc_tab, &h->dc_bytes, &h->dc_of})
         if (b->p) (void)hipFree(b->p);
     h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
@@ -2159,6 +2164,118 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
     rc = fetch_offsets(h, out_off, n_chunks, memkind, hout);
     if (rc) return rc;
     return decompress_core(h, in, hin, n_chunks, container, flags, out, hout, out_len, status, consumed, memkind);
+}
+
+// Streams with preset dictionaries: every stream by k_inflate_dict, a wave each (no spans, no workgroup-per-stream kernel).
+int flate_hip_decompress_batch_dict(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
+                                    int container, int flags, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                                    int32_t* status, uint64_t* consumed, int memkind, const uint8_t* dict,
+                                    const uint64_t* dict_off, uint32_t n_dicts, const uint32_t* dict_of) {
+    if (!h || !in_off || !out_off || !out_len || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (container == FLATE_HIP_GZIP || (n_dicts && !dict_off) || (!dict_of && n_dicts != 1)) return FLATE_HIP_E_INVALID_ARG;
+    if (n_chunks == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    std::vector<uint64_t> hin, hout, hdoff(1, 0);
+    std::vector<uint32_t> hof;
+    int rc;
+    if ((rc = fetch_offsets(h, in_off, n_chunks, memkind, hin))) return rc;
+    if ((rc = fetch_offsets(h, out_off, n_chunks, memkind, hout))) return rc;
+    if (n_dicts && (rc = fetch_offsets(h, dict_off, n_dicts, memkind, hdoff))) return rc;
+    if (dict_of) {
+        hof.resize(n_chunks);
+        if (memkind == FLATE_HIP_MEM_HOST) {
+            memcpy(hof.data(), dict_of, sizeof(uint32_t) * n_chunks);
+        } else {
+            HIP_OK(h, hipMemcpyAsync(hof.data(), dict_of, sizeof(uint32_t) * n_chunks, hipMemcpyDeviceToHost, st));
+            HIP_OK(h, hipStreamSynchronize(st));
+        }
+    }
+    if (!fl_dict_args_ok(container, hdoff.data(), n_dicts, dict_of ? hof.data() : nullptr, dict_of != nullptr, n_chunks))
+        return FLATE_HIP_E_INVALID_ARG;
+    const uint64_t d_lo = hdoff[0], d_hi = hdoff[n_dicts];
+    if (d_hi > d_lo && !dict) return FLATE_HIP_E_INVALID_ARG;
+    std::vector<fl_dict_ent> tab;
+    fl_dict_table(hdoff.data(), n_dicts, tab);
+
+    const uint64_t in_lo = hin[0], in_hi = hin[n_chunks], out_lo = hout[0], out_hi = hout[n_chunks];
+    const uint8_t* d_in = in;
+    const uint8_t* d_dict = dict;
+    const uint32_t* d_of = dict_of;
+    uint8_t* d_out = out;
+    uint64_t* d_outlen = out_len;
+    int32_t* d_status = status;
+    uint64_t* d_consumed = consumed;
+    uint64_t in_shift = 0, out_shift = 0;
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16)) || (rc = ensure(h, h->st_out, (out_hi - out_lo) + 16)) ||
+            (rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_chunks)) || (rc = ensure(h, h->st_status, sizeof(int32_t) * n_chunks)) ||
+            (rc = ensure(h, h->st_consumed, sizeof(uint64_t) * n_chunks)) || (rc = ensure(h, h->dc_bytes, (d_hi - d_lo) + 16)) ||
+            (rc = ensure(h, h->dc_of, sizeof(uint32_t) * n_chunks)))
+            return rc;
+        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+        if (d_hi > d_lo) HIP_OK(h, hipMemcpyAsync(h->dc_bytes.p, dict + d_lo, d_hi - d_lo, hipMemcpyHostToDevice, st));
+        if (dict_of) HIP_OK(h, hipMemcpyAsync(h->dc_of.p, hof.data(), sizeof(uint32_t) * n_chunks, hipMemcpyHostToDevice, st));
+        if (out_hi > out_lo) HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, out_hi - out_lo, st));  // (as decompress_core)
+        d_in = (const uint8_t*)h->st_in.p;
+        d_dict = (const uint8_t*)h->dc_bytes.p;
+        d_of = dict_of ? (const uint32_t*)h->dc_of.p : nullptr;
+        d_out = (uint8_t*)h->st_out.p;
+        d_outlen = (uint64_t*)h->st_outlen.p;
+        d_status = (int32_t*)h->st_status.p;
+        d_consumed = (uint64_t*)h->st_consumed.p;
+        in_shift = in_lo;
+        out_shift = out_lo;
+        for (fl_dict_ent& e : tab) {
+            e.start -= d_lo;
+            e.end -= d_lo;
+        }
+    }
+    std::vector<fl_chunk> chunks(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; i++) {
+        fl_chunk& c = chunks[i];
+        const uint64_t len = hin[i + 1] - hin[i];
+        if (len > 0xfffffff0ull) return FLATE_HIP_E_INVALID_ARG;
+        c.in_off = hin[i] - in_shift;
+        c.out_off = hout[i] - out_shift;
+        c.out_cap = hout[i + 1] - hout[i];
+        c.in_len = (uint32_t)len;
+        c.first_block = 0;
+        c.n_blocks = 0;
+        c.skip = 0;
+    }
+    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n_chunks)) || (rc = ensure(h, h->dc_tab, sizeof(fl_dict_ent) * (n_dicts + 1))))
+        return rc;
+    HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
+    if (n_dicts) HIP_OK(h, hipMemcpyAsync(h->dc_tab.p, tab.data(), sizeof(fl_dict_ent) * n_dicts, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));  // (the tables are on the host's stack)
+    h->dbg_span_taken = h->dbg_span_done = h->dbg_par_taken = 0;  // (flate_hip_debug_inflate_paths: every stream by the wave-per-stream kernel)
+    if (h->dbg_par_handed.p) HIP_OK(h, hipMemsetAsync(h->dbg_par_handed.p, 0, sizeof(uint32_t), st));
+    fl_dict_ent* d_tab = (fl_dict_ent*)h->dc_tab.p;
+    if (n_dicts) hipLaunchKernelGGL(k_dict_adler, dim3(n_dicts), dim3(64), 0, st, d_dict, d_tab, n_dicts);
+    const bool large = h->knobs.inflate_ring >= 0 ? h->knobs.inflate_ring >= (int64_t)FL_INF_RING_LARGE : n_chunks <= 4u * 256u;  // (as decompress_core)
+    {
+        ProfScope ps(h, K_INFLATE_DICT);
+        if (large)
+            hipLaunchKernelGGL(k_inflate_dict<FL_INF_RING_LARGE>, dim3(n_chunks), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p,
+                               container, flags, h->crc, d_out, d_outlen, d_status, d_consumed, d_dict, (const fl_dict_ent*)d_tab, d_of);
+        else
+            hipLaunchKernelGGL(k_inflate_dict<FL_INF_RING_SMALL>, dim3(n_chunks), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p,
+                               container, flags, h->crc, d_out, d_outlen, d_status, d_consumed, d_dict, (const fl_dict_ent*)d_tab, d_of);
+    }
+    HIP_OK(h, hipGetLastError());
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_chunks, hipMemcpyDeviceToHost, st));
+        if (consumed) HIP_OK(h, hipMemcpyAsync(consumed, d_consumed, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+        if ((rc = copy_out_host(h, d_out, d_outlen, n_chunks, hout, out_shift, out, out_len))) return rc;
+    } else if (h->sync) {
+        HIP_OK(h, hipStreamSynchronize(st));
+    }
+    return FLATE_HIP_OK;
 }
 
 }  // extern "C"
@@ -3147,6 +3264,8 @@ struct flate_hip_inflater {
     void* sess = nullptr;  // FL_RS_STRIDE bytes per stream: state, carry, input window, history, output window
     // host-memory feeds: the pieces, offsets and slots on the device
     DevBuf in, in_off, fin, out, out_off, out_len, consumed, status, which;
+    DevBuf dict, dict_tab, applied;  // flate_hip_inflater_set_dictionary: a host caller's dictionary, its table entry, the answers
+    bool dict_aware = false;  // feeds run k_inflater_dict: created with FLATE_HIP_INFLATER_NEED_DICT, or a dictionary was ever set
     std::vector<uint8_t> host_out;  // host-memory feeds of many streams: the slots on their way to the caller
 };
 
@@ -3184,7 +3303,8 @@ int flate_hip_inflater_create(flate_hip_handle h, uint32_t n_streams, int contai
     flate_hip_inflater* s = new flate_hip_inflater();
     s->n = n_streams;
     s->container = container;
-    s->flags = flags & FLATE_HIP_INFLATE_STRICT_Q6;
+    s->flags = flags & (FLATE_HIP_INFLATE_STRICT_Q6 | (container != FLATE_HIP_GZIP ? FLATE_HIP_INFLATER_NEED_DICT : 0));
+    s->dict_aware = (s->flags & FLATE_HIP_INFLATER_NEED_DICT) != 0;
     if (hipMalloc(&s->sess, (size_t)n_streams * FL_RS_STRIDE) != hipSuccess) {
         h->last_error = "hipMalloc of the inflater's state (" + std::to_string((size_t)n_streams * FL_RS_STRIDE) + " bytes) failed";
         delete s;
@@ -3205,7 +3325,8 @@ int flate_hip_inflater_destroy(flate_hip_handle h, flate_hip_inflater_t s) {
     if (!h || !s) return FLATE_HIP_E_INVALID_ARG;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (DevBuf* b : {&s->in, &s->in_off, &s->fin, &s->out, &s->out_off, &s->out_len, &s->consumed, &s->status, &s->which})
+    for (DevBuf* b : {&s->in, &s->in_off, &s->fin, &s->out, &s->out_off, &s->out_len, &s->consumed, &s->status, &s->which,
+                      &s->dict, &s->dict_tab, &s->applied})
         if (b->p) (void)hipFree(b->p);
     (void)hipFree(s->sess);
     delete s;
@@ -3227,6 +3348,45 @@ int flate_hip_inflater_reset(flate_hip_handle h, flate_hip_inflater_t s, const u
     return FLATE_HIP_OK;
 }
 
+int flate_hip_inflater_set_dictionary(flate_hip_handle h, flate_hip_inflater_t s, const uint32_t* which, uint32_t n_which,
+                                      const uint8_t* dict, uint64_t dict_len, int memkind, uint8_t* applied) {
+    if (!h || !s || (n_which && !which) || (dict_len && !dict)) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (s->container == FLATE_HIP_GZIP) return FLATE_HIP_E_INVALID_ARG;
+    for (uint32_t k = 0; k < n_which; k++)
+        if (which[k] >= s->n) return FLATE_HIP_E_INVALID_ARG;
+    if (n_which == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    int rc;
+    if ((rc = inflater_buf(h, s->which, sizeof(uint32_t) * n_which)) || (rc = inflater_buf(h, s->applied, n_which)) ||
+        (rc = inflater_buf(h, s->dict_tab, sizeof(fl_dict_ent))))
+        return rc;
+    const uint8_t* d_dict = dict;
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        if ((rc = inflater_buf(h, s->dict, dict_len + 16))) return rc;
+        if (dict_len) HIP_OK(h, hipMemcpyAsync(s->dict.p, dict, dict_len, hipMemcpyHostToDevice, st));
+        d_dict = (const uint8_t*)s->dict.p;
+    }
+    const uint64_t off[2] = {0, dict_len};
+    std::vector<fl_dict_ent> tab;
+    fl_dict_table(off, 1, tab);
+    HIP_OK(h, hipMemcpyAsync(s->which.p, which, sizeof(uint32_t) * n_which, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(s->dict_tab.p, tab.data(), sizeof(fl_dict_ent), hipMemcpyHostToDevice, st));
+    s->dict_aware = true;
+    hipLaunchKernelGGL(k_dict_adler, dim3(1), dim3(64), 0, st, d_dict, (fl_dict_ent*)s->dict_tab.p, 1u);
+    hipLaunchKernelGGL(k_inflater_set_dict, dim3(n_which), dim3(64), 0, st, (uint8_t*)s->sess, (const uint32_t*)s->which.p, n_which,
+                       s->n, s->container, d_dict, (const fl_dict_ent*)s->dict_tab.p, (uint8_t*)s->applied.p);
+    HIP_OK(h, hipGetLastError());
+    if (applied) HIP_OK(h, hipMemcpyAsync(applied, s->applied.p, n_which, hipMemcpyDeviceToHost, st));
+    // `which` and the table are pageable host memory: their copies have been taken when hipMemcpyAsync returns, and the
+    // kernels are ordered behind them (as in flate_hip_inflater_reset), so nothing here has to wait for them.  A host
+    // caller's dictionary may be pinned, so the call waits for its copy; a device caller's dictionary is read in stream
+    // order, and without `applied` and with set_sync(0) the call returns before that.
+    if (applied || memkind == FLATE_HIP_MEM_HOST || h->sync) HIP_OK(h, hipStreamSynchronize(st));
+    return FLATE_HIP_OK;
+}
+
 int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const uint8_t* in, const uint64_t* in_off,
                             const uint8_t* final_, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
                             uint64_t* consumed, int32_t* status, int memkind) {
@@ -3237,8 +3397,8 @@ int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const ui
     const uint32_t n = s->n;
     if (memkind == FLATE_HIP_MEM_DEVICE) {  // enqueue only: the kernel reads the offsets itself
         ProfScope ps(h, K_INFLATER);
-        hipLaunchKernelGGL(k_inflater, dim3(n), dim3(64), 0, st, in, in_off, final_, out, out_off, out_len, consumed, status,
-                           (uint8_t*)s->sess, s->container, s->flags, h->crc);
+        hipLaunchKernelGGL(s->dict_aware ? k_inflater_dict : k_inflater, dim3(n), dim3(64), 0, st, in, in_off, final_, out, out_off,
+                           out_len, consumed, status, (uint8_t*)s->sess, s->container, s->flags, h->crc);
         HIP_OK(h, hipGetLastError());
         if (h->sync) HIP_OK(h, hipStreamSynchronize(st));
         return FLATE_HIP_OK;
@@ -3268,7 +3428,7 @@ int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const ui
     HIP_OK(h, hipMemcpyAsync(s->fin.p, final_, n, hipMemcpyHostToDevice, st));
     {
         ProfScope ps(h, K_INFLATER);
-        hipLaunchKernelGGL(k_inflater, dim3(n), dim3(64), 0, st, (const uint8_t*)s->in.p, (const uint64_t*)s->in_off.p,
+        hipLaunchKernelGGL(s->dict_aware ? k_inflater_dict : k_inflater, dim3(n), dim3(64), 0, st, (const uint8_t*)s->in.p, (const uint64_t*)s->in_off.p,
                            (const uint8_t*)s->fin.p, (uint8_t*)s->out.p, (const uint64_t*)s->out_off.p,
                            (uint64_t*)s->out_len.p, (uint64_t*)s->consumed.p, (int32_t*)s->status.p, (uint8_t*)s->sess,
                            s->container, s->flags, h->crc);

@@ -12,7 +12,12 @@
 // copied together; anything unusual takes the symbol-at-a-time path, which keeps the reference's order of errors.
 // Output goes to an LDS ring and leaves in coalesced 8-byte stores; the checksum is spread over the 64 lanes.
 // Throughput comes from many streams in flight: 20 per CU with the 2 KiB ring (6.5 KB of LDS per stream).
+// Streams with a preset dictionary (k_inflate_dict, k_inflater_dict after k_inflater_set_dict) decode with history that is
+// not in the output slot: the ring is seeded with the dictionary's tail, far copies pick their source per lane.
 #pragma once
+#include <type_traits>
+
+#include "dict_plan.h"
 #include "kernels_common.h"
 
 // canonical decoder tables (huffman_decoder.zig:71-153); NSYM = alphabet capacity
@@ -357,6 +362,7 @@ __device__ __forceinline__ uint32_t fl_rev_bits(uint32_t v, uint32_t n) { return
 // ring[(k + bias) & (RING - 1)], bias = low 3 bits of the output address, so that an 8-byte
 // aligned global address is an 8-byte aligned ring index.
 struct fl_inf_out {
+    enum { DICT = 0 };
     uint8_t* out;
     FL_LDS uint8_t* ring;
     uint64_t cap;
@@ -367,6 +373,27 @@ struct fl_inf_out {
     uint32_t rmask;     // ring size - 1
     uint32_t near_max;  // ring size - 260
 };
+// ... of a stream with a preset dictionary: the last hist_len (<= 32768) bytes in front of dict_end are the output
+// bytes -hist_len .. -1.  The ring is seeded with them (fl_inf_seed_ring), so near copies do not know; a far copy picks
+// its source per lane: an output position below 0 is read from the dictionary, anything else from the slot.
+struct fl_inf_out_dict : fl_inf_out {
+    enum { DICT = 1 };
+    const uint8_t* dict_end;
+    uint32_t hist_len;
+};
+// bytes of history in front of output byte 0
+template <class O>
+__device__ __forceinline__ uint32_t fl_inf_hist(const O& o) {
+    if constexpr (O::DICT) return o.hist_len;
+    return 0u;
+}
+// the dictionary's last min(hist_len, ring) bytes at the ring positions of output bytes -1, -2, ...
+__device__ __forceinline__ void fl_inf_seed_ring(fl_inf_out_dict& o, uint32_t lane) {
+    const uint32_t nr = min(o.hist_len, o.rmask + 1);
+    fl_lds_order();
+    for (uint32_t k = lane; k < nr; k += 64) o.ring[(o.bias - 1u - k) & o.rmask] = o.dict_end[-1 - (int32_t)k];
+    fl_lds_order();
+}
 
 // store output bytes [flushed, upto) from the ring
 __device__ __forceinline__ void fl_inf_flush(fl_inf_out& o, uint64_t upto, uint32_t lane) {
@@ -401,8 +428,9 @@ __device__ __forceinline__ void fl_inf_advance(fl_inf_out& o, uint32_t lane) {
 // CircularBuffer.zig:44-75, spread over the wave.  Near matches copy inside the LDS ring; far
 // ones read the output buffer: that far back everything has been flushed (see fl_inf_advance),
 // the wave only has to wait for those stores if they are younger than the last wait.
-__device__ __forceinline__ int fl_inf_match(fl_inf_out& o, uint32_t length, uint32_t distance, uint32_t lane) {
-    if (o.wp < distance || length < 3 || length > 258 || distance < 1 || distance > 32768) return 11;
+template <class O>
+__device__ __forceinline__ int fl_inf_match(O& o, uint32_t length, uint32_t distance, uint32_t lane) {
+    if (o.wp + fl_inf_hist(o) < distance || length < 3 || length > 258 || distance < 1 || distance > 32768) return 11;
     if (o.wp + length > o.cap) return 100;
     const uint32_t vp = (uint32_t)o.wp + o.bias;  // ring positions only need the low bits
     if (distance <= o.near_max) {
@@ -418,6 +446,18 @@ __device__ __forceinline__ int fl_inf_match(fl_inf_out& o, uint32_t length, uint
             if (i < length) o.ring[(vp + i) & o.rmask] = (uint8_t)byte;
             fl_lds_order();
         }
+    } else if constexpr (O::DICT) {
+        const int64_t s0 = (int64_t)o.wp - (int64_t)distance;  // output position of the first source byte
+        if (s0 + (int64_t)length > (int64_t)o.fenced) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            o.fenced = o.flushed;
+        }
+        for (uint32_t i0 = 0; i0 < length; i0 += 64) {
+            const uint32_t i = i0 + lane;
+            const int64_t sp = s0 + (int64_t)i;
+            if (i < length) o.ring[(vp + i) & o.rmask] = (sp < 0 ? o.dict_end : (const uint8_t*)o.out)[sp];
+        }
+        fl_lds_order();
     } else {
         if (o.wp - distance + length > o.fenced) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -446,6 +486,9 @@ __device__ __forceinline__ int fl_inf_literal(fl_inf_out& o, uint32_t byte, uint
 // (kernels_inflate_size.h) adds their number up.
 __device__ __forceinline__ int fl_sink_literal(fl_inf_out& o, uint32_t byte, uint32_t lane) { return fl_inf_literal(o, byte, lane); }
 __device__ __forceinline__ int fl_sink_match(fl_inf_out& o, uint32_t length, uint32_t distance, uint32_t lane) {
+    return fl_inf_match(o, length, distance, lane);
+}
+__device__ __forceinline__ int fl_sink_match(fl_inf_out_dict& o, uint32_t length, uint32_t distance, uint32_t lane) {
     return fl_inf_match(o, length, distance, lane);
 }
 
@@ -819,7 +862,8 @@ __device__ __forceinline__ void fl_round_chain(fl_round& t) {
     }
 }
 
-__device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, fl_inf_out& o, uint32_t lane) {
+template <class O>
+__device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, O& o, uint32_t lane) {
     FL_T0();
     const uint64_t left0 = fl_uni64((uint64_t)r.left);
     fl_round t;
@@ -831,7 +875,9 @@ __device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_w
     // (32-bit halves: there is no 64-bit scalar compare, and the vector one costs a constant pair and the compare each time)
     const uint64_t roomq = cap - wp0;
     const uint32_t room0 = (uint32_t)(roomq >> 32) ? 0x40000000u : min((uint32_t)roomq, 0x40000000u);  // output bytes left (saturated)
-    const uint32_t hist0 = (uint32_t)(wp0 >> 32) ? 0x100000u : min((uint32_t)wp0, 0x100000u);  // bytes a match may reach back (saturated)
+    // bytes a match may reach back (saturated); a dictionary counts, so that matches into it stay in the rounds
+    const uint64_t histq = wp0 + fl_inf_hist(o);
+    const uint32_t hist0 = (uint32_t)(histq >> 32) ? 0x100000u : min((uint32_t)histq, 0x100000u);
     int32_t unfl0 = (int32_t)fl_uni((uint32_t)(wp0 - o.flushed));                // unflushed bytes = unfl0 + adv
     const uint32_t bias = fl_uni(o.bias), rmask = fl_uni(o.rmask), near_max = fl_uni(o.near_max);
     const uint32_t vp0 = (uint32_t)wp0 + bias;  // ring position of output byte wp0 (low bits)
@@ -904,7 +950,12 @@ __device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_w
                     fgap = (uint32_t)(gapq >> 32) ? 0xfffffff0u - 512u : min((uint32_t)gapq, 0xfffffff0u - 512u);
                 }
                 // a far match reaches back 32768 at most: uniform base, unsigned 32-bit lane offset
-                if (FL_INV(m_far)) byte = far_base[b + 32768u - v];
+                if constexpr (O::DICT) {  // output position wp0 + b - v: below 0 it is a byte of the dictionary
+                    const uint8_t* src = wp0 + b < v ? o.dict_end + ((int64_t)wp0 - 32768) : far_base;
+                    if (FL_INV(m_far)) byte = src[b + 32768u - v];
+                } else {
+                    if (FL_INV(m_far)) byte = far_base[b + 32768u - v];
+                }
             }
             if (FL_INV(m_copy & ~m_far)) byte = o.ring[(vp0 + b - v) & rmask];
             fl_lds_order();
@@ -960,6 +1011,18 @@ __device__ __forceinline__ int fl_inf_fast_round(fl_bitr& r, FL_LDS fl_inflate_w
                     done += chunk;
                     have += chunk;
                 } while (done < length_m);
+            } else if constexpr (O::DICT) {
+                const int64_t s0 = (int64_t)(wp0 + moff) - (int64_t)distance;
+                if (s0 + (int64_t)length_m > (int64_t)fl_uni64(o.fenced)) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    o.fenced = o.flushed;
+                }
+                for (uint32_t i0 = 0; i0 < length_m; i0 += 64) {
+                    const uint32_t i = i0 + lane;
+                    const int64_t sp = s0 + (int64_t)i;
+                    if (i < length_m) o.ring[(vp + i) & rmask] = (sp < 0 ? o.dict_end : (const uint8_t*)o.out)[sp];
+                }
+                fl_lds_order();
             } else {
                 const uint64_t wp = wp0 + moff;
                 if (wp - distance + length_m > fl_uni64(o.fenced)) {
@@ -1043,7 +1106,8 @@ __device__ __forceinline__ int fl_inf_dynamic_symbol(fl_bitr& r, FL_LDS fl_infla
     return 0;
 }
 
-__device__ __forceinline__ int fl_inf_dynamic(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, fl_inf_out& o, uint32_t lane) {
+template <class O>
+__device__ __forceinline__ int fl_inf_dynamic(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, O& o, uint32_t lane) {
     for (;;) {
         if (r.left >= FL_INF_FAST_MIN_BITS) {
             int rc;
@@ -1154,13 +1218,46 @@ __device__ __forceinline__ uint32_t fl_wave_adler32(const uint8_t* p, uint64_t n
 #ifndef FL_INF_ATTR
 #define FL_INF_ATTR
 #endif
-template <uint32_t RING>
-__global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1)) void k_inflate(const uint8_t* __restrict__ in, const fl_chunk* __restrict__ chunks,
+// A zlib header in front of a stream that may name a preset dictionary (RFC 1950 2.2): with FDICT set the four bytes
+// behind FLG are the big-endian Adler-32 of the dictionary the encoder was given.  ent: the stream's dictionary, null:
+// it has none.  use = 1 when the dictionary is the stream's history; with FDICT clear it is not (zlib's inflate too
+// ignores the dictionary it was handed for such a stream).
+#define FL_ST_NEED_DICT 106
+#define FL_ST_WRONG_DICT 107
+__device__ __forceinline__ int fl_inf_header_zdict(fl_bitr& r, const fl_dict_ent* ent, uint32_t& use) {
+    uint32_t cm, cinfo, flg, id;
+    use = 0;
+    FL_TRY(fl_br_read(r, 4, cm));
+    FL_TRY(fl_br_read(r, 4, cinfo));
+    FL_TRY(fl_br_read(r, 8, flg));
+    if (cm != 8 || cinfo > 7) return 3;
+    if (!(flg & 0x20)) return 0;
+    FL_TRY(fl_br_read(r, 32, id));
+    if (!ent) return FL_ST_NEED_DICT;
+    if (__builtin_bswap32(id) != ent->adler) return FL_ST_WRONG_DICT;
+    use = 1;
+    return 0;
+}
+
+// The Adler-32 of every dictionary of a call, a wave each (the DICTID comparison of every stream reads it from the table).
+__global__ __launch_bounds__(64) void k_dict_adler(const uint8_t* __restrict__ dict, fl_dict_ent* __restrict__ tab, uint32_t n) {
+    const uint32_t d = blockIdx.x, lane = threadIdx.x;
+    if (d >= n) return;
+    const uint32_t a = fl_wave_adler32(dict + tab[d].start, tab[d].end - tab[d].start, lane);
+    if (lane == 0) tab[d].adler = a;
+}
+
+// One stream by one wave: k_inflate (DICT false) and k_inflate_dict, whose streams have preset dictionaries: dtab is the
+// call's table of dictionaries, dict their bytes, dict_of the dictionary of every stream (null: all use number 0).
+template <uint32_t RING, bool DICT>
+__device__ __forceinline__ void fl_inflate_stream(const uint8_t* __restrict__ in, const fl_chunk* __restrict__ chunks,
                                                 int container, int flags, fl_crc_consts cc,
                                                 uint8_t* __restrict__ out, uint64_t* __restrict__ out_len,
                                                 int32_t* __restrict__ status, uint64_t* __restrict__ consumed,
                                                 const int32_t* redo_only /* non-null: only streams marked -1 */,
-                                                uint32_t* handed_on /* with redo_only: counts the streams taken here */) {
+                                                uint32_t* handed_on /* with redo_only: counts the streams taken here */,
+                                                const uint8_t* __restrict__ dict, const fl_dict_ent* __restrict__ dtab,
+                                                const uint32_t* __restrict__ dict_of) {
     __shared__ fl_inflate_ws16 ws_mem;
     __shared__ alignas(8) uint8_t ring_mem[RING];
 #ifdef FL_INF_PAD  // tuning build: fewer streams per CU
@@ -1184,7 +1281,7 @@ __global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1))
     r.lane = lane;
     r.inring = (FL_LDS uint32_t*)inring_mem;
     fl_br_seek(r, 0);
-    fl_inf_out o;
+    typename std::conditional<DICT, fl_inf_out_dict, fl_inf_out>::type o;
     o.out = out + ck.out_off;
     o.ring = (FL_LDS uint8_t*)ring_mem;
     o.rmask = RING - 1;
@@ -1195,7 +1292,19 @@ __global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1))
     o.fenced = 0;
     o.bias = (uint32_t)((uintptr_t)o.out & 7);
 
-    int rc = (int)fl_uni((uint32_t)fl_inf_header(r, container));
+    int rc;
+    if constexpr (DICT) {
+        const uint32_t d = dict_of ? dict_of[c] : 0u;
+        const fl_dict_ent* ent = d == FL_DICT_NONE ? nullptr : dtab + d;
+        uint32_t use = ent ? 1u : 0u;
+        rc = container == 2 ? (int)fl_uni((uint32_t)fl_inf_header_zdict(r, ent, use)) : 0;
+        use = fl_uni(use);
+        o.dict_end = dict + (use ? ent->end : 0);
+        o.hist_len = use ? ent->hist_len : 0u;
+        if (rc == 0) fl_inf_seed_ring(o, lane);
+    } else {
+        rc = (int)fl_uni((uint32_t)fl_inf_header(r, container));
+    }
     while (rc == 0) {  // inflate.zig:251-280
         uint32_t bfinal, btype;
         if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 1, bfinal)))) break;
@@ -1243,6 +1352,26 @@ __global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1))
         if (consumed) consumed[c] = fl_br_consumed(r);
     }
 }
+template <uint32_t RING>
+__global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1)) void k_inflate(const uint8_t* __restrict__ in, const fl_chunk* __restrict__ chunks,
+                                                int container, int flags, fl_crc_consts cc,
+                                                uint8_t* __restrict__ out, uint64_t* __restrict__ out_len,
+                                                int32_t* __restrict__ status, uint64_t* __restrict__ consumed,
+                                                const int32_t* redo_only, uint32_t* handed_on) {
+    fl_inflate_stream<RING, false>(in, chunks, container, flags, cc, out, out_len, status, consumed, redo_only, handed_on,
+                                   nullptr, nullptr, nullptr);
+}
+// ... with preset dictionaries (flate_hip_decompress_batch_dict; container 0 or 2)
+template <uint32_t RING>
+__global__ FL_INF_ATTR __launch_bounds__(64, (RING <= 4096u ? FL_INF_WAVES : 1)) void k_inflate_dict(const uint8_t* __restrict__ in, const fl_chunk* __restrict__ chunks,
+                                                int container, int flags, fl_crc_consts cc,
+                                                uint8_t* __restrict__ out, uint64_t* __restrict__ out_len,
+                                                int32_t* __restrict__ status, uint64_t* __restrict__ consumed,
+                                                const uint8_t* __restrict__ dict, const fl_dict_ent* __restrict__ dtab,
+                                                const uint32_t* __restrict__ dict_of) {
+    fl_inflate_stream<RING, true>(in, chunks, container, flags, cc, out, out_len, status, consumed, nullptr, nullptr, dict,
+                                  dtab, dict_of);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Resumable inflate (flate_hip_inflater_*): the decoder above, stopped and restarted at safe points, with its state in
@@ -1286,13 +1415,22 @@ struct fl_rs_state {
     uint32_t carry_len;   // bytes in the carry (stage[FL_RS_CARRY - carry_len, FL_RS_CARRY))
     uint32_t carry_bit;   // bits of the carry's first byte already consumed
     uint32_t hflags;      // gzip FLG | 0x100 when the fixed header was wrong
-    uint32_t hcount;      // gzip FEXTRA bytes left
-    uint32_t pad[6];
+    // gzip: FEXTRA bytes left.  raw and zlib, which have no such field, keep the stream's preset dictionary here, in a word
+    // the decoder carries anyway and reset clears anyway: FL_RS_DICT_LEN = bytes of the dictionary in `hist` in front of
+    // the member's output (k_inflater_set_dict), FL_RS_DICT_SET = the stream has been given one (it may be empty),
+    // FL_RS_DICT_FED = a feed of k_inflater_dict has absorbed input since create / reset.
+    uint32_t hcount;
+    uint32_t dict_id;     // the Adler-32 of that dictionary (all of it); meaningful with FL_RS_DICT_SET
+    uint32_t pad[5];
     uint8_t lens[320];    // code lengths of the current dynamic block (lens layout of fl_inflate_ws16)
 };
 static_assert(sizeof(fl_rs_state) <= FL_RS_STATE, "inflater state");
 
-enum { FL_RS_STOP_IN = 1, FL_RS_STOP_OUT, FL_RS_STOP_FOOT, FL_RS_STOP_END };
+enum { FL_RS_STOP_IN = 1, FL_RS_STOP_OUT, FL_RS_STOP_FOOT, FL_RS_STOP_END, FL_RS_STOP_HIST };
+#define FL_RS_DICT_LEN 0xffffu
+#define FL_RS_DICT_SET 0x10000u
+#define FL_RS_DICT_FED 0x20000u
+#define FL_RS_FLAG_NEED_DICT 2  // create flag: a zlib stream with FDICT on a stream without a dictionary is NeedDict
 
 // one byte of the stream (the container's header and footer are parsed byte by byte)
 __device__ __forceinline__ bool fl_rs_byte(fl_bitr& r, uint32_t& v) {
@@ -1323,9 +1461,11 @@ struct fl_rs_regs {
 
 // Decode from the current safe point until a stop: FL_RS_STOP_IN (the next unit does not finish with the bits staged, and
 // more may follow), FL_RS_STOP_OUT (the output window is full), FL_RS_STOP_FOOT (the last block ended: the caller folds
-// the checksum before the footer is read), FL_RS_STOP_END (the member is complete, or an error).  `safe_left` is r.left at
+// the checksum before the footer is read), FL_RS_STOP_END (the member is complete, or an error), FL_RS_STOP_HIST (the
+// zlib header did not name the stream's dictionary: the caller sets the output up again without it).  `safe_left` is r.left at
 // the start of the unit the decoder stopped in front of.  fin: no input follows what is staged (the reference's
 // EndOfStream model applies).
+template <bool DICT>
 __device__ __forceinline__ int fl_rs_run(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, fl_inf_out& o, fl_rs_regs& s, fl_rs_state* S,
                                       bool fin, int container, int flags, uint32_t lane, int64_t& safe_left) {
 #define FL_RS_ERR(code)                          \
@@ -1380,10 +1520,40 @@ __device__ __forceinline__ int fl_rs_run(fl_bitr& r, FL_LDS fl_inflate_ws16* ws,
                         uint32_t v;
                         if (!fl_rs_byte(r, v)) FL_RS_SHORT();
                         v = fl_uni(v);
-                        if (s.sub == 0) s.hflags = v;
+                        if constexpr (DICT) {
+                            s.hflags |= v << (8 * s.sub);  // CMF, FLG
+                        } else {
+                            if (s.sub == 0) s.hflags = v;
+                        }
                         s.sub++;
                     }
-                    if ((s.hflags & 15) != 8 || (s.hflags >> 4) > 7) FL_RS_ERR(3);
+                    if constexpr (DICT) {  // (FLG lies above CMF)
+                        if ((s.hflags & 15) != 8 || ((s.hflags >> 4) & 15) > 7) FL_RS_ERR(3);
+                    } else {
+                        if ((s.hflags & 15) != 8 || (s.hflags >> 4) > 7) FL_RS_ERR(3);
+                    }
+                    if constexpr (DICT) {
+                        // FDICT (RFC 1950 2.2): DICTID is one more unit, four bytes that may be cut anywhere.
+                        const uint32_t dict_set = s.hcount & FL_RS_DICT_SET;
+                        if ((s.hflags & 0x2000) && (dict_set || (flags & FL_RS_FLAG_NEED_DICT))) {
+                            while (s.sub < 6) {
+                                uint32_t v;
+                                if (!fl_rs_byte(r, v)) FL_RS_SHORT();
+                                s.foot = (s.foot << 8) | fl_uni(v);
+                                s.sub++;
+                            }
+                            const uint32_t id = (uint32_t)s.foot;
+                            s.foot = 0;
+                            if (!dict_set) FL_RS_ERR(FL_ST_NEED_DICT);
+                            if (id != fl_uni(S->dict_id)) FL_RS_ERR(FL_ST_WRONG_DICT);
+                        } else if (s.hcount & FL_RS_DICT_LEN) {  // FDICT clear: the dictionary is not this stream's history
+                            s.hcount &= ~FL_RS_DICT_LEN;
+                            s.sub = 0;
+                            s.phase = FL_RS_BLOCK;
+                            safe_left = r.left;
+                            return FL_RS_STOP_HIST;
+                        }
+                    }
                 }
                 s.sub = 0;
                 s.phase = FL_RS_BLOCK;
@@ -1570,11 +1740,14 @@ __device__ __forceinline__ uint32_t fl_rs_fold(uint32_t check, const uint8_t* p,
 }
 
 // One feed: stream i continues with in[in_off[i], in_off[i + 1]) and writes to out[out_off[i], out_off[i + 1]).
-__global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
-                                                               const uint8_t* __restrict__ final_, uint8_t* __restrict__ out,
-                                                               const uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
-                                                               uint64_t* __restrict__ consumed, int32_t* __restrict__ status,
-                                                               uint8_t* __restrict__ sess, int container, int flags,
+// (DICT: streams may have preset dictionaries -- k_inflater_dict; the plain kernel's code knows nothing of them but the mark
+// that a stream has absorbed input)
+template <bool DICT>
+__device__ __forceinline__ void fl_inflater_feed(const uint8_t* in, const uint64_t* in_off,
+                                                               const uint8_t* final_, uint8_t* out,
+                                                               const uint64_t* out_off, uint64_t* out_len,
+                                                               uint64_t* consumed, int32_t* status,
+                                                               uint8_t* sess, int container, int flags,
                                                                fl_crc_consts cc) {
     __shared__ fl_inflate_ws16 ws_mem;
     __shared__ alignas(8) uint8_t ring_mem[FL_INF_RING_SMALL];
@@ -1635,7 +1808,8 @@ __global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __
         fl_br_resync(r);
         int64_t safe_left = r.left;
         for (;;) {  // output windows
-            const uint64_t H = min(s.total, (uint64_t)FL_RS_HIST);
+            // (a dictionary's tail lies in front of the output)
+            const uint64_t H = min(DICT ? s.total + (s.hcount & FL_RS_DICT_LEN) : s.total, (uint64_t)FL_RS_HIST);
             const bool win_limited = slot - spos > FL_RS_WOUT;
             fl_inf_out o;
             o.out = hist + FL_RS_HIST - H;
@@ -1656,7 +1830,7 @@ __global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __
                 }
                 fl_wave_lds_sync();
             }
-            stop = fl_rs_run(r, ws, o, s, S, fin_w, container, flags, lane, safe_left);
+            stop = fl_rs_run<DICT>(r, ws, o, s, S, fin_w, container, flags, lane, safe_left);
             // this window's output: to the caller's slot, and its last 32 KiB become the history
             fl_inf_flush(o, o.wp, lane);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1668,6 +1842,7 @@ __global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __
                 s.total += P;
                 spos += P;
             }
+            if (DICT && stop == FL_RS_STOP_HIST) continue;
             if (stop == FL_RS_STOP_FOOT) {
                 s.check = fl_rs_fold(s.check, slot_p + folded, spos - folded, container, cc, ws, lane);
                 folded = spos;
@@ -1729,7 +1904,7 @@ __global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __
         S->bfinal = s.bfinal;
         S->stored_left = s.stored_left;
         S->hflags = s.hflags;
-        S->hcount = s.hcount;
+        S->hcount = DICT && used ? s.hcount | FL_RS_DICT_FED : s.hcount;
         S->check = s.check;
         S->status = s.status;
         S->carry_len = carry;
@@ -1740,6 +1915,25 @@ __global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __
                     : s.phase == FL_RS_DONE ? 0
                     : stop == FL_RS_STOP_OUT ? FL_RS_NEED_OUTPUT : FL_RS_NEED_INPUT;
     }
+}
+
+__global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                               const uint8_t* __restrict__ final_, uint8_t* __restrict__ out,
+                                                               const uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                                               uint64_t* __restrict__ consumed, int32_t* __restrict__ status,
+                                                               uint8_t* __restrict__ sess, int container, int flags,
+                                                               fl_crc_consts cc) {
+    fl_inflater_feed<false>(in, in_off, final_, out, out_off, out_len, consumed, status, sess, container, flags, cc);
+}
+// ... of an inflater whose streams may have preset dictionaries (flate_hip_inflater_set_dictionary was called, or the
+// inflater was created with FLATE_HIP_INFLATER_NEED_DICT); raw and zlib only
+__global__ __launch_bounds__(64, FL_INF_WAVES) void k_inflater_dict(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                                    const uint8_t* __restrict__ final_, uint8_t* __restrict__ out,
+                                                                    const uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                                                    uint64_t* __restrict__ consumed, int32_t* __restrict__ status,
+                                                                    uint8_t* __restrict__ sess, int container, int flags,
+                                                                    fl_crc_consts cc) {
+    fl_inflater_feed<true>(in, in_off, final_, out, out_off, out_len, consumed, status, sess, container, flags, cc);
 }
 
 // start a new member on the listed streams (Inflate.reset, inflate.zig:301-309)
@@ -1762,4 +1956,35 @@ __global__ void k_inflater_reset(uint8_t* __restrict__ sess, const uint32_t* __r
     S->carry_bit = 0;
     S->hflags = 0;
     S->hcount = 0;
+}
+
+// Give the listed streams one preset dictionary (flate_hip_inflater_set_dictionary), a wave each: its last hist_len bytes
+// go right-aligned into `hist`, where the decoder finds them as the bytes in front of the member's output.  Only a stream
+// that has absorbed nothing since create / reset takes it; applied[k] says so.  ent: the dictionary's table entry (k_dict_adler).
+__global__ __launch_bounds__(64) void k_inflater_set_dict(uint8_t* __restrict__ sess, const uint32_t* __restrict__ which, uint32_t n,
+                                                          uint32_t n_streams, int container,
+                                                          const uint8_t* __restrict__ dict, const fl_dict_ent* __restrict__ ent,
+                                                          uint8_t* __restrict__ applied) {
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (k >= n) return;
+    const uint32_t i = which[k];
+    if (i >= n_streams) return;
+    uint8_t* base = sess + (uint64_t)i * FL_RS_STRIDE;
+    fl_rs_state* S = (fl_rs_state*)base;
+    // Nothing absorbed: k_inflater_dict leaves a mark; the plain kernel, which the stream's feeds ran until now, leaves the
+    // state itself: a zlib stream is in front of its header's first byte, a raw stream has no output, no carry and stands in
+    // front of a block (whole blocks without output that ended on a byte boundary leave no trace, and no history either:
+    // the dictionary then is what it would have been before them).
+    const bool fresh = container == 2 ? S->phase == FL_RS_HEADER && S->sub == 0
+                                      : S->phase <= FL_RS_BLOCK && S->total == 0 && S->carry_bit == 0;
+    const bool take = !(S->hcount & FL_RS_DICT_FED) && fresh && S->carry_len == 0;
+    if (lane == 0) applied[k] = take ? 1 : 0;
+    if (!take) return;
+    const uint32_t hl = ent->hist_len;
+    uint8_t* hist = base + FL_RS_STATE + FL_RS_CARRY + FL_RS_WIN_IN;
+    fl_rs_copy(hist + FL_RS_HIST - hl, dict + ent->end - hl, hl, lane);
+    if (lane == 0) {
+        S->hcount = hl | FL_RS_DICT_SET;
+        S->dict_id = ent->adler;
+    }
 }

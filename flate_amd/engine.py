@@ -256,6 +256,43 @@ class Engine:
         res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
         return res, [int(s) for s in status], [int(c) for c in consumed]
 
+    def decompress_many_dict(self, streams, dicts, dict_of=None, container=0, flags=0, caps=None):
+        """Streams compressed against preset dictionaries (flate_hip_decompress_batch_dict; raw or zlib).  dicts: sequence
+        of bytes-like.  dict_of: per stream the index of its dictionary or None (it has none); default None: there is
+        exactly one dictionary and every stream uses it.  caps: output capacity per stream (default: the worst case of
+        1100 output bytes per input byte).  Returns (list of bytes, list of status codes, list of consumed input bytes)."""
+        self._sync_env()
+        if container == _capi.GZIP:
+            raise ValueError("gzip has no preset dictionaries")
+        n = len(streams)
+        if dict_of is None and len(dicts) != 1:
+            raise ValueError("dict_of may be left out only with exactly one dictionary")
+        if n == 0:
+            return [], [], []
+        blob, in_off = self._host_input(streams)
+        dblob, d_off = self._host_input(dicts)
+        of = None
+        if dict_of is not None:
+            if len(dict_of) != n:
+                raise ValueError("dict_of wants one entry per stream")
+            of = np.array([_capi.DICT_NONE if d is None else int(d) for d in dict_of], dtype=np.uint32)
+        if caps is None:
+            caps = [max(1 << 16, len(c) * 1100 + 1024) for c in streams]
+        caps = np.array([int(c) for c in caps], dtype=np.uint64)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(caps, out=out_off[1:])
+        out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int32)
+        consumed = np.zeros(n, dtype=np.uint64)
+        rc = self._L.flate_hip_decompress_batch_dict(self._h, blob.ctypes.data, in_off.ctypes.data, n, container, flags,
+                                                     out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                                     status.ctypes.data, consumed.ctypes.data, MEM_HOST, dblob.ctypes.data,
+                                                     d_off.ctypes.data, len(dicts), None if of is None else of.ctypes.data)
+        self._check(rc, "flate_hip_decompress_batch_dict")
+        res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
+        return res, [int(s) for s in status], [int(c) for c in consumed]
+
     # ---- device buffers (raw pointers; everything already in HBM) ----
     def compress_device(self, in_ptr, in_off_ptr, n_chunks, container, mode, out_ptr, out_off_ptr, out_len_ptr,
                         status_ptr):
@@ -290,6 +327,16 @@ class Engine:
         rc = self._L.flate_hip_decompress_batch(self._h, in_ptr, in_off_ptr, n_chunks, container, flags, out_ptr,
                                                 out_off_ptr, out_len_ptr, status_ptr, consumed_ptr, MEM_DEVICE)
         self._check(rc, "flate_hip_decompress_batch")
+
+    def decompress_dict_device(self, in_ptr, in_off_ptr, n_chunks, container, flags, out_ptr, out_off_ptr, out_len_ptr,
+                               status_ptr, consumed_ptr, dict_ptr, dict_off_ptr, n_dicts, dict_of_ptr=None):
+        """flate_hip_decompress_batch_dict on device memory (n_dicts + 1 dictionary offsets; dict_of: n_chunks uint32 or
+        None with one dictionary)."""
+        self._sync_env()
+        rc = self._L.flate_hip_decompress_batch_dict(self._h, in_ptr, in_off_ptr, n_chunks, container, flags, out_ptr,
+                                                     out_off_ptr, out_len_ptr, status_ptr, consumed_ptr, MEM_DEVICE,
+                                                     dict_ptr, dict_off_ptr, n_dicts, dict_of_ptr)
+        self._check(rc, "flate_hip_decompress_batch_dict")
 
     def decompressed_sizes_device(self, in_ptr, in_off_ptr, n_chunks, container, flags, sizes_ptr, status_ptr,
                                   consumed_ptr=None):
@@ -494,8 +541,21 @@ class Inflater:
         outs = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
         return outs, [int(v) for v in status], [int(v) for v in consumed]
 
+    def set_dictionary(self, indices, zdict):
+        """Give these streams one preset dictionary (flate_hip_inflater_set_dictionary).  Only a stream that has absorbed
+        nothing since create / reset takes it.  Returns the list of booleans: applied or not, one per index."""
+        w = np.ascontiguousarray(list(indices), dtype=np.uint32)
+        if w.size == 0:
+            return []
+        d = np.frombuffer(bytes(zdict), dtype=np.uint8) if len(zdict) else np.zeros(1, dtype=np.uint8)
+        applied = np.zeros(w.size, dtype=np.uint8)
+        rc = self._eng._L.flate_hip_inflater_set_dictionary(self._eng._h, self._s, w.ctypes.data, w.size, d.ctypes.data,
+                                                            len(zdict), MEM_HOST, applied.ctypes.data)
+        self._eng._check(rc, "flate_hip_inflater_set_dictionary")
+        return [bool(a) for a in applied]
+
     def reset(self, indices):
-        """Start a new member on these streams (Inflate.reset, inflate.zig:301-309)."""
+        """Start a new member on these streams (Inflate.reset, inflate.zig:301-309).  Drops a preset dictionary."""
         w = np.ascontiguousarray(list(indices), dtype=np.uint32)
         rc = self._eng._L.flate_hip_inflater_reset(self._eng._h, self._s, w.ctypes.data if w.size else None, w.size)
         self._eng._check(rc, "flate_hip_inflater_reset")

@@ -93,7 +93,10 @@ enum {
     FLATE_HIP_ST_REFERENCE_Q1_STREAM = 102,
     /* 103 is taken host-side (InvalidState of the Python mirror) */
     FLATE_HIP_ST_NEED_INPUT = 104,  /* inflater feed: all input absorbed, the member is not finished, more input may follow */
-    FLATE_HIP_ST_NEED_OUTPUT = 105  /* inflater feed: the output slot is full; feed the unabsorbed rest again with room */
+    FLATE_HIP_ST_NEED_OUTPUT = 105, /* inflater feed: the output slot is full; feed the unabsorbed rest again with room */
+    /* inflate with preset dictionaries (flate_hip_decompress_batch_dict, flate_hip_inflater_set_dictionary) */
+    FLATE_HIP_ST_NEED_DICT = 106,   /* a zlib stream with FDICT set, and the stream was given no dictionary */
+    FLATE_HIP_ST_WRONG_DICT = 107   /* ... its DICTID is not the Adler-32 of the dictionary the stream was given */
 };
 
 /* handle flags (flate_hip_set_flags).  bit0: compress at levels 4..9 hands every block the bytes its tokens cover -- the
@@ -197,6 +200,37 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
                                uint32_t n_chunks, int container, int flags, uint8_t* out,
                                const uint64_t* out_off, uint64_t* out_len, int32_t* status,
                                uint64_t* consumed, int memkind);
+
+/*
+ * Decompress n_chunks independent streams that were compressed against preset dictionaries (zlib's deflateSetDictionary,
+ * Python's zlib.compressobj(zdict=...)).  The first twelve arguments are those of flate_hip_decompress_batch, and so are
+ * out_len, consumed, the footer check and the rules for the slots.  Then:
+ *   dict      all dictionary bytes; dictionary d is dict[dict_off[d] .. dict_off[d+1]), of any length, 0 included
+ *   dict_off  n_dicts + 1 ascending offsets
+ *   n_dicts   number of dictionaries (0: dict and dict_off may be NULL, and every dict_of entry is 0xffffffff)
+ *   dict_of   n_chunks entries: the dictionary of stream i, or 0xffffffff for a stream without one.  NULL is allowed only
+ *             with n_dicts == 1: every stream uses dictionary 0.
+ * All arrays live where memkind says; dict_off and dict_of are read back once, as the other offsets are.
+ * Only the last 32768 bytes of a dictionary are history; its Adler-32 covers all of it.
+ *   raw (container 0)    the stream's dictionary is its history from the first byte.
+ *   zlib (container 2)   FDICT set: the four big-endian bytes behind the header (DICTID, RFC 1950 2.2) must be the
+ *                        Adler-32 of the stream's dictionary, else FLATE_HIP_ST_WRONG_DICT; a stream without a dictionary
+ *                        is FLATE_HIP_ST_NEED_DICT; a stream that ends inside DICTID is EndOfStream.  consumed counts the
+ *                        four bytes.  FDICT clear: the dictionary is NOT used and the stream decodes exactly as
+ *                        flate_hip_decompress_batch decodes it (zlib.decompressobj(15, zdict) does the same).
+ *   gzip                 has no dictionaries: FLATE_HIP_E_INVALID_ARG.
+ * InvalidMatch is a distance beyond (bytes produced so far + min(dictionary length, 32768)).  The footer's Adler-32 is over
+ * the output alone.
+ * Every stream of such a call is decoded by the wave-per-stream kernel: there are no spans and no workgroup-per-stream
+ * kernel here, so a LONG stream with a dictionary runs at the speed of one wave.  The shape this call is made for is a
+ * large batch of short records that share a few dictionaries.  The Adler-32 of every dictionary is computed once per call.
+ * Not covered: compressing with a dictionary, the size probe, flate_hip_decompress_members, the sharded entry points.
+ * flate_hip_decompress_batch itself is unchanged: it knows nothing of FDICT.
+ */
+int flate_hip_decompress_batch_dict(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
+                                    int container, int flags, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                                    int32_t* status, uint64_t* consumed, int memkind, const uint8_t* dict,
+                                    const uint64_t* dict_off, uint32_t n_dicts, const uint32_t* dict_of);
 
 /*
  * Size probe: how many bytes each of n_chunks independent streams inflates to, without inflating it.  The arguments have
@@ -340,6 +374,10 @@ int flate_hip_decompress_batch_sharded(flate_hip_handle h, void* nccl_comm, int 
  * (no host wait, no host read of the offsets); flate_hip_set_sync decides about the final wait.
  * flate_hip_inflater_reset (host array `which`) starts a new member on the listed streams.
  */
+/* flate_hip_inflater_create flag (beside FLATE_HIP_INFLATE_STRICT_Q6): a zlib stream with FDICT set on a stream that was
+ * given no dictionary reads its DICTID and reports FLATE_HIP_ST_NEED_DICT.  Without the flag such a stream is decoded
+ * as it always was: the FDICT bit is ignored and the DICTID bytes are taken for deflate data. */
+enum { FLATE_HIP_INFLATER_NEED_DICT = 2 };
 typedef struct flate_hip_inflater* flate_hip_inflater_t;
 int flate_hip_inflater_create(flate_hip_handle h, uint32_t n_streams, int container, int flags, flate_hip_inflater_t* s);
 int flate_hip_inflater_destroy(flate_hip_handle h, flate_hip_inflater_t s);
@@ -347,6 +385,20 @@ int flate_hip_inflater_reset(flate_hip_handle h, flate_hip_inflater_t s, const u
 int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const uint8_t* in, const uint64_t* in_off,
                             const uint8_t* final_, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
                             uint64_t* consumed, int32_t* status, int memkind);
+/*
+ * Give the listed streams (host array `which`) of a raw or zlib inflater one preset dictionary: dict[0 .. dict_len), in
+ * memory of kind memkind, any length.  It is copied in (its last 32768 bytes and its Adler-32 are kept): a host
+ * buffer is free on return; a device buffer is read on the handle's stream and is free in stream order (on return when
+ * `applied` is given or flate_hip_set_sync is on).  It takes effect only on a stream that has absorbed no input since create or reset (a raw
+ * stream that has absorbed nothing but whole blocks without output, ending on a byte boundary, counts as such: it has no
+ * history yet, and the dictionary is what it would have been in front of those blocks); any
+ * other listed stream is left untouched.  applied (host array of n_which bytes, may be NULL) receives 1 or 0 per listed
+ * stream; the call waits when it is given.  Feeding then behaves as flate_hip_decompress_batch_dict does for the
+ * concatenated pieces, DICTID may be cut anywhere across feeds, and FLATE_HIP_ST_NEED_DICT / _WRONG_DICT are sticky as the
+ * other errors are.  flate_hip_inflater_reset drops the dictionary.  A gzip inflater: FLATE_HIP_E_INVALID_ARG.
+ */
+int flate_hip_inflater_set_dictionary(flate_hip_handle h, flate_hip_inflater_t s, const uint32_t* which, uint32_t n_which,
+                                      const uint8_t* dict, uint64_t dict_len, int memkind, uint8_t* applied);
 
 /*
  * Resumable compress: n_streams independent huffman-only (mode 1) or store-only (mode 0) compressors whose state stays
