@@ -16,7 +16,6 @@
 #include <deque>
 #include <vector>
 #include <thread>
-#include <functional>
 
 #include "../../include/flate_hip.h"
 #include "kernels_block.h"
@@ -83,6 +82,10 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
 };
+struct PinBuf {  // pinned host memory the handle keeps (pin_grow)
+    void* p = nullptr;
+    size_t cap = 0;
+};
 
 }  // namespace
 
@@ -105,8 +108,10 @@ struct flate_hip_plan {
 // (flate_hip_debug_reload_env reads them again: the test suite's seam).
 struct fl_knobs {
     size_t max_pass_chunks = 32768;       // FLATE_HIP_MAX_PASS_CHUNKS
+    // host-buffer calls whose buffers are pinned run in sub-batches of this many chunks, so that the H2D copy of
+    // sub-batch k + 1 and the D2H copy of k - 1 overlap the kernels of k
     size_t host_pass_chunks = 1024;       // FLATE_HIP_HOST_PASS_CHUNKS
-    uint64_t stream_pass_bytes = 4096ull << 20;  // FLATE_HIP_MAX_STREAM_PASS_MIB
+    uint64_t stream_pass_bytes = 4096ull << 20;  // FLATE_HIP_MAX_STREAM_PASS_MIB: whole-stream passes, uncompressed bytes per pass (about 30 bytes of scratch per input byte)
     uint64_t span_min_bytes = 0;          // FLATE_HIP_INFLATE_SPANS (0 = never); set to the default below
     bool span_debug = false;              // FLATE_HIP_SPAN_DEBUG
     int span_twin = -1;                   // FLATE_HIP_SPAN_TWIN: -1 unset, 0 never, 2..950 where to cut
@@ -138,16 +143,9 @@ struct flate_hip_ctx {
     DevBuf chunks, blk_chunk, plans, hist, cks, S, NC, rec, desc, marks, tokens, ntok, cflag, links, shard_sz;
     DevBuf wexit;  // per window and sub-pass: where the path left it; per group: its exit, its entry; a flag (kernels_parse.h, fix launch)
     DevBuf wchunks, swins;  // whole-stream passes on k_lz_parse<true>: the streams' windows as chunks, a table entry per stream
-    void* pin_in = nullptr;   // pinned mirrors of pageable host buffers (compress_impl)
-    void* pin_out = nullptr;
-    void* pin_len = nullptr;  // out_len of a sub-batch on its way home (mirror_out reads it before the call ends)
-    void* pin_tab = nullptr;  // the pinned path's per-pass tables on their way to the device (a copy from PAGEABLE memory is staged by the runtime)
-    size_t pin_tab_cap = 0;
-    bool in_mirror = false;   // compress_impl is running on the mirrors (no second level of them)
-    size_t pin_in_cap = 0, pin_out_cap = 0, pin_len_cap = 0;
-    // pageable callers: a sub-batch's input is copied into the mirror right before its H2D copy is enqueued, its produced
-    // bytes out of the mirror as soon as they have landed -- while the GPU works on the other sub-batches
-    std::function<void(uint32_t, uint32_t)> mirror_in, mirror_out;
+    PinBuf pin_in, pin_out;  // pinned mirrors of pageable host buffers (run_on_mirrors)
+    PinBuf pin_len;          // out_len of a sub-batch on its way home (Mirror::copy_out reads it before the call ends)
+    PinBuf pin_tab;          // the pinned path's per-pass tables on their way to the device (a copy from PAGEABLE memory is staged by the runtime)
     uint32_t n_cu = 0;  // of the device (spans)
     DevBuf sp_points, sp_found, sp_spans, sp_res, sp_cand, sp_candoff, sp_tails, sp_tails_b, sp_chain, sp_chainoff,
         sp_pool, sp_pooltab, sp_poolctl, sp_items, sp_part, sp_footoff, sp_foot, sp_fin, sp_chainpos, sp_rs;  // inflate of long streams by spans
@@ -253,6 +251,25 @@ bool room(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
     if (ensure(h, b, bytes) == FLATE_HIP_OK) return true;
     (void)hipGetLastError();
     return false;
+}
+
+// Pinned host memory of at least `want` bytes: what is there if it is large enough, else `sz` new bytes (the old ones are
+// not kept).  false: no memory, the buffer is empty and the failure is answered here.
+void pin_release(PinBuf& b) {
+    if (b.p) (void)hipHostFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+bool pin_grow(PinBuf& b, size_t want, size_t sz) {
+    if (want <= b.cap) return true;
+    pin_release(b);
+    if (hipHostMalloc(&b.p, sz, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return false;
+    }
+    b.cap = sz;
+    return true;
 }
 
 // A side stream and the two events that tie it to the caller's stream: all three or none
@@ -376,10 +393,6 @@ void read_knobs(fl_knobs& k, uint64_t span_default) {
     if ((e = getenv("FLATE_HIP_MEMBER_SCAN"))) k.member_scan = atoi(e) != 0;
     if ((e = getenv("FLATE_HIP_MEMBER_CANDIDATES")) && atoll(e) >= 0 && atoll(e) <= 0x7fffffffll) k.member_candidates = (uint32_t)atoll(e);
 }
-size_t pass_chunk_limit(const flate_hip_ctx* h) { return h->knobs.max_pass_chunks; }
-// host-buffer calls whose buffers are pinned run in sub-batches of this many chunks, so that the H2D copy of
-// sub-batch k + 1 and the D2H copy of k - 1 overlap the kernels of k
-size_t host_pass_chunk_limit(const flate_hip_ctx* h) { return h->knobs.host_pass_chunks; }
 bool is_pinned_host(const void* p) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
@@ -413,9 +426,6 @@ int xfer_event(flate_hip_ctx* h, size_t k, hipEvent_t* ev) {
     return FLATE_HIP_OK;
 }
 
-// whole-stream passes: uncompressed bytes per pass (about 30 bytes of scratch per input byte)
-uint64_t stream_pass_byte_limit(const flate_hip_ctx* h) { return h->knobs.stream_pass_bytes; }
-
 // Levels 4..9, whole-stream pass: tokenizer kernels (kernels_stream.h).  Leaves tokens,
 // histograms and the block table for the shared back end.
 #ifndef FL_STREAM_FIX_MAX
@@ -427,7 +437,7 @@ int compress_stream_pass(flate_hip_ctx* h, const uint8_t* d_in, const fl_params&
     int rc;
     const uint32_t nseg = (uint32_t)t.segs.size(), npc = (uint32_t)t.pieces.size();
     const uint64_t npos = t.npos;
-    const size_t tile_limit = pass_chunk_limit(h);
+    const size_t tile_limit = h->knobs.max_pass_chunks;
     const size_t tiles_per_launch = std::min(t.tiles.size(), tile_limit);
     if ((rc = ensure(h, h->tiles, sizeof(fl_tile) * t.tiles.size()))) return rc;
     if ((rc = ensure(h, h->segs, sizeof(fl_seg) * (t.segs.size() + 1)))) return rc;
@@ -1362,10 +1372,7 @@ int flate_hip_destroy(flate_hip_handle h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     fold_profile(h);
-    if (h->pin_in) (void)hipHostFree(h->pin_in);
-    if (h->pin_len) (void)hipHostFree(h->pin_len);
-    if (h->pin_tab) (void)hipHostFree(h->pin_tab);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
+    for (PinBuf* b : {&h->pin_in, &h->pin_len, &h->pin_tab, &h->pin_out}) pin_release(*b);
     for (DevBuf* b : {&h->sp_points, &h->sp_found, &h->sp_spans, &h->sp_res, &h->sp_cand, &h->sp_candoff, &h->sp_tails,
                       &h->sp_tails_b, &h->sp_chain, &h->sp_chainoff, &h->sp_pool, &h->sp_pooltab, &h->sp_poolctl, &h->sp_items,
                       &h->sp_part, &h->sp_footoff, &h->sp_foot, &h->sp_fin, &h->sp_chainpos, &h->sp_rs, &h->sz_spans, &h->sz_recs})
@@ -1458,662 +1465,563 @@ int flate_hip_profile_read(flate_hip_handle h, const char** names, double* total
 }  // extern "C"
 
 namespace {
-int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container,
-                  int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind,
-                  const FlushSpec* fs, flate_hip_plan* pl = nullptr) {
-    // pl: the batch's layout is known (plan): no offsets are fetched; while the plan is being built
-    // (!pl->ready) the per-pass tables are made and kept and nothing is launched, afterwards they are
-    // used as they are and the call only enqueues work
-    const bool planning = pl && !pl->ready;
-    if (!h || (!pl && (!in_off || !out_off)) || (!planning && (!out_len || !status))) return FLATE_HIP_E_INVALID_ARG;
-    if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
-    fl_params prm{};
-    if (!level_args(mode, prm)) return FLATE_HIP_E_INVALID_ARG;
-    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
-    if (n_chunks == 0) return FLATE_HIP_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
-    prm.container = container;
-    prm.mode = mode;
-    prm.flags = (h->flags & FLATE_HIP_DEFLATE_REPAIR_Q1) ? FL_PRM_REPAIR_Q1 : 0u;
-    hipStream_t st = h->stream;
+// ---- compress_impl: every compress entry point.  Its decisions are pass_plan.h's (plain C++, tested on the CPU); the
+// functions below carry them out, one per stage, over one record per call.
 
-    std::vector<uint64_t> hin_, hout_;
-    int rc = 0;
-    if (!pl) {
-        rc = fetch_offsets(h, in_off, n_chunks, memkind, hin_);
-        if (rc) return rc;
-        rc = fetch_offsets(h, out_off, n_chunks, memkind, hout_);
-        if (rc) return rc;
-    }
-    const std::vector<uint64_t>& hin = pl ? pl->hin : hin_;
-    const std::vector<uint64_t>& hout = pl ? pl->hout : hout_;
-    const uint64_t in_lo = hin[0], in_hi = hin[n_chunks];
-    const uint64_t out_lo = hout[0], out_hi = hout[n_chunks];
-
-    // Pageable host buffers of some size (what every caller of the facade's compress(reader, writer) has): a
-    // staged hipMemcpy each way moves about 10 GB/s and nothing overlaps.  Instead a few host threads copy the
-    // input into a pinned mirror, the call runs on the mirrors (sub-batches, DMA copies on their own streams
-    // beside the kernels: the pinned path below), and the threads copy the produced bytes out of the mirror.
-    // (Pinned buffers are used where they lie: no host thread touches the data.  On a shared host both ways have their
-    // bad minutes -- the direct one 16.6 instead of 10.1 ms in one process of five, the mirrors 17.6 instead of 11.3 when
-    // the neighbours keep the memory system busy -- and the direct one needs no CPU.)
-    if (memkind == FLATE_HIP_MEM_HOST && !fs && !pl && (in_hi - in_lo) >= (8ull << 20) && in && out && !h->in_mirror &&
-        !is_pinned_host(in + in_lo) && !is_pinned_host(out + out_lo) && !h->knobs.no_pin_mirror) {
-        auto grow = [&](void*& p, size_t& cap, size_t want) -> bool {
-            if (want <= cap) return true;
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            const size_t sz = want + want / 8 + 4096;
-            if (hipHostMalloc(&p, sz, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                p = nullptr;
-                return false;
-            }
-            cap = sz;
-            return true;
-        };
-        if (grow(h->pin_in, h->pin_in_cap, (in_hi - in_lo) + 16) && grow(h->pin_out, h->pin_out_cap, (out_hi - out_lo) + 16)) {
-            const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-            const unsigned nt = std::min(8u, hw);
-            auto parallel = [&](uint64_t items, const std::function<void(uint64_t, uint64_t)>& fn) {
-                std::vector<std::thread> th;
-                const uint64_t per = (items + nt - 1) / nt;
-                for (unsigned t = 1; t < nt; t++) {
-                    const uint64_t a = std::min(items, t * per), b = std::min(items, a + per);
-                    if (b > a) th.emplace_back(fn, a, b);
-                }
-                fn(0, std::min(items, per));
-                for (auto& x : th) x.join();
-            };
-            const uint8_t* src = in + in_lo;
-            uint8_t* pin = (uint8_t*)h->pin_in;
-            const uint8_t* pout = (const uint8_t*)h->pin_out;
-            // the mirrors take the place of the caller's buffers: same offsets.  A sub-batch's input is copied right before
-            // its H2D copy is enqueued, its produced bytes leave the mirror as soon as they have landed.
-            h->mirror_in = [&](uint32_t c0, uint32_t nc) {
-                const uint64_t a = hin[c0] - in_lo, b = hin[c0 + nc] - in_lo;
-                parallel(b - a, [&](uint64_t x, uint64_t y) { memcpy(pin + a + x, src + a + x, y - x); });
-            };
-            bool landed = false;
-            h->mirror_out = [&](uint32_t c0, uint32_t nc) {
-                landed = true;
-                parallel(nc, [&](uint64_t x, uint64_t y) {
-                    for (uint64_t i = c0 + x; i < c0 + y; i++) {
-                        const uint64_t n = std::min<uint64_t>(out_len[i], hout[i + 1] - hout[i]);
-                        if (n) memcpy(out + hout[i], pout + (hout[i] - out_lo), n);
-                    }
-                });
-            };
-            h->in_mirror = true;
-            rc = compress_impl(h, pin - in_lo, in_off, n_chunks, container, mode, (uint8_t*)h->pin_out - out_lo,
-                               out_off, out_len, status, memkind, nullptr, nullptr);
-            h->in_mirror = false;
-            auto take_out = h->mirror_out;
-            h->mirror_in = nullptr;
-            h->mirror_out = nullptr;
-            if (rc) return rc;
-            if (!landed) take_out(0, n_chunks);  // (the call did not take the overlapped path)
-            // (large mirrors do not stay pinned with the handle)
-            if (h->pin_in_cap > (1ull << 30)) {
-                (void)hipHostFree(h->pin_in);
-                h->pin_in = nullptr;
-                h->pin_in_cap = 0;
-            }
-            if (h->pin_out_cap > (1ull << 30)) {
-                (void)hipHostFree(h->pin_out);
-                h->pin_out = nullptr;
-                h->pin_out_cap = 0;
-            }
-            return FLATE_HIP_OK;
+// Pageable callers' buffers behind pinned mirrors (run_on_mirrors): a sub-batch's input is copied into the mirror right
+// before its H2D copy is enqueued, its produced bytes out of the mirror as soon as they have landed -- while the GPU works
+// on the other sub-batches.  State of ONE call: the call that runs on the mirrors is handed a pointer to it.
+struct Mirror {
+    const uint8_t* src = nullptr;   // the caller's input from in_lo on, and its mirror
+    uint8_t* pin = nullptr;
+    const uint8_t* pout = nullptr;  // the output's mirror from out_lo on, and the caller's output
+    uint8_t* out = nullptr;
+    const uint64_t* out_len = nullptr;
+    const uint64_t *hin = nullptr, *hout = nullptr;
+    uint64_t in_lo = 0, out_lo = 0;
+    unsigned nt = 1;  // host threads that copy
+    bool landed = false;
+    template <class F>
+    void parallel(uint64_t items, const F& fn) const {
+        std::vector<std::thread> th;
+        const uint64_t per = (items + nt - 1) / nt;
+        for (unsigned t = 1; t < nt; t++) {
+            const uint64_t a = std::min(items, t * per), b = std::min(items, a + per);
+            if (b > a) th.emplace_back(fn, a, b);
         }
+        fn(0, std::min(items, per));
+        for (auto& x : th) x.join();
     }
+    void copy_in(uint32_t c0, uint32_t nc) const {
+        const uint64_t a = hin[c0] - in_lo, b = hin[c0 + nc] - in_lo;
+        parallel(b - a, [&](uint64_t x, uint64_t y) { memcpy(pin + a + x, src + a + x, y - x); });
+    }
+    void copy_out(uint32_t c0, uint32_t nc) {
+        landed = true;
+        parallel(nc, [&](uint64_t x, uint64_t y) {
+            for (uint64_t i = c0 + x; i < c0 + y; i++) {
+                const uint64_t n = std::min<uint64_t>(out_len[i], hout[i + 1] - hout[i]);
+                if (n) memcpy(out + hout[i], pout + (hout[i] - out_lo), n);
+            }
+        });
+    }
+};
 
+// What the stages of one compress_impl call share.
+struct CompressCall {
+    flate_hip_ctx* h = nullptr;
+    // the caller's arguments
+    const uint8_t* in = nullptr;
+    uint8_t* out = nullptr;
+    uint64_t* out_len = nullptr;
+    int32_t* status = nullptr;
+    uint32_t n_chunks = 0;
+    int container = 0, mode = 0, memkind = 0;
+    const FlushSpec* fs = nullptr;
+    // pl: the batch's layout is known (plan): no offsets are fetched; while the plan is being built
+    // (!pl->ready, `planning`) the per-pass tables are made and kept and nothing is launched, afterwards
+    // (`planned_run`) they are used as they are and the call only enqueues work
+    flate_hip_plan* pl = nullptr;
+    bool planning = false, planned_run = false;
+    Mirror* mirror = nullptr;  // the call runs on a pageable caller's mirrors
+    hipStream_t st = nullptr;  // the caller's stream
+    fl_params prm{};
+    std::vector<uint64_t> hin_, hout_;  // the offsets on the host (a plan holds its own)
+    const std::vector<uint64_t>*hin = nullptr, *hout = nullptr;
+    uint64_t in_lo = 0, in_hi = 0, out_lo = 0, out_hi = 0;
     // device views of the caller's buffers
-    const uint8_t* d_in = in;
-    uint8_t* d_out = out;
-    uint64_t* d_outlen = out_len;
-    int32_t* d_status = status;
+    const uint8_t* d_in = nullptr;
+    uint8_t* d_out = nullptr;
+    uint64_t* d_outlen = nullptr;
+    int32_t* d_status = nullptr;
     uint64_t in_shift = 0, out_shift = 0;  // subtracted from offsets when staging host buffers
     bool pin_in = false, pin_out = false;
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16))) return rc;
-        if ((rc = ensure(h, h->st_out, (out_hi - out_lo) + 16))) return rc;
-        if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_chunks))) return rc;
-        if ((rc = ensure(h, h->st_status, sizeof(int32_t) * n_chunks))) return rc;
-        // Pinned host buffers (hipHostMalloc / hipHostRegister, torch pin_memory): the copies are real DMA
-        // and run on their own streams, a sub-batch at a time (below).  Pageable: one staged copy each way.
-        pin_in = !fs && is_pinned_host(in + in_lo);
-        pin_out = !fs && is_pinned_host(out + out_lo);
-        if ((pin_in && !h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) ||
-            (pin_out && !h->s_out && create_copy_stream(&h->s_out, false) != hipSuccess))
-            return FLATE_HIP_E_ALLOC;
-        if (in_hi > in_lo && !pin_in)
-            HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-        d_in = (const uint8_t*)h->st_in.p;
-        d_out = (uint8_t*)h->st_out.p;
-        d_outlen = (uint64_t*)h->st_outlen.p;
-        d_status = (int32_t*)h->st_status.p;
-        in_shift = in_lo;
-        out_shift = out_lo;
-    } else if (((uintptr_t)out & 3) != 0) {
-        return FLATE_HIP_E_INVALID_ARG;
-    }
-
-    // chunk table + initial status
-    std::vector<fl_chunk> chunks(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; i++) {
-        fl_chunk& c = chunks[i];
-        const uint64_t len = hin[i + 1] - hin[i];
-        c.in_off = hin[i] - in_shift;
-        c.out_off = hout[i] - out_shift;
-        c.out_cap = hout[i + 1] - hout[i];
-        c.skip = 0;
-        // stream positions are 32-bit and the last match tile looks 64 KiB + 258 bytes ahead of its start
-        if (len > (mode >= 4 ? 0xfff00000ull : 0xfffffff0ull)) return FLATE_HIP_E_INVALID_ARG;
-        c.in_len = (uint32_t)len;
-        c.pos_off = 0;
-        c.piece0 = c.n_piece = c.flush_off = c.n_flush = c.zone_off = c.n_slides = 0;
-        c.unfinished = (fs && !fs->finish) ? 1u : 0u;
-        c.pad_ = 0;
-    }
-    if (!planning) {
-        HIP_OK(h, hipMemsetAsync(d_outlen, 0, sizeof(uint64_t) * n_chunks, st));
-        HIP_OK(h, hipMemsetAsync(d_status, 0, sizeof(int32_t) * n_chunks, st));
-    }
-
-    // the bit packer ORs into the output: clear the slots first -- on a stream of its own, behind what the caller's stream holds
-    // so far; the back end's first kernel that writes the slots waits for it (enqueue_back_end).  The tokenizer / the histograms
-    // and the planner do not touch the slots: 0.08 ms of config #4's 0.98 and 0.15 ms of the headline's 26.5 are hidden.
-    struct MsGuard {  // (whatever way this call ends, the caller's stream is behind the clearing)
-        flate_hip_ctx* h;
-        ~MsGuard() {
-            if (h->ms_pending) {
-                (void)hipStreamWaitEvent(h->stream, h->ms_ev1, 0);
-                h->ms_pending = false;
-            }
-        }
-    } ms_guard{h};
-    if (out_hi > out_lo && !planning) {
-        if (!h->s_ms) (void)side_stream(h->s_ms, h->ms_ev0, h->ms_ev1);
-        if (h->s_ms && !h->knobs.memset_inline) {
-            HIP_OK(h, hipEventRecord(h->ms_ev0, st));
-            HIP_OK(h, hipStreamWaitEvent(h->s_ms, h->ms_ev0, 0));
-            {
-                ProfScope ps(h, K_MEMSET, h->s_ms);
-                HIP_OK(h, hipMemsetAsync(d_out + (out_lo - out_shift), 0, out_hi - out_lo, h->s_ms));
-            }
-            HIP_OK(h, hipEventRecord(h->ms_ev1, h->s_ms));
-            h->ms_pending = true;
-        } else {
-            ProfScope ps(h, K_MEMSET);
-            HIP_OK(h, hipMemsetAsync(d_out + (out_lo - out_shift), 0, out_hi - out_lo, st));
-        }
-    }
-
-    // A pass is a run of consecutive chunks of one kind: at levels 4..9 inputs of up to 65535 bytes
-    // take the chunk path (kernels_lz.h), longer ones the whole-stream path (kernels_stream.h).
-    // (pass_plan.h: the sub-batch size, the merged tail, the ramp)
-    fl_pass_cfg pcfg;
-    pcfg.n_chunks = n_chunks;
-    pcfg.host_pass_chunks = host_pass_chunk_limit(h);
-    pcfg.max_pass_chunks = pass_chunk_limit(h);
-    pcfg.pinned = pin_in || pin_out;  // (never with a plan: planned batches are device memory)
-    pcfg.ramp = !h->knobs.no_ramp;
-    pcfg.planned = pl != nullptr;
-    const size_t pass_limit = fl_pass_limit(pcfg);
-    const uint64_t stream_pass_bytes = stream_pass_byte_limit(h);
-    if (pin_out) HIP_OK(h, hipStreamSynchronize(h->s_out));  // (nothing of an earlier call may still read st_out)
-    // Pinned output: the link is shared by both directions (57 GB/s one way, 28.6 each way at once: tools/pcie_probe.py),
-    // so what must not cross it is the unused part of the slots.  A copy kernel on the output stream writes the
-    // produced bytes of every slot straight into the caller's (device-visible) pinned memory: 52 GB/s for the bytes
-    // that matter (tools/zero_copy_probe.py) instead of 57 GB/s for 2.5 x as many.  Bytes of a slot beyond out_len[i]
-    // are then not touched at all.
-    uint8_t* zc_out = nullptr;  // device view of out + out_lo
+    bool pinned_passes = false;  // the tables of a pass travel on the input stream (prepare_pinned_tables)
+    bool landing = false;        // a mirrored call whose passes' output leaves the mirror as it lands
+    uint8_t* zc_out = nullptr;   // device view of out + out_lo
     std::vector<uint64_t> zc_slot;
-    if (pin_out && out_hi > out_lo) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, out + out_lo, 0) == hipSuccess && dp) {
-            zc_out = (uint8_t*)dp;
-            zc_slot.resize((size_t)n_chunks + 1);
-            for (uint32_t i = 0; i <= n_chunks; i++) zc_slot[i] = hout[i] - out_lo;
-            if ((rc = ensure(h, h->st_slot, sizeof(uint64_t) * ((size_t)n_chunks + 1)))) return rc;
-            HIP_OK(h, hipMemcpyAsync(h->st_slot.p, zc_slot.data(), sizeof(uint64_t) * ((size_t)n_chunks + 1), hipMemcpyHostToDevice, st));
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    // Pinned path: the tables of a pass (chunk table, block -> chunk) are copies from pageable vectors, which the runtime
-    // stages and moves with a blit kernel -- 0.3-0.4 ms each time, on the compute stream between two passes (rocprofv3
-    // timeline, tools/e2e_timeline.py).  They go on the input stream instead, into a slice of their own per pass, ahead of
-    // the pass's input; the compute stream waits for one event per pass.
-    const bool pinned_passes = (pin_in || pin_out) && !pl;
-    uint64_t blk_total = 0, blk_base = 0;
-    if (pinned_passes) {
-        if (!h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) return FLATE_HIP_E_ALLOC;
-        for (uint32_t i = 0; i < n_chunks; i++)
-            blk_total += mode >= 4 ? 2u : (uint64_t)(chunks[i].in_len / FL_BLOCK_BYTES + 1);
-        if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * (size_t)n_chunks))) return rc;
-        if ((rc = ensure(h, h->blk_chunk, sizeof(uint32_t) * (size_t)std::max<uint64_t>(blk_total, 1)))) return rc;
-        HIP_OK(h, hipStreamSynchronize(h->s_in));  // (nothing of an earlier call may still write the tables)
-        // the tables leave from pinned memory: [fl_chunk x n_chunks | uint32 x blk_total]
-        const size_t tab_need = sizeof(fl_chunk) * (size_t)n_chunks + sizeof(uint32_t) * (size_t)std::max<uint64_t>(blk_total, 1);
-        if (h->pin_tab_cap < tab_need) {
-            if (h->pin_tab) (void)hipHostFree(h->pin_tab);
-            h->pin_tab = nullptr;
-            h->pin_tab_cap = 0;
-            const size_t sz = tab_need + tab_need / 4 + 4096;
-            if (hipHostMalloc(&h->pin_tab, sz, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                h->pin_tab = nullptr;
-                return FLATE_HIP_E_ALLOC;
-            }
-            h->pin_tab_cap = sz;
-        }
-    }
-    uint32_t nc = 0;
-    size_t pass_count = 0;
+    // the tables: the copies of the pinned path read them until the call ends (PassGuard)
+    std::vector<fl_chunk> chunks;
     std::deque<std::vector<uint32_t>> keep_blk;
     std::deque<std::vector<fl_sblock>> keep_sb;
-    // On the pinned path the passes are enqueued without a host wait in between and the copies on the input stream read the
-    // vectors above: whichever way this function is left (an error in the middle included), they are outlived by the copies,
-    // and on two compute streams (set below) no kernel of the second one still writes the caller's output.
-    struct PassGuard {
-        flate_hip_ctx* h;
-        bool on;
-        ~PassGuard() {
-            if (on) {
-                if (h->s_in) (void)hipStreamSynchronize(h->s_in);
-                if (h->s_c2) (void)hipStreamSynchronize(h->s_c2);
-                (void)hipStreamSynchronize(h->stream);
-            }
-            h->ck_pending = false;  // (an error between the checksum launch and the back end must not leave a stale wait)
-        }
-    } pass_guard{h, pinned_passes};
-    // Round 6: TWO compute streams.  A sub-batch's six kernels each end in a tail that fills the chip less and less (1024 chunks are
-    // four per CU: 2.15 ms a sub-batch where a quarter of the whole batch's 6.6 ms would be 1.65) and the next sub-batch's first
-    // kernel waits behind the last one's tail.  The sub-batches alternate between the caller's stream and a second one -- every
-    // per-pass buffer has a slice per stream, so two passes that may run at once never touch the same bytes -- and the kernels of sub-batch
-    // k + 1 start as soon as its input is there and run into the tails of k's: 10.3 -> 10.0 ms per 256 MiB in one process, 11.7 ->
-    // 10.1 in another (bench e2e_host).  Levels 4-9, every input on the chunk path.  What lost (profiles/r06_host_path.txt): the
-    // tokenizers of all sub-batches in a row on one stream with the chains and the back ends on streams of higher priority beside
-    // them, 11.0 ms -- k_lz_parse takes a CU's whole LDS, a single small workgroup on a CU keeps the next tokenizer workgroup off it,
-    // and every kernel ran a quarter to a half longer than alone.
-    // (planned device batches of more than one pass take the same way: flate_hip_compress_planned)
-    const bool planned_run = pl && pl->ready;
-    bool two = ((pinned_passes && (size_t)n_chunks > pass_limit) || (planned_run && pl->passes.size() > 1)) && mode >= 4 && !fs && !h->knobs.one_stream;
-    for (uint32_t i = 0; two && i < n_chunks; i++) two = chunks[i].in_len <= FLATE_HIP_MAX_LZ_CHUNK;
-    if (two && !h->s_c2) two = side_stream(h->s_c2, h->c2_ev0, h->c2_ev1);
-    // The two streams' workspace is TWO slices of every per-pass buffer, each as large as the largest pass (pass_plan.h: the
-    // merged tail, not the sub-batch size); pass k runs on stream k & 1 in slice k & 1.  Passes k and k + 2 run in order on one
-    // stream, so pass k + 2 reuses pass k's bytes only after pass k's last kernel.  The other streams that touch a slice:
-    // - s_ck (k_checksum of containers 1 and 2 at levels 4..7, launch_checksum_side) writes the pass's `cks` slice behind an
-    //   event recorded on the pass's stream after the pass's own k_lz_chain -- after pass k's back end, which reads that slice;
-    // - s_in writes the batch-wide tables and input only (a slice of their own per pass), never the workspace.
-    // Everything is sized HERE, before the first pass is enqueued: ensure() synchronises only h->stream, which enqueue_sliced
-    // swaps, and would free a buffer the other stream still uses.  Until every pass is enqueued ensure() refuses to grow a
-    // buffer (h->ws_fixed): enqueue_pass's ensure_lz_workspace on the slice is a check, never a reallocation of a shifted buffer.
-    // Slices that cannot be had: the passes one after the other on the caller's stream (round 5's way).
-    std::vector<fl_pass> sched;  // the passes of the two-stream path
-    uint64_t slice_nc = 0, slice_nb = 0;
-    auto size_two_slices = [&](uint64_t nc_, uint64_t nb_) -> int {
-        int r;
-        if ((r = ensure_lz_workspace(h, (uint32_t)(2 * nc_), prm.chain))) return r;
-        return ensure_block_workspace(h, 2 * nb_);
-    };
-    if (two) {
-        if (planned_run) {
-            for (size_t k = 0; k < pl->passes.size(); k++) {
-                fl_pass p;
-                p.c0 = sched.empty() ? 0 : sched.back().c0 + sched.back().nc;
-                p.nc = pl->passes[k].nc;
-                p.stream = (uint32_t)(k & 1u);
-                sched.push_back(p);
-                slice_nc = std::max<uint64_t>(slice_nc, pl->passes[k].nc);
-                slice_nb = std::max<uint64_t>(slice_nb, pl->passes[k].nb);
-            }
-        } else {
-            slice_nc = fl_pass_schedule(pcfg, sched);
-            slice_nb = 2 * slice_nc;  // (levels 4..9 on the chunk path: two block slots per chunk)
-            // (up to 1.5 x the limit the merged tail is ONE pass: a second slice would never be used)
-            if (sched.size() < 2) two = false;
-        }
-        if (two && size_two_slices(slice_nc, slice_nb)) {
-            (void)hipGetLastError();
-            two = false;
-        }
-    }
-    pass_guard.on = pinned_passes || two;
-    struct WsFixed {
-        flate_hip_ctx* h;
-        ~WsFixed() { h->ws_fixed = false; }
-    } ws_fixed{h};
-    h->ws_fixed = two;
-    if (two) {
-        // the second stream behind what the caller's stream holds so far (the cleared lengths and statuses)
-        HIP_OK(h, hipEventRecord(h->c2_ev0, st));
-        HIP_OK(h, hipStreamWaitEvent(h->s_c2, h->c2_ev0, 0));
-        if (h->ms_pending) HIP_OK(h, hipStreamWaitEvent(h->s_c2, h->ms_ev1, 0));  // ... and behind the clearing of the slots
-    }
-    struct WsShift {  // a pass's view of the two-slice workspace: every buffer from its slice on (undone when the pass is enqueued)
-        std::vector<std::pair<DevBuf*, size_t>> undo;
-        void add(DevBuf& b, size_t bytes) {
-            b.p = (uint8_t*)b.p + bytes;
-            b.cap -= bytes;
-            undo.emplace_back(&b, bytes);
-        }
-        ~WsShift() {
-            for (auto& u : undo) {
-                u.first->p = (uint8_t*)u.first->p - u.second;
-                u.first->cap += u.second;
-            }
-        }
-    };
-    // a pass over slice k & 1 of every per-pass buffer, its kernels on that stream
-    auto enqueue_sliced = [&](size_t k, uint32_t nc_, uint32_t nb_, uint32_t c0_, const fl_chunk* dch_, const uint32_t* dbc_,
-                              const fl_sblock* dsb_) -> int {
-        if (k >= sched.size() || sched[k].c0 != c0_ || sched[k].nc != nc_ || nc_ > slice_nc || nb_ > slice_nb) {
-            h->last_error = "two-stream pass " + std::to_string(k) + " (" + std::to_string(c0_) + " + " + std::to_string(nc_) +
-                            " chunks) is not the scheduled one";
-            return FLATE_HIP_E_LAUNCH;
-        }
-        const uint32_t slice = sched[k].stream;
-        hipStream_t sq = slice ? h->s_c2 : st;
-        WsShift ws;
-        const size_t c_sl = (size_t)slice * slice_nc, b0 = (size_t)slice * slice_nb;
-        const bool bulk = prm.chain >= FL_BULK_MIN_CHAIN;
-        const fl_lz_sizes z = fl_lz_chunk_sizes(bulk);
-        const fl_blk_sizes bs = fl_block_slot_sizes();
-        ws.add(h->plans, bs.plan * b0);
-        ws.add(h->hist, bs.hist * b0);
-        ws.add(h->cks, bs.cks * b0);
-        ws.add(bulk ? h->links : h->S, z.links * c_sl);
-        ws.add(h->desc, z.desc * c_sl);
-        ws.add(h->marks, z.marks * c_sl);
-        ws.add(h->tokens, z.tokens * c_sl);
-        ws.add(h->ntok, z.ntok * c_sl);
-        ws.add(h->cflag, z.cflag * c_sl);
-        hipStream_t saved = h->stream;
-        h->stream = sq;
-        const int r = enqueue_pass(h, prm, nc_, nb_, c0_, dch_, dbc_, dsb_, d_in, d_out, d_outlen, d_status);
-        h->stream = saved;
-        return r;
-    };
-    std::vector<uint32_t> pass_c0;  // first chunk of every pass (mirror_out)
-    const bool landing = pin_out && (bool)h->mirror_out;
-    if (landing && h->pin_len_cap < sizeof(uint64_t) * (size_t)n_chunks) {
-        if (h->pin_len) (void)hipHostFree(h->pin_len);
-        h->pin_len = nullptr;
-        h->pin_len_cap = 0;
-        const size_t sz = sizeof(uint64_t) * ((size_t)n_chunks + n_chunks / 4 + 64);
-        if (hipHostMalloc(&h->pin_len, sz, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            h->pin_len = nullptr;
-            return FLATE_HIP_E_ALLOC;
-        }
-        h->pin_len_cap = sz;
-    }
-    for (uint32_t c0 = 0; c0 < n_chunks; c0 += nc) {
-        const bool stream = mode >= 4 && (fs || chunks[c0].in_len > FLATE_HIP_MAX_LZ_CHUNK);
-        uint64_t pass_bytes = 0;
-        // (a sub-batch of the pinned path costs about 0.9 ms whatever it holds: a tail of less than half a sub-batch
-        // goes with the one before it)
-        // (the GPU idles until the first sub-batch has crossed the link: the first two are a quarter and a half)
-        const size_t limit = (size_t)fl_pass_cap(pcfg, c0, pass_count);
-        for (nc = 0; c0 + nc < n_chunks; nc++) {
-            const fl_chunk& c = chunks[c0 + nc];
-            if ((mode >= 4 && (fs || c.in_len > FLATE_HIP_MAX_LZ_CHUNK)) != stream) break;
-            if (stream ? (nc > 0 && pass_bytes + c.in_len > stream_pass_bytes) : nc >= limit) break;
-            pass_bytes += c.in_len;
-        }
-        if (pl && stream) return FLATE_HIP_E_UNSUPPORTED;  // (whole-stream passes build more tables per call)
-        const size_t pass_index = pass_count++;
-        if (h->mirror_in) h->mirror_in(c0, nc);
-        pass_c0.push_back(c0);
-        hipEvent_t ev_in = nullptr;
-        const bool sliced = pinned_passes && !stream;  // this pass's tables: a slice of their own, filled on the input stream
-        if (pin_in && !sliced) {  // this sub-batch's input: in flight while the previous sub-batch is computed
-            const uint64_t a = hin[c0], b = hin[c0 + nc];
-            if ((rc = xfer_event(h, 4 * pass_index, &ev_in))) return rc;
-            if (b > a)
-                HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (a - in_lo), in + a, b - a, hipMemcpyHostToDevice, h->s_in));
-            HIP_OK(h, hipEventRecord(ev_in, h->s_in));
-        }
-        if (pl && pl->ready) {
-            // planned batch: the tables of this pass are on the device already
-            const flate_hip_plan::Pass& pp = pl->passes[pass_index];
-            const uint32_t nb = pp.nb;
-            prm.n_chunks = nc;
-            prm.n_blocks = nb;
-            prm.stream = 0;
-            if (two) {  // (sized before the first pass)
-                if ((rc = enqueue_sliced(pass_index, nc, nb, c0, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr))) return rc;
-                continue;
-            }
-            if ((rc = ensure_block_workspace(h, nb))) return rc;
-            if ((rc = enqueue_pass(h, prm, nc, nb, c0, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr,
-                                          d_in, d_out, d_outlen, d_status))) {
-                return rc;
-            }
-            continue;
-        }
-        // block table of this pass (kept until the end of the call: on the pinned path the passes are enqueued without a
-        // host wait in between -- 0.27 ms per pass, tools/e2e_probe.py -- and the copies below read these vectors)
-        keep_blk.emplace_back();
-        keep_sb.emplace_back();
-        std::vector<uint32_t>& blk_chunk = keep_blk.back();
-        std::vector<fl_sblock>& sblocks = keep_sb.back();  // huffman-only / store-only with flush points
-        StreamTables tabs;
-        uint32_t nb = 0;
-        for (uint32_t i = 0; i < nc; i++) {
-            fl_chunk& c = chunks[c0 + i];
-            c.first_block = nb;
-            if (stream) {
-                add_stream_chunk(tabs, c, i, nb, fs);
-            } else if (fs) {
-                // SimpleCompressor (deflate.zig:449-529): the 65535-byte buffer goes out as soon as it is
-                // full; flush / finish write what it holds then, an empty block if nothing (474-484)
-                uint32_t prev = 0;
-                auto piece = [&](uint32_t start, uint32_t end, bool last) {
-                    uint32_t p = start;
-                    for (; end - p >= FL_BLOCK_BYTES; p += FL_BLOCK_BYTES) sblocks.push_back(fl_sblock{p, FL_BLOCK_BYTES, 0u});
-                    sblocks.push_back(fl_sblock{p, end - p, last ? 1u : 0u});
-                    if (!last) sblocks.push_back(fl_sblock{0u, 0u, 2u});
-                };
-                for (uint32_t k = 0; k < fs->n; k++) {
-                    piece(prev, (uint32_t)fs->pos[k], false);
-                    prev = (uint32_t)fs->pos[k];
-                }
-                if (fs->finish) piece(prev, c.in_len, true);
-                c.n_blocks = (uint32_t)sblocks.size();
-                c.pos_off = 0;
-            } else {
-                c.n_blocks = mode >= 4 ? 2u : (uint32_t)(c.in_len / FL_BLOCK_BYTES + 1);  // deflate.zig:498-511, 480-484
-                c.pos_off = (uint64_t)i * FL_CHUNK_STRIDE;
-            }
-            for (uint32_t k = 0; k < c.n_blocks; k++) blk_chunk.push_back(i);
-            nb += c.n_blocks;
-        }
-        prm.n_chunks = nc;
-        prm.n_blocks = nb;
-        prm.stream = stream ? 1u : 0u;
-        if (!sliced) {
-            if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * nc))) return rc;
-            if ((rc = ensure(h, h->blk_chunk, sizeof(uint32_t) * nb))) return rc;
-        }
-        if (!two && (rc = ensure_block_workspace(h, nb))) return rc;  // (the two-stream path's are sized before the first pass)
-        fl_chunk* tab_chunks = (fl_chunk*)h->chunks.p + (sliced ? c0 : 0u);
-        uint32_t* tab_blk = (uint32_t*)h->blk_chunk.p + (sliced ? blk_base : 0u);
-        if (sliced) {
-            if (blk_base + nb > blk_total) return FLATE_HIP_E_LAUNCH;
-            blk_base += nb;
-            // (through the pinned table buffer: a copy from a pageable vector is staged by the runtime, and the staged copy of
-            // sub-batch k + 1 did not start before the way home of sub-batch k was over -- rocprofv3 timeline, round 5)
-            fl_chunk* pt_chunks = (fl_chunk*)h->pin_tab + c0;
-            uint32_t* pt_blk = (uint32_t*)((fl_chunk*)h->pin_tab + n_chunks) + (blk_base - nb);
-            memcpy(pt_chunks, &chunks[c0], sizeof(fl_chunk) * nc);
-            memcpy(pt_blk, blk_chunk.data(), sizeof(uint32_t) * nb);
-            HIP_OK(h, hipMemcpyAsync(tab_chunks, pt_chunks, sizeof(fl_chunk) * nc, hipMemcpyHostToDevice, h->s_in));
-            HIP_OK(h, hipMemcpyAsync(tab_blk, pt_blk, sizeof(uint32_t) * nb, hipMemcpyHostToDevice, h->s_in));
-            const uint64_t a = hin[c0], b = hin[c0 + nc];
-            if (pin_in && b > a)
-                HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (a - in_lo), in + a, b - a, hipMemcpyHostToDevice, h->s_in));
-            if ((rc = xfer_event(h, 4 * pass_index, &ev_in))) return rc;
-            HIP_OK(h, hipEventRecord(ev_in, h->s_in));
-        } else {
-            HIP_OK(h, hipMemcpyAsync(tab_chunks, &chunks[c0], sizeof(fl_chunk) * nc, hipMemcpyHostToDevice, st));
-            HIP_OK(h, hipMemcpyAsync(tab_blk, blk_chunk.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
-        }
-        const fl_sblock* dsb = nullptr;
-        if (!sblocks.empty()) {
-            if ((rc = ensure(h, h->sblocks, sizeof(fl_sblock) * sblocks.size()))) return rc;
-            HIP_OK(h, hipMemcpyAsync(h->sblocks.p, sblocks.data(), sizeof(fl_sblock) * sblocks.size(), hipMemcpyHostToDevice, st));
-            dsb = (const fl_sblock*)h->sblocks.p;
-        }
-        // the host vectors must outlive the async copies
-        if (!(pin_in || pin_out) || stream || planning) HIP_OK(h, hipStreamSynchronize(st));
-        const bool alt = two && pass_index < sched.size() && sched[pass_index].stream != 0;  // every other sub-batch on the second compute stream
-        hipStream_t stp = alt ? h->s_c2 : st;
-        if (ev_in) HIP_OK(h, hipStreamWaitEvent(stp, ev_in, 0));
-        if (planning) {
-            // keep this pass's tables in the plan; size the workspace now so that planned calls never allocate
-            flate_hip_plan::Pass pp;
-            pp.nc = nc;
-            pp.nb = nb;
-            if (hipMalloc(&pp.chunks, sizeof(fl_chunk) * nc) != hipSuccess ||
-                hipMalloc(&pp.blk_chunk, sizeof(uint32_t) * std::max(nb, 1u)) != hipSuccess) {
-                if (pp.chunks) (void)hipFree(pp.chunks);
-                if (pp.blk_chunk) (void)hipFree(pp.blk_chunk);
-                return FLATE_HIP_E_ALLOC;
-            }
-            pl->passes.push_back(pp);  // the plan owns the tables from here on (flate_hip_plan_destroy frees them)
-            HIP_OK(h, hipMemcpy(pp.chunks, h->chunks.p, sizeof(fl_chunk) * nc, hipMemcpyDeviceToDevice));
-            HIP_OK(h, hipMemcpy(pp.blk_chunk, h->blk_chunk.p, sizeof(uint32_t) * nb, hipMemcpyDeviceToDevice));
-            if (mode >= 4 && (rc = ensure_lz_workspace(h, nc, prm.chain))) return rc;
-            continue;
-        }
+    std::vector<uint32_t> pass_c0;  // first chunk of every pass (Mirror::copy_out)
+    uint64_t blk_total = 0, blk_base = 0;  // pinned path: block slots of the whole batch, and those of the passes so far
+    fl_pass_cfg pcfg;
+    bool two = false;      // the passes alternate between two compute streams
+    fl_two_slices slices;  // ... over these slices of the workspace
+};
 
-        const fl_chunk* dch = tab_chunks;
-        const uint32_t* dbc = tab_blk;
-        if (stream) {
-            if (container != 0) {
-                ProfScope ps(h, K_CHECKSUM);
-                hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(64), 0, st, d_in, dch, dbc, dsb, prm, h->crc,
-                                   (uint32_t*)h->cks.p);
-            }
-            if ((rc = compress_stream_pass(h, d_in, prm, nc, nb, tabs, &chunks[c0]))) return rc;
-            h->dbg_pass_chunks = nc;
-            h->dbg_first_chunk = c0;
-            h->dbg_pos_off.clear();
-            h->dbg_chunks.assign(chunks.begin() + c0, chunks.begin() + c0 + nc);
-            h->dbg_pieces = tabs.pieces;
-            if ((rc = enqueue_back_end(h, prm, nc, nb, c0, dch, dbc, dsb, d_in, d_out, d_outlen, d_status))) return rc;
-            if (pinned_passes) {
-                // A whole-stream pass keeps its tables at the START of the table buffers (its block count is not known when
-                // the slices are laid out), where the slices of the chunk passes lie: its kernels are only enqueued here, so
-                // the input stream -- which fills the next chunk pass's slice -- waits for them first.
-                hipEvent_t ev_tab;
-                if ((rc = xfer_event(h, 4 * pass_index + 3, &ev_tab))) return rc;
-                HIP_OK(h, hipEventRecord(ev_tab, st));
-                HIP_OK(h, hipStreamWaitEvent(h->s_in, ev_tab, 0));
-            }
-        } else if (two) {
-            if ((rc = enqueue_sliced(pass_index, nc, nb, c0, dch, dbc, dsb))) return rc;
-        } else {
-            if ((rc = enqueue_pass(h, prm, nc, nb, c0, dch, dbc, dsb, d_in, d_out, d_outlen, d_status))) return rc;
-        }
-        HIP_OK(h, hipGetLastError());
-        if (pin_out) {  // this sub-batch's output slots go home while the next sub-batch is computed
-            hipEvent_t ev_out;
-            if ((rc = xfer_event(h, 4 * pass_index + 1, &ev_out))) return rc;
-            HIP_OK(h, hipEventRecord(ev_out, stp));
-            HIP_OK(h, hipStreamWaitEvent(h->s_out, ev_out, 0));
-            const uint64_t a = hout[c0], b = hout[c0 + nc];
-            bool len_by_kernel = false;
-            if (b > a && zc_out) {
-                // Slots of one size (the usual case: compress_bound of one chunk size): the first half of every slot goes
-                // home by the DMA engine's rectangle copy -- what lies beyond out_len[i] there is the zeros the slots were
-                // cleared with --, and only what a chunk produced BEYOND that half by the copy kernel: a few workgroups that
-                // take the slots in turn.  The kernel is not free beside the next sub-batch's kernels: its stores wait for the
-                // link and the stores of the other kernels wait behind them (k_lz_chain took 0.47 ms instead of 0.09 beside
-                // it, started behind it the tokenizer paid the same); the DMA engine costs them nothing (11.7 -> 10.5 ms for
-                // 256 MiB of text, where no chunk reaches the second half).
-                uint32_t urows = 0;
-                uint64_t pitch = 0, half = 0;
-                if (nc > 1) {
-                    pitch = hout[c0 + 1] - hout[c0];
-                    for (urows = 1; urows < nc && hout[c0 + urows + 1] - hout[c0 + urows] == pitch; urows++) {}
-                    half = (pitch / 2) & ~(uint64_t)15;
-                    // (Round 5: OFF unless FLATE_HIP_RECT=1.  The rectangle copy is a DMA copy that waits for the sub-batch's kernels
-                    // -- and the input copy of the NEXT sub-batch, submitted behind it, lands in the same in-order DMA queue in most
-                    // calls of a process: then nothing overlaps any more, 16.6 ms per 256 MiB instead of 10.4 (rocprofv3 timelines,
-                    // profiles/r05_host_path.txt: the 10.4 only ever showed in the second call of a process).  The copy kernel
-                    // alone is 11.4 ms in every call.)
-                    if (urows < 64 || half < 4096 || h->knobs.rect != 1) urows = 0;
-                }
-                if (urows)
-                    HIP_OK(h, hipMemcpy2DAsync(out + a, pitch, d_out + (a - out_shift), pitch, half, urows, hipMemcpyDeviceToHost, h->s_out));
-                uint64_t* len_dev = nullptr;  // device view of pin_len + c0 (the mirror path reads the lengths as the passes land)
-                if (landing) {
-                    void* dp = nullptr;
-                    if (hipHostGetDevicePointer(&dp, (uint64_t*)h->pin_len + c0, 0) == hipSuccess && dp) len_dev = (uint64_t*)dp;
-                    else (void)hipGetLastError();
-                }
-                len_by_kernel = len_dev != nullptr;
-                hipLaunchKernelGGL(k_copy_slots, dim3(std::min(64u, nc)), dim3(256), 0, h->s_out, d_out,
-                                   (const uint64_t*)h->st_slot.p + c0, (const uint64_t*)d_outlen + c0, zc_out,
-                                   (const uint64_t*)h->st_slot.p + c0, nc, urows, half, len_dev);
-                HIP_OK(h, hipGetLastError());
-            } else if (b > a) {
-                HIP_OK(h, hipMemcpyAsync(out + a, d_out + (a - out_shift), b - a, hipMemcpyDeviceToHost, h->s_out));
-            }
-            if (landing) {  // this pass's lengths and an event behind its way home
-                hipEvent_t ev_done;
-                if ((rc = xfer_event(h, 4 * pass_index + 2, &ev_done))) return rc;
-                if (!len_by_kernel)
-                    HIP_OK(h, hipMemcpyAsync((uint64_t*)h->pin_len + c0, d_outlen + c0, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost, h->s_out));
-                HIP_OK(h, hipEventRecord(ev_done, h->s_out));
-            }
+// One pass [c0, c0 + nc) on its way through the stages
+struct PassRun {
+    uint32_t c0 = 0, nc = 0, nb = 0;
+    size_t index = 0;
+    bool stream = false;           // a whole-stream pass
+    bool sliced = false;           // this pass's tables: a slice of their own, filled on the input stream
+    hipEvent_t ev_in = nullptr;    // its input (and tables) are on the device
+    hipStream_t stp = nullptr;     // the compute stream its kernels run on
+    const fl_chunk* dch = nullptr; // its tables on the device
+    const uint32_t* dbc = nullptr;
+    const fl_sblock* dsb = nullptr;
+    StreamTables tabs;
+    std::vector<uint32_t>* blk_chunk = nullptr;
+    std::vector<fl_sblock>* sblocks = nullptr;  // huffman-only / store-only with flush points
+};
+
+struct MsGuard {  // (whatever way this call ends, the caller's stream is behind the clearing)
+    flate_hip_ctx* h;
+    ~MsGuard() {
+        if (h->ms_pending) {
+            (void)hipStreamWaitEvent(h->stream, h->ms_ev1, 0);
+            h->ms_pending = false;
         }
     }
-    if (two) {  // the caller's stream behind the second one
+};
+// On the pinned path the passes are enqueued without a host wait in between and the copies on the input stream read the
+// call's vectors: whichever way compress_impl is left (an error in the middle included), they are outlived by the copies,
+// and on two compute streams no kernel of the second one still writes the caller's output.
+struct PassGuard {
+    flate_hip_ctx* h;
+    bool on;
+    ~PassGuard() {
+        if (on) {
+            if (h->s_in) (void)hipStreamSynchronize(h->s_in);
+            if (h->s_c2) (void)hipStreamSynchronize(h->s_c2);
+            (void)hipStreamSynchronize(h->stream);
+        }
+        h->ck_pending = false;  // (an error between the checksum launch and the back end must not leave a stale wait)
+    }
+};
+struct WsFixed {
+    flate_hip_ctx* h;
+    ~WsFixed() { h->ws_fixed = false; }
+};
+struct WsShift {  // a pass's view of the two-slice workspace: every buffer from its slice on (undone when the pass is enqueued)
+    std::vector<std::pair<DevBuf*, size_t>> undo;
+    void add(DevBuf& b, size_t bytes) {
+        b.p = (uint8_t*)b.p + bytes;
+        b.cap -= bytes;
+        undo.emplace_back(&b, bytes);
+    }
+    ~WsShift() {
+        for (auto& u : undo) {
+            u.first->p = (uint8_t*)u.first->p - u.second;
+            u.first->cap += u.second;
+        }
+    }
+};
+
+int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container,
+                  int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind,
+                  const FlushSpec* fs, flate_hip_plan* pl = nullptr, Mirror* mirror = nullptr);
+
+// Pageable host buffers of some size (what every caller of the facade's compress(reader, writer) has): a
+// staged hipMemcpy each way moves about 10 GB/s and nothing overlaps.  Instead a few host threads copy the
+// input into a pinned mirror, the call runs on the mirrors (sub-batches, DMA copies on their own streams
+// beside the kernels: the pinned path), and the threads copy the produced bytes out of the mirror.
+// (Pinned buffers are used where they lie: no host thread touches the data.  On a shared host both ways have their
+// bad minutes -- the direct one 16.6 instead of 10.1 ms in one process of five, the mirrors 17.6 instead of 11.3 when
+// the neighbours keep the memory system busy -- and the direct one needs no CPU.)
+// *taken: the call went this way and is over.
+int run_on_mirrors(CompressCall& cc, const uint64_t* in_off, const uint64_t* out_off, bool* taken) {
+    flate_hip_ctx* h = cc.h;
+    *taken = false;
+    if (!(cc.memkind == FLATE_HIP_MEM_HOST && !cc.fs && !cc.pl && (cc.in_hi - cc.in_lo) >= (8ull << 20) && cc.in && cc.out && !cc.mirror &&
+          !is_pinned_host(cc.in + cc.in_lo) && !is_pinned_host(cc.out + cc.out_lo) && !h->knobs.no_pin_mirror))
+        return FLATE_HIP_OK;
+    const size_t want_in = (cc.in_hi - cc.in_lo) + 16, want_out = (cc.out_hi - cc.out_lo) + 16;
+    if (!pin_grow(h->pin_in, want_in, want_in + want_in / 8 + 4096) || !pin_grow(h->pin_out, want_out, want_out + want_out / 8 + 4096))
+        return FLATE_HIP_OK;
+    *taken = true;
+    // the mirrors take the place of the caller's buffers: same offsets.  A sub-batch's input is copied right before
+    // its H2D copy is enqueued, its produced bytes leave the mirror as soon as they have landed.
+    Mirror m;
+    m.src = cc.in + cc.in_lo;
+    m.pin = (uint8_t*)h->pin_in.p;
+    m.pout = (const uint8_t*)h->pin_out.p;
+    m.out = cc.out;
+    m.out_len = cc.out_len;
+    m.hin = cc.hin->data();
+    m.hout = cc.hout->data();
+    m.in_lo = cc.in_lo;
+    m.out_lo = cc.out_lo;
+    m.nt = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+    const int rc = compress_impl(h, m.pin - cc.in_lo, in_off, cc.n_chunks, cc.container, cc.mode, (uint8_t*)h->pin_out.p - cc.out_lo,
+                                 out_off, cc.out_len, cc.status, cc.memkind, nullptr, nullptr, &m);
+    if (rc) return rc;
+    if (!m.landed) m.copy_out(0, cc.n_chunks);  // (the call did not take the overlapped path)
+    // (large mirrors do not stay pinned with the handle)
+    if (h->pin_in.cap > (1ull << 30)) pin_release(h->pin_in);
+    if (h->pin_out.cap > (1ull << 30)) pin_release(h->pin_out);
+    return FLATE_HIP_OK;
+}
+
+// Host buffers are staged: the device views, the shifts, and whether the copies run as DMA on streams of their own
+int stage_host_buffers(CompressCall& cc) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    cc.d_in = cc.in;
+    cc.d_out = cc.out;
+    cc.d_outlen = cc.out_len;
+    cc.d_status = cc.status;
+    if (cc.memkind == FLATE_HIP_MEM_HOST) {
+        if ((rc = ensure(h, h->st_in, (cc.in_hi - cc.in_lo) + 16))) return rc;
+        if ((rc = ensure(h, h->st_out, (cc.out_hi - cc.out_lo) + 16))) return rc;
+        if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * cc.n_chunks))) return rc;
+        if ((rc = ensure(h, h->st_status, sizeof(int32_t) * cc.n_chunks))) return rc;
+        // Pinned host buffers (hipHostMalloc / hipHostRegister, torch pin_memory): the copies are real DMA
+        // and run on their own streams, a sub-batch at a time (below).  Pageable: one staged copy each way.
+        cc.pin_in = !cc.fs && is_pinned_host(cc.in + cc.in_lo);
+        cc.pin_out = !cc.fs && is_pinned_host(cc.out + cc.out_lo);
+        if ((cc.pin_in && !h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) ||
+            (cc.pin_out && !h->s_out && create_copy_stream(&h->s_out, false) != hipSuccess))
+            return FLATE_HIP_E_ALLOC;
+        if (cc.in_hi > cc.in_lo && !cc.pin_in)
+            HIP_OK(h, hipMemcpyAsync(h->st_in.p, cc.in + cc.in_lo, cc.in_hi - cc.in_lo, hipMemcpyHostToDevice, cc.st));
+        cc.d_in = (const uint8_t*)h->st_in.p;
+        cc.d_out = (uint8_t*)h->st_out.p;
+        cc.d_outlen = (uint64_t*)h->st_outlen.p;
+        cc.d_status = (int32_t*)h->st_status.p;
+        cc.in_shift = cc.in_lo;
+        cc.out_shift = cc.out_lo;
+    } else if (((uintptr_t)cc.out & 3) != 0) {
+        return FLATE_HIP_E_INVALID_ARG;
+    }
+    return FLATE_HIP_OK;
+}
+
+// the bit packer ORs into the output: clear the slots first -- on a stream of its own, behind what the caller's stream holds
+// so far; the back end's first kernel that writes the slots waits for it (enqueue_back_end).  The tokenizer / the histograms
+// and the planner do not touch the slots: 0.08 ms of config #4's 0.98 and 0.15 ms of the headline's 26.5 are hidden.
+// (MsGuard puts the caller's stream behind the clearing when the call ends)
+int clear_slots(CompressCall& cc) {
+    flate_hip_ctx* h = cc.h;
+    if (!(cc.out_hi > cc.out_lo && !cc.planning)) return FLATE_HIP_OK;
+    if (!h->s_ms) (void)side_stream(h->s_ms, h->ms_ev0, h->ms_ev1);
+    if (h->s_ms && !h->knobs.memset_inline) {
+        HIP_OK(h, hipEventRecord(h->ms_ev0, cc.st));
+        HIP_OK(h, hipStreamWaitEvent(h->s_ms, h->ms_ev0, 0));
+        {
+            ProfScope ps(h, K_MEMSET, h->s_ms);
+            HIP_OK(h, hipMemsetAsync(cc.d_out + (cc.out_lo - cc.out_shift), 0, cc.out_hi - cc.out_lo, h->s_ms));
+        }
+        HIP_OK(h, hipEventRecord(h->ms_ev1, h->s_ms));
+        h->ms_pending = true;
+    } else {
+        ProfScope ps(h, K_MEMSET);
+        HIP_OK(h, hipMemsetAsync(cc.d_out + (cc.out_lo - cc.out_shift), 0, cc.out_hi - cc.out_lo, cc.st));
+    }
+    return FLATE_HIP_OK;
+}
+
+// Pinned output: the link is shared by both directions (57 GB/s one way, 28.6 each way at once: tools/pcie_probe.py),
+// so what must not cross it is the unused part of the slots.  A copy kernel on the output stream writes the
+// produced bytes of every slot straight into the caller's (device-visible) pinned memory: 52 GB/s for the bytes
+// that matter (tools/zero_copy_probe.py) instead of 57 GB/s for 2.5 x as many.  Bytes of a slot beyond out_len[i]
+// are then not touched at all.
+// Pinned path: the tables of a pass (chunk table, block -> chunk) are copies from pageable vectors, which the runtime
+// stages and moves with a blit kernel -- 0.3-0.4 ms each time, on the compute stream between two passes (rocprofv3
+// timeline, tools/e2e_timeline.py).  They go on the input stream instead, into a slice of their own per pass, ahead of
+// the pass's input; the compute stream waits for one event per pass.
+int prepare_pinned_tables(CompressCall& cc) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    const uint32_t n_chunks = cc.n_chunks;
+    if (cc.pin_out) HIP_OK(h, hipStreamSynchronize(h->s_out));  // (nothing of an earlier call may still read st_out)
+    if (cc.pin_out && cc.out_hi > cc.out_lo) {
+        void* dp = nullptr;
+        if (hipHostGetDevicePointer(&dp, cc.out + cc.out_lo, 0) == hipSuccess && dp) {
+            cc.zc_out = (uint8_t*)dp;
+            cc.zc_slot.resize((size_t)n_chunks + 1);
+            for (uint32_t i = 0; i <= n_chunks; i++) cc.zc_slot[i] = (*cc.hout)[i] - cc.out_lo;
+            if ((rc = ensure(h, h->st_slot, sizeof(uint64_t) * ((size_t)n_chunks + 1)))) return rc;
+            HIP_OK(h, hipMemcpyAsync(h->st_slot.p, cc.zc_slot.data(), sizeof(uint64_t) * ((size_t)n_chunks + 1), hipMemcpyHostToDevice, cc.st));
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    cc.pinned_passes = (cc.pin_in || cc.pin_out) && !cc.pl;
+    if (cc.pinned_passes) {
+        if (!h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) return FLATE_HIP_E_ALLOC;
+        cc.blk_total = fl_batch_blocks(cc.chunks.data(), n_chunks, cc.mode);
+        if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * (size_t)n_chunks))) return rc;
+        if ((rc = ensure(h, h->blk_chunk, sizeof(uint32_t) * (size_t)std::max<uint64_t>(cc.blk_total, 1)))) return rc;
+        HIP_OK(h, hipStreamSynchronize(h->s_in));  // (nothing of an earlier call may still write the tables)
+        // the tables leave from pinned memory: [fl_chunk x n_chunks | uint32 x blk_total]
+        const size_t tab_need = sizeof(fl_chunk) * (size_t)n_chunks + sizeof(uint32_t) * (size_t)std::max<uint64_t>(cc.blk_total, 1);
+        if (!pin_grow(h->pin_tab, tab_need, tab_need + tab_need / 4 + 4096)) return FLATE_HIP_E_ALLOC;
+    }
+    return FLATE_HIP_OK;
+}
+
+int size_two_slices(flate_hip_ctx* h, const fl_params& prm, uint64_t nc, uint64_t nb) {
+    int r;
+    if ((r = ensure_lz_workspace(h, (uint32_t)(2 * nc), prm.chain))) return r;
+    return ensure_block_workspace(h, 2 * nb);
+}
+
+// Two compute streams (pass_plan.h, fl_two_eligible: when, and why) and their workspace (fl_two_slices).  The other streams
+// that touch a slice:
+// - s_ck (k_checksum of containers 1 and 2 at levels 4..7, launch_checksum_side) writes the pass's `cks` slice behind an
+//   event recorded on the pass's stream after the pass's own k_lz_chain -- after pass k's back end, which reads that slice;
+// - s_in writes the batch-wide tables and input only (a slice of their own per pass), never the workspace.
+// Everything is sized HERE, before the first pass is enqueued: ensure() synchronises only h->stream, which enqueue_sliced
+// swaps, and would free a buffer the other stream still uses.  Until every pass is enqueued ensure() refuses to grow a
+// buffer (h->ws_fixed): enqueue_pass's ensure_lz_workspace on the slice is a check, never a reallocation of a shifted buffer.
+// Slices that cannot be had: the passes one after the other on the caller's stream (round 5's way).
+void setup_two_streams(CompressCall& cc) {
+    flate_hip_ctx* h = cc.h;
+    cc.two = fl_two_eligible(cc.pcfg, cc.pinned_passes, cc.planned_run ? cc.pl->passes.size() : 0, cc.mode, cc.fs != nullptr,
+                             h->knobs.one_stream, cc.chunks.data());
+    if (cc.two && !h->s_c2) cc.two = side_stream(h->s_c2, h->c2_ev0, h->c2_ev1);
+    if (!cc.two) return;
+    cc.two = cc.planned_run ? fl_two_from_plan(cc.pl->passes, cc.slices) : fl_two_from_schedule(cc.pcfg, cc.slices);
+    if (cc.two && size_two_slices(h, cc.prm, cc.slices.nc, cc.slices.nb)) {
+        (void)hipGetLastError();
+        cc.two = false;
+    }
+}
+
+// a pass over slice k & 1 of every per-pass buffer, its kernels on that stream
+int enqueue_sliced(CompressCall& cc, size_t k, uint32_t nc, uint32_t nb, uint32_t c0, const fl_chunk* dch, const uint32_t* dbc,
+                   const fl_sblock* dsb) {
+    flate_hip_ctx* h = cc.h;
+    const std::vector<fl_pass>& sched = cc.slices.sched;
+    if (k >= sched.size() || sched[k].c0 != c0 || sched[k].nc != nc || nc > cc.slices.nc || nb > cc.slices.nb) {
+        h->last_error = "two-stream pass " + std::to_string(k) + " (" + std::to_string(c0) + " + " + std::to_string(nc) +
+                        " chunks) is not the scheduled one";
+        return FLATE_HIP_E_LAUNCH;
+    }
+    const uint32_t slice = sched[k].stream;
+    hipStream_t sq = slice ? h->s_c2 : cc.st;
+    WsShift ws;
+    const size_t c_sl = (size_t)slice * cc.slices.nc, b0 = (size_t)slice * cc.slices.nb;
+    const bool bulk = cc.prm.chain >= FL_BULK_MIN_CHAIN;
+    const fl_lz_sizes z = fl_lz_chunk_sizes(bulk);
+    const fl_blk_sizes bs = fl_block_slot_sizes();
+    ws.add(h->plans, bs.plan * b0);
+    ws.add(h->hist, bs.hist * b0);
+    ws.add(h->cks, bs.cks * b0);
+    ws.add(bulk ? h->links : h->S, z.links * c_sl);
+    ws.add(h->desc, z.desc * c_sl);
+    ws.add(h->marks, z.marks * c_sl);
+    ws.add(h->tokens, z.tokens * c_sl);
+    ws.add(h->ntok, z.ntok * c_sl);
+    ws.add(h->cflag, z.cflag * c_sl);
+    hipStream_t saved = h->stream;
+    h->stream = sq;
+    const int r = enqueue_pass(h, cc.prm, nc, nb, c0, dch, dbc, dsb, cc.d_in, cc.d_out, cc.d_outlen, cc.d_status);
+    h->stream = saved;
+    return r;
+}
+
+// planned batch: the tables of this pass are on the device already
+int enqueue_planned_pass(CompressCall& cc, const PassRun& p) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    const flate_hip_plan::Pass& pp = cc.pl->passes[p.index];
+    const uint32_t nb = pp.nb;
+    cc.prm.n_chunks = p.nc;
+    cc.prm.n_blocks = nb;
+    cc.prm.stream = 0;
+    if (cc.two)  // (sized before the first pass)
+        return enqueue_sliced(cc, p.index, p.nc, nb, p.c0, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr);
+    if ((rc = ensure_block_workspace(h, nb))) return rc;
+    return enqueue_pass(h, cc.prm, p.nc, nb, p.c0, (const fl_chunk*)pp.chunks, (const uint32_t*)pp.blk_chunk, nullptr, cc.d_in, cc.d_out,
+                        cc.d_outlen, cc.d_status);
+}
+
+// A pass's input (pinned input) and its tables on their way to the device, and the compute stream of the pass behind them
+int upload_pass(CompressCall& cc, PassRun& p) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    hipStream_t st = cc.st;
+    const std::vector<uint64_t>& hin = *cc.hin;
+    const uint32_t c0 = p.c0, nc = p.nc, nb = p.nb;
+    if (cc.pin_in && !p.sliced) {  // this sub-batch's input: in flight while the previous sub-batch is computed
+        const uint64_t a = hin[c0], b = hin[c0 + nc];
+        if ((rc = xfer_event(h, 4 * p.index, &p.ev_in))) return rc;
+        if (b > a)
+            HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (a - cc.in_lo), cc.in + a, b - a, hipMemcpyHostToDevice, h->s_in));
+        HIP_OK(h, hipEventRecord(p.ev_in, h->s_in));
+    }
+    cc.prm.n_chunks = nc;
+    cc.prm.n_blocks = nb;
+    cc.prm.stream = p.stream ? 1u : 0u;
+    if (!p.sliced) {
+        if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * nc))) return rc;
+        if ((rc = ensure(h, h->blk_chunk, sizeof(uint32_t) * nb))) return rc;
+    }
+    if (!cc.two && (rc = ensure_block_workspace(h, nb))) return rc;  // (the two-stream path's are sized before the first pass)
+    fl_chunk* tab_chunks = (fl_chunk*)h->chunks.p + (p.sliced ? c0 : 0u);
+    uint32_t* tab_blk = (uint32_t*)h->blk_chunk.p + (p.sliced ? cc.blk_base : 0u);
+    if (p.sliced) {
+        if (cc.blk_base + nb > cc.blk_total) return FLATE_HIP_E_LAUNCH;
+        cc.blk_base += nb;
+        // (through the pinned table buffer: a copy from a pageable vector is staged by the runtime, and the staged copy of
+        // sub-batch k + 1 did not start before the way home of sub-batch k was over -- rocprofv3 timeline, round 5)
+        fl_chunk* pt_chunks = (fl_chunk*)h->pin_tab.p + c0;
+        uint32_t* pt_blk = (uint32_t*)((fl_chunk*)h->pin_tab.p + cc.n_chunks) + (cc.blk_base - nb);
+        memcpy(pt_chunks, &cc.chunks[c0], sizeof(fl_chunk) * nc);
+        memcpy(pt_blk, p.blk_chunk->data(), sizeof(uint32_t) * nb);
+        HIP_OK(h, hipMemcpyAsync(tab_chunks, pt_chunks, sizeof(fl_chunk) * nc, hipMemcpyHostToDevice, h->s_in));
+        HIP_OK(h, hipMemcpyAsync(tab_blk, pt_blk, sizeof(uint32_t) * nb, hipMemcpyHostToDevice, h->s_in));
+        const uint64_t a = hin[c0], b = hin[c0 + nc];
+        if (cc.pin_in && b > a)
+            HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (a - cc.in_lo), cc.in + a, b - a, hipMemcpyHostToDevice, h->s_in));
+        if ((rc = xfer_event(h, 4 * p.index, &p.ev_in))) return rc;
+        HIP_OK(h, hipEventRecord(p.ev_in, h->s_in));
+    } else {
+        HIP_OK(h, hipMemcpyAsync(tab_chunks, &cc.chunks[c0], sizeof(fl_chunk) * nc, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipMemcpyAsync(tab_blk, p.blk_chunk->data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
+    }
+    if (!p.sblocks->empty()) {
+        if ((rc = ensure(h, h->sblocks, sizeof(fl_sblock) * p.sblocks->size()))) return rc;
+        HIP_OK(h, hipMemcpyAsync(h->sblocks.p, p.sblocks->data(), sizeof(fl_sblock) * p.sblocks->size(), hipMemcpyHostToDevice, st));
+        p.dsb = (const fl_sblock*)h->sblocks.p;
+    }
+    // the host vectors must outlive the async copies
+    if (!(cc.pin_in || cc.pin_out) || p.stream || cc.planning) HIP_OK(h, hipStreamSynchronize(st));
+    const bool alt = cc.two && p.index < cc.slices.sched.size() && cc.slices.sched[p.index].stream != 0;  // every other sub-batch on the second compute stream
+    p.stp = alt ? h->s_c2 : st;
+    if (p.ev_in) HIP_OK(h, hipStreamWaitEvent(p.stp, p.ev_in, 0));
+    p.dch = tab_chunks;
+    p.dbc = tab_blk;
+    return FLATE_HIP_OK;
+}
+
+// keep this pass's tables in the plan; size the workspace now so that planned calls never allocate
+int keep_pass_in_plan(CompressCall& cc, const PassRun& p) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    const uint32_t nc = p.nc, nb = p.nb;
+    flate_hip_plan::Pass pp;
+    pp.nc = nc;
+    pp.nb = nb;
+    if (hipMalloc(&pp.chunks, sizeof(fl_chunk) * nc) != hipSuccess ||
+        hipMalloc(&pp.blk_chunk, sizeof(uint32_t) * std::max(nb, 1u)) != hipSuccess) {
+        if (pp.chunks) (void)hipFree(pp.chunks);
+        if (pp.blk_chunk) (void)hipFree(pp.blk_chunk);
+        return FLATE_HIP_E_ALLOC;
+    }
+    cc.pl->passes.push_back(pp);  // the plan owns the tables from here on (flate_hip_plan_destroy frees them)
+    // (on the call's stream, ahead of the next pass's tables, which overwrite the source there: a device-to-device hipMemcpy
+    // runs on the null stream and does not wait for the host, so the next upload could overtake it)
+    HIP_OK(h, hipMemcpyAsync(pp.chunks, h->chunks.p, sizeof(fl_chunk) * nc, hipMemcpyDeviceToDevice, cc.st));
+    HIP_OK(h, hipMemcpyAsync(pp.blk_chunk, h->blk_chunk.p, sizeof(uint32_t) * nb, hipMemcpyDeviceToDevice, cc.st));
+    if (cc.mode >= 4 && (rc = ensure_lz_workspace(h, nc, cc.prm.chain))) return rc;
+    return FLATE_HIP_OK;
+}
+
+// a whole-stream pass: its checksum, its tokenizer (compress_stream_pass), the shared back end
+int enqueue_stream_pass(CompressCall& cc, const PassRun& p) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    hipStream_t st = cc.st;
+    const uint32_t c0 = p.c0, nc = p.nc, nb = p.nb;
+    if (cc.container != 0) {
+        ProfScope ps(h, K_CHECKSUM);
+        hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(64), 0, st, cc.d_in, p.dch, p.dbc, p.dsb, cc.prm, h->crc,
+                           (uint32_t*)h->cks.p);
+    }
+    if ((rc = compress_stream_pass(h, cc.d_in, cc.prm, nc, nb, p.tabs, &cc.chunks[c0]))) return rc;
+    h->dbg_pass_chunks = nc;
+    h->dbg_first_chunk = c0;
+    h->dbg_pos_off.clear();
+    h->dbg_chunks.assign(cc.chunks.begin() + c0, cc.chunks.begin() + c0 + nc);
+    h->dbg_pieces = p.tabs.pieces;
+    if ((rc = enqueue_back_end(h, cc.prm, nc, nb, c0, p.dch, p.dbc, p.dsb, cc.d_in, cc.d_out, cc.d_outlen, cc.d_status))) return rc;
+    if (cc.pinned_passes) {
+        // A whole-stream pass keeps its tables at the START of the table buffers (its block count is not known when
+        // the slices are laid out), where the slices of the chunk passes lie: its kernels are only enqueued here, so
+        // the input stream -- which fills the next chunk pass's slice -- waits for them first.
+        hipEvent_t ev_tab;
+        if ((rc = xfer_event(h, 4 * p.index + 3, &ev_tab))) return rc;
+        HIP_OK(h, hipEventRecord(ev_tab, st));
+        HIP_OK(h, hipStreamWaitEvent(h->s_in, ev_tab, 0));
+    }
+    return FLATE_HIP_OK;
+}
+
+// Pinned output: this sub-batch's output slots go home while the next sub-batch is computed
+int send_pass_home(CompressCall& cc, const PassRun& p) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    const std::vector<uint64_t>& hout = *cc.hout;
+    const uint32_t c0 = p.c0, nc = p.nc;
+    hipEvent_t ev_out;
+    if ((rc = xfer_event(h, 4 * p.index + 1, &ev_out))) return rc;
+    HIP_OK(h, hipEventRecord(ev_out, p.stp));
+    HIP_OK(h, hipStreamWaitEvent(h->s_out, ev_out, 0));
+    const uint64_t a = hout[c0], b = hout[c0 + nc];
+    bool len_by_kernel = false;
+    if (b > a && cc.zc_out) {
+        const fl_rect r = fl_rect_rows(&hout[c0], nc, h->knobs.rect);  // (pass_plan.h: which slots, and why off by default)
+        if (r.urows)
+            HIP_OK(h, hipMemcpy2DAsync(cc.out + a, r.pitch, cc.d_out + (a - cc.out_shift), r.pitch, r.half, r.urows, hipMemcpyDeviceToHost, h->s_out));
+        uint64_t* len_dev = nullptr;  // device view of pin_len + c0 (the mirror path reads the lengths as the passes land)
+        if (cc.landing) {
+            void* dp = nullptr;
+            if (hipHostGetDevicePointer(&dp, (uint64_t*)h->pin_len.p + c0, 0) == hipSuccess && dp) len_dev = (uint64_t*)dp;
+            else (void)hipGetLastError();
+        }
+        len_by_kernel = len_dev != nullptr;
+        hipLaunchKernelGGL(k_copy_slots, dim3(std::min(64u, nc)), dim3(256), 0, h->s_out, cc.d_out,
+                           (const uint64_t*)h->st_slot.p + c0, (const uint64_t*)cc.d_outlen + c0, cc.zc_out,
+                           (const uint64_t*)h->st_slot.p + c0, nc, r.urows, r.half, len_dev);
+        HIP_OK(h, hipGetLastError());
+    } else if (b > a) {
+        HIP_OK(h, hipMemcpyAsync(cc.out + a, cc.d_out + (a - cc.out_shift), b - a, hipMemcpyDeviceToHost, h->s_out));
+    }
+    if (cc.landing) {  // this pass's lengths and an event behind its way home
+        hipEvent_t ev_done;
+        if ((rc = xfer_event(h, 4 * p.index + 2, &ev_done))) return rc;
+        if (!len_by_kernel)
+            HIP_OK(h, hipMemcpyAsync((uint64_t*)h->pin_len.p + c0, cc.d_outlen + c0, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost, h->s_out));
+        HIP_OK(h, hipEventRecord(ev_done, h->s_out));
+    }
+    return FLATE_HIP_OK;
+}
+
+// Every pass is enqueued: the caller's stream behind the second one, the slices of a plan that was just built, the
+// mirror emptied as the passes land, a host caller's lengths, statuses and bytes
+int finish_call(CompressCall& cc, PassGuard& pass_guard) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    hipStream_t st = cc.st;
+    const uint32_t n_chunks = cc.n_chunks;
+    if (cc.two) {  // the caller's stream behind the second one
         HIP_OK(h, hipEventRecord(h->c2_ev1, h->s_c2));
         HIP_OK(h, hipStreamWaitEvent(st, h->c2_ev1, 0));
         // the caller's stream is behind the second one: from here on nothing of s_c2 outlives the call unseen, and a planned
         // call only enqueues (flate_hip_compress_planned) -- the host waits below only where it did without two streams
-        pass_guard.on = pinned_passes;
+        pass_guard.on = cc.pinned_passes;
     }
     // every pass is enqueued and the caller's stream is behind both: the buffers may grow again (copy_out_host below packs
     // a pageable caller's output in a buffer of its own)
     h->ws_fixed = false;
-    if (planning && mode >= 4 && pl->passes.size() > 1 && !h->knobs.one_stream) {
+    if (cc.planning && cc.mode >= 4 && !h->knobs.one_stream) {
         // the planned calls will take two streams: their slices now too (if they cannot be had, the calls take one stream)
-        uint64_t snc = 0, snb = 0;
-        for (const flate_hip_plan::Pass& pp : pl->passes) {
-            snc = std::max<uint64_t>(snc, pp.nc);
-            snb = std::max<uint64_t>(snb, pp.nb);
-        }
-        if (size_two_slices(snc, snb)) (void)hipGetLastError();
+        fl_two_slices s;
+        if (fl_two_from_plan(cc.pl->passes, s) && size_two_slices(h, cc.prm, s.nc, s.nb)) (void)hipGetLastError();
     }
-    if (landing) {
+    if (cc.landing) {
         // everything is enqueued: take the passes' output out of the mirror as they land
-        for (size_t k = 0; k < pass_c0.size(); k++) {
-            const uint32_t a = pass_c0[k], b = k + 1 < pass_c0.size() ? pass_c0[k + 1] : n_chunks;
+        for (size_t k = 0; k < cc.pass_c0.size(); k++) {
+            const uint32_t a = cc.pass_c0[k], b = k + 1 < cc.pass_c0.size() ? cc.pass_c0[k + 1] : n_chunks;
             hipEvent_t ev_done;
             if ((rc = xfer_event(h, 4 * k + 2, &ev_done))) return rc;
             HIP_OK(h, hipEventSynchronize(ev_done));
-            memcpy(out_len + a, (const uint64_t*)h->pin_len + a, sizeof(uint64_t) * (b - a));
-            h->mirror_out(a, b - a);
+            memcpy(cc.out_len + a, (const uint64_t*)h->pin_len.p + a, sizeof(uint64_t) * (b - a));
+            cc.mirror->copy_out(a, b - a);
         }
     }
-
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_chunks, hipMemcpyDeviceToHost, st));
+    if (cc.memkind == FLATE_HIP_MEM_HOST) {
+        HIP_OK(h, hipMemcpyAsync(cc.out_len, cc.d_outlen, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(cc.status, cc.d_status, sizeof(int32_t) * n_chunks, hipMemcpyDeviceToHost, st));
         HIP_OK(h, hipStreamSynchronize(st));
-        if (pin_out)
+        if (cc.pin_out)
             HIP_OK(h, hipStreamSynchronize(h->s_out));
-        else if ((rc = copy_out_host(h, d_out, d_outlen, n_chunks, hout, out_shift, out, out_len)))
+        else if ((rc = copy_out_host(h, cc.d_out, cc.d_outlen, n_chunks, *cc.hout, cc.out_shift, cc.out, cc.out_len)))
             return rc;
     } else if (h->sync) {
         HIP_OK(h, hipStreamSynchronize(st));
@@ -2121,6 +2029,129 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     return FLATE_HIP_OK;
 }
 
+int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container,
+                  int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind,
+                  const FlushSpec* fs, flate_hip_plan* pl, Mirror* mirror) {
+    const bool planning = pl && !pl->ready;
+    if (!h || (!pl && (!in_off || !out_off)) || (!planning && (!out_len || !status))) return FLATE_HIP_E_INVALID_ARG;
+    if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
+    // The record is declared before the guards, so whatever way the call ends the guards' destructors run first, in this
+    // order, and the record's vectors -- which copies on the input stream may still read -- are freed after them:
+    // ws_fixed (ensure() may grow buffers again), then pass_guard (the streams are waited for, ck_pending is reset),
+    // then ms_guard (the caller's stream waits for the slot clearing).
+    CompressCall cc;
+    if (!level_args(mode, cc.prm)) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (n_chunks == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    cc.prm.container = container;
+    cc.prm.mode = mode;
+    cc.prm.flags = (h->flags & FLATE_HIP_DEFLATE_REPAIR_Q1) ? FL_PRM_REPAIR_Q1 : 0u;
+    cc.h = h;
+    cc.in = in;
+    cc.out = out;
+    cc.out_len = out_len;
+    cc.status = status;
+    cc.n_chunks = n_chunks;
+    cc.container = container;
+    cc.mode = mode;
+    cc.memkind = memkind;
+    cc.fs = fs;
+    cc.pl = pl;
+    cc.planning = planning;
+    cc.planned_run = pl && pl->ready;
+    cc.mirror = mirror;
+    cc.st = h->stream;
+
+    int rc = 0;
+    if (!pl) {
+        rc = fetch_offsets(h, in_off, n_chunks, memkind, cc.hin_);
+        if (rc) return rc;
+        rc = fetch_offsets(h, out_off, n_chunks, memkind, cc.hout_);
+        if (rc) return rc;
+    }
+    cc.hin = pl ? &pl->hin : &cc.hin_;
+    cc.hout = pl ? &pl->hout : &cc.hout_;
+    cc.in_lo = (*cc.hin)[0], cc.in_hi = (*cc.hin)[n_chunks];
+    cc.out_lo = (*cc.hout)[0], cc.out_hi = (*cc.hout)[n_chunks];
+
+    bool mirrored = false;
+    rc = run_on_mirrors(cc, in_off, out_off, &mirrored);
+    if (rc || mirrored) return rc;
+    if ((rc = stage_host_buffers(cc))) return rc;
+    // chunk table + initial status
+    if (!fl_chunk_table(cc.hin->data(), cc.hout->data(), n_chunks, cc.in_shift, cc.out_shift, mode, fs, cc.chunks)) return FLATE_HIP_E_INVALID_ARG;
+    if (!planning) {
+        HIP_OK(h, hipMemsetAsync(cc.d_outlen, 0, sizeof(uint64_t) * n_chunks, cc.st));
+        HIP_OK(h, hipMemsetAsync(cc.d_status, 0, sizeof(int32_t) * n_chunks, cc.st));
+    }
+    MsGuard ms_guard{h};
+    if ((rc = clear_slots(cc))) return rc;
+
+    // (pass_plan.h: the kinds of pass, the sub-batch size, the merged tail, the ramp)
+    cc.pcfg.n_chunks = n_chunks;
+    cc.pcfg.host_pass_chunks = h->knobs.host_pass_chunks;
+    cc.pcfg.max_pass_chunks = h->knobs.max_pass_chunks;
+    cc.pcfg.pinned = cc.pin_in || cc.pin_out;  // (never with a plan: planned batches are device memory)
+    cc.pcfg.ramp = !h->knobs.no_ramp;
+    cc.pcfg.planned = pl != nullptr;
+    if ((rc = prepare_pinned_tables(cc))) return rc;
+    PassGuard pass_guard{h, cc.pinned_passes};
+    setup_two_streams(cc);
+    pass_guard.on = cc.pinned_passes || cc.two;
+    WsFixed ws_fixed{h};
+    h->ws_fixed = cc.two;
+    if (cc.two) {
+        // the second stream behind what the caller's stream holds so far (the cleared lengths and statuses)
+        HIP_OK(h, hipEventRecord(h->c2_ev0, cc.st));
+        HIP_OK(h, hipStreamWaitEvent(h->s_c2, h->c2_ev0, 0));
+        if (h->ms_pending) HIP_OK(h, hipStreamWaitEvent(h->s_c2, h->ms_ev1, 0));  // ... and behind the clearing of the slots
+    }
+    cc.landing = cc.pin_out && mirror;
+    if (cc.landing && !pin_grow(h->pin_len, sizeof(uint64_t) * (size_t)n_chunks, sizeof(uint64_t) * ((size_t)n_chunks + n_chunks / 4 + 64)))
+        return FLATE_HIP_E_ALLOC;
+
+    size_t pass_count = 0;
+    for (uint32_t c0 = 0, nc = 0; c0 < n_chunks; c0 += nc) {
+        const fl_pass_pick pk = fl_pass_next(cc.pcfg, cc.chunks.data(), c0, pass_count, mode, fs != nullptr, h->knobs.stream_pass_bytes);
+        nc = pk.nc;
+        if (pl && pk.stream) return FLATE_HIP_E_UNSUPPORTED;  // (whole-stream passes build more tables per call)
+        PassRun p;
+        p.c0 = c0;
+        p.nc = nc;
+        p.index = pass_count++;
+        p.stream = pk.stream;
+        p.sliced = cc.pinned_passes && !pk.stream;
+        if (mirror) mirror->copy_in(c0, nc);
+        cc.pass_c0.push_back(c0);
+        if (cc.planned_run) {
+            if ((rc = enqueue_planned_pass(cc, p))) return rc;
+            continue;
+        }
+        // block table of this pass (kept until the end of the call: on the pinned path the passes are enqueued without a
+        // host wait in between -- 0.27 ms per pass, tools/e2e_probe.py -- and the copies read these vectors)
+        cc.keep_blk.emplace_back();
+        cc.keep_sb.emplace_back();
+        p.blk_chunk = &cc.keep_blk.back();
+        p.sblocks = &cc.keep_sb.back();
+        p.nb = fl_pass_tables(&cc.chunks[c0], nc, p.stream, mode, fs, p.tabs, *p.blk_chunk, *p.sblocks);
+        if ((rc = upload_pass(cc, p))) return rc;
+        if (planning) {
+            if ((rc = keep_pass_in_plan(cc, p))) return rc;
+            continue;
+        }
+        if (p.stream)
+            rc = enqueue_stream_pass(cc, p);
+        else if (cc.two)
+            rc = enqueue_sliced(cc, p.index, nc, p.nb, c0, p.dch, p.dbc, p.dsb);
+        else
+            rc = enqueue_pass(h, cc.prm, nc, p.nb, c0, p.dch, p.dbc, p.dsb, cc.d_in, cc.d_out, cc.d_outlen, cc.d_status);
+        if (rc) return rc;
+        HIP_OK(h, hipGetLastError());
+        if (cc.pin_out && (rc = send_pass_home(cc, p))) return rc;
+    }
+    return finish_call(cc, pass_guard);
+}
 }  // namespace
 
 extern "C" {
@@ -2309,7 +2340,7 @@ int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint6
         // the sizes): sub-batches with the copies on their own streams, as in compress_impl.  Otherwise one
         // staged copy in, and only the produced bytes come back (copy_out_host).
         pin_io = is_pinned_host(in + in_lo) && is_pinned_host(out + out_lo) &&
-                 (out_hi - out_lo) <= 8 * (in_hi - in_lo) + (1ull << 20) && n_chunks > 4 * host_pass_chunk_limit(h);
+                 (out_hi - out_lo) <= 8 * (in_hi - in_lo) + (1ull << 20) && n_chunks > 4 * h->knobs.host_pass_chunks;
         if (pin_io && ((!h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) ||
                        (!h->s_out && create_copy_stream(&h->s_out, false) != hipSuccess)))
             return FLATE_HIP_E_ALLOC;
@@ -2391,7 +2422,7 @@ int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint6
     if (pin_io) {
         // (a sub-batch has to fill the chip -- 20 streams per CU -- or the latency of a stream decides: two sub-batches of
         // 2049 streams take as long as one batch, five of 3277 are 33 GB/s against 24, tools/e2e_inflate_probe.py)
-        const uint32_t target = 3u * (uint32_t)host_pass_chunk_limit(h);
+        const uint32_t target = 3u * (uint32_t)h->knobs.host_pass_chunks;
         const uint32_t nsub = std::max(1u, n_chunks / target);
         sub = (n_chunks + nsub - 1) / nsub;
     }

@@ -20,8 +20,9 @@ def lib():
     global _lib
     if _lib is None:
         src = os.path.join(SHIM_DIR, "pass_plan_shim.cpp")
-        deps = [src] + [os.path.join(ROOT, "flate_amd", "csrc", h)
-                        for h in ("pass_plan.h", "flate_layout.h", "flate_common.h")]
+        deps = [src, os.path.join(ROOT, "include", "flate_hip.h")] + [
+            os.path.join(ROOT, "flate_amd", "csrc", h)
+            for h in ("pass_plan.h", "stream_tables.h", "flate_layout.h", "flate_common.h")]
         if not os.path.exists(SHIM_SO) or os.path.getmtime(SHIM_SO) < max(os.path.getmtime(d) for d in deps):
             subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-fsanitize=undefined", "-fno-sanitize-recover",
                             "-fPIC", "-shared", "-o", SHIM_SO, src], check=True)

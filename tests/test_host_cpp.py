@@ -24,6 +24,24 @@ def test_facade_compiles_and_links():
     assert os.path.exists(BIN)
 
 
+def test_pass_plan_under_the_sanitizers():
+    """tests/host_cpp/test_pass_plan.cpp: a program of its own, built with AddressSanitizer and UBSan, that walks a few
+    thousand random and hostile batches (empty ones, offsets that do not grow, flush points beyond the input, nearly 2^32
+    chunks) through compress_impl's chunk table, pass walk and table builder (flate_amd/csrc/pass_plan.h).  It checks that
+    the passes cover the batch exactly once and that a pass's block count is the length of its block table; what the
+    calls decide is tests/test_compress_plan_cpu.py's business."""
+    src = os.path.join(ROOT, "tests", "host_cpp", "test_pass_plan.cpp")
+    exe = os.path.join(ROOT, "tests", "host_cpp", "test_pass_plan")
+    deps = [src, os.path.join(ROOT, "include", "flate_hip.h")] + [
+        os.path.join(ROOT, "flate_amd", "csrc", h) for h in ("pass_plan.h", "stream_tables.h", "flate_layout.h", "flate_common.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-o", exe, src],
+                       check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ok" in r.stdout
+
+
 @pytest.mark.gpu
 def test_facade_public_interface_on_gpu():
     import torch
