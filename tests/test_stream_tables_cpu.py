@@ -104,6 +104,44 @@ def test_slide_table_matches_a_model_of_the_reference_window(shim):  # noqa: F81
             assert not bad, (n, fl, t["zones"], bad[:3])
 
 
+def test_zones_with_a_flush_point_on_every_edge_of_the_first_three_slides(shim):  # noqa: F811
+    """a flush point 262, 261 and 1 bytes before the window is full for the first, second and third time, on that fill and one
+    behind it, alone and three at once: the slide table is the rule that tests/_planted_flush.py derives its expected tokens
+    from (262 bytes before the fill, or the last flush point inside those 262 bytes), and that rule is what the model of the
+    reference's window does with literal steps -- every position visited -- and with random ones"""
+    import _planted_flush as PF
+    rng = np.random.default_rng(4)
+    fills = (65536, 98304, 131072)
+    offs = (-262, -261, -1, 0, 1)
+    cases = [(135000, [full + d]) for full in fills for d in offs]
+    cases += [(135000, [full + d for full in fills]) for d in offs]
+    cases += [(135000, [65536 - 261, 65536 - 1, 98304 - 262, 98304, 131072 - 100, 131072 + 1]), (131072, [131072 - 1]), (131071, [131071 - 1])]
+    for n, fl in cases:
+        t = tables(shim, n, fl)
+        want = PF.zones(n, fl)
+        assert t["zones"] == want, (n, fl, t["zones"], want)
+        for j, full in enumerate(fills):
+            inside = [f for f in fl if full - 262 < f < full]
+            if full <= n:
+                assert want[j] == (max(inside) if inside else full - 262), (n, fl, want)
+        for literal in (True, False):
+            seen = model_bases(n, fl, True, _Ones() if literal else rng)
+            if literal:
+                assert len(seen) == n
+            bad = [(p, b, formula_base(p, want)) for p, b in seen.items() if b != formula_base(p, want)]
+            assert not bad, (n, fl, want, bad[:3])
+
+
+class _Ones:
+    """a parse of literals only: every position is visited"""
+
+    def random(self):
+        return 1.0
+
+    def integers(self, lo, hi):
+        return 1
+
+
 def test_tables_cover_the_stream(shim):  # noqa: F811
     for n, fl in CASES + [(10, [3, 3, 10]), (0, [0]), (5, [])]:
         for finish in (True, False):
