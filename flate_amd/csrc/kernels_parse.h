@@ -408,6 +408,13 @@ __device__ __forceinline__ uint32_t pz_vseg(const pz_vtab& vt, uint32_t D) {
 #define PZ_EV(K)
 #endif
 
+// index of the lowest set bit; all ones for 0 (__builtin_ctz leaves that case undefined)
+__device__ __forceinline__ uint32_t pz_ffbl(uint32_t v) {
+    uint32_t r;
+    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(v));
+    return r;
+}
+
 __device__ __forceinline__ uint32_t pz_lds4(const uint32_t* win32, uint32_t off) {
     const uint32_t* w = win32 + (off >> 2);
     return __builtin_amdgcn_alignbyte(w[1], w[0], off);
@@ -648,6 +655,7 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
         const uint32_t wabs_r = FL_MAX_DIST * ws + r0;  // stream position of relative position 0
         const bool has_fl = STREAM && fpl && nfl && (uint64_t)fl_next_flush(fpl, nfl, FL_MAX_DIST * ws, 0xffffffffu) <= (uint64_t)FL_MAX_DIST * ws + 65536u + 300u;
         const uint32_t endr = end - r0, t0r = t0 - r0;
+        uint32_t* descr = descg + r0;  // descriptors by relative position
         // STREAM: a position at or beyond the window's last target is visited AFTER the next slide (a lazy call of the window's
         // last anchor gets there): the reference has dropped every candidate at or below the next window's start by then
         // (Lookup.zig:43-51) -- relative to this window: at or below 32768
@@ -931,7 +939,7 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
         lo = p > FL_MAX_DIST ? p - FL_MAX_DIST : 1u;                           \
         if (STREAM && p >= zt) lo = max(lo, zlo);                              \
         cnt = (maxlen > best && q >= lo) ? (BUDGET) : 0u;                      \
-        PZ_SET_FILTER(best ? best - 3u : 0u);                                  \
+        PZ_SET_FILTER(__builtin_elementwise_sub_sat(best, 3u)); /* best is 0 or a match length */ \
     } while (0)
 #define PZ_LOAD_CAND()                                                         \
     do {                                                                       \
@@ -1290,28 +1298,28 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
                         PZ_EV(2);
                         // the candidate agrees where it must: its exact common prefix with p
                         uint32_t l = 0;
-                        uint64_t x;
+                        uint32_t x0, x1;
                         for (;;) {
                             PZ_EV(4);
                             PZ_CNT(c_meas, 1);
-                            uint32_t a0, a1, b0, b1, a2, a3, b2, b3;
-                            fl_lds_load8(win32, p + l, a0, a1);
-                            fl_lds_load8(win32, qh + l, b0, b1);
-                            fl_lds_load8(win32, p + l + 8u, a2, a3);
-                            fl_lds_load8(win32, qh + l + 8u, b2, b3);
-                            // (64-bit tests: all the dwords of 16 bytes are loaded together, one LDS round trip per 16 bytes -- round 6:
-                            // 1.85 trips a compare at 8)
-                            x = (uint64_t)(a0 ^ b0) | ((uint64_t)(a1 ^ b1) << 32);
-                            const uint64_t y = (uint64_t)(a2 ^ b2) | ((uint64_t)(a3 ^ b3) << 32);
-                            if (x || l + 8 >= maxlen) break;
-                            l += 8;
-                            x = y;
-                            if (x || l + 8 >= maxlen) break;
+                            // 8 bytes a side and iteration, the loads of BOTH sides asked for before the first is waited for: one LDS round
+                            // trip per 8 bytes, and a lane whose bytes differ in the first eight -- most of them -- loads no more.
+                            // (Measured, profiles/parse_visit_valu.txt: 16 bytes an iteration, and dwords read at the byte address
+                            // without v_alignbyte, issue fewer vector instructions still and are SLOWER -- the LDS is half busy.)
+                            const uint32_t pa = p + l, qa = qh + l;
+                            const uint32_t* wp = win32 + (pa >> 2);
+                            const uint32_t* wq = win32 + (qa >> 2);
+                            const uint32_t p0 = wp[0], p1 = wp[1], p2 = wp[2];
+                            const uint32_t q0 = wq[0], q1 = wq[1], q2 = wq[2];
+                            x0 = __builtin_amdgcn_alignbyte(p1, p0, pa) ^ __builtin_amdgcn_alignbyte(q1, q0, qa);
+                            x1 = __builtin_amdgcn_alignbyte(p2, p1, pa) ^ __builtin_amdgcn_alignbyte(q2, q1, qa);
+                            if ((x0 | x1) != 0 || l + 8 >= maxlen) break;
                             l += 8;
                         }
-                        // (the byte count of the last eight once, behind the loop, for all lanes together; eight equal bytes: ctz of 0
-                        // would be undefined, bit 63 of ~0 stands for "8")
-                        l = min(l + (x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u), maxlen);
+                        // (the first differing byte of the last eight, once behind the loop for all lanes together: the lowest set bit of
+                        // the two dwords.  v_ffbl_b32 gives all ones for a dword of zero, which the OR of 32 leaves as it is; eight equal
+                        // bytes give 64.  The count is capped at maxlen: what lies beyond it may say what it likes.)
+                        l = min(l + (min(min(pz_ffbl(x0), pz_ffbl(x1) | 32u), 64u) >> 3), maxlen);
                         cnt = q >= lo ? crem : 0u;            // the walk goes on behind the candidate ...
                         bool runhit = false;  // the candidate is the position before p and it is the best so far
                         if (l >= FL_MIN_MATCH && l > best) {  // deflate.zig:254-261
@@ -1414,10 +1422,12 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
                                 uint32_t desc = LITD, next = a + 1;
                                 if (plen) {
                                     PZ_EV(20);
-                                    desc = 0x80000000u | (j << 23) | ((plen - 3u) << 15) | (pdist - 1u);
+                                    // (length and distance by ONE constant: (plen << 15) + pdist has no carry between its fields and
+                                    // stays below 2^23; j is OR-ed in as it always was)
+                                    desc = (j << 23) | ((plen << 15) + pdist + (0x80000000u - (3u << 15) - 1u));
                                     next = a + j + plen;
                                 }
-                                descg[a + r0] = desc;
+                                fl_st32_off(descr, 4u * a, desc);  // (a uniform base and the lane's 32-bit offset)
                                 amask |= 1ull << (a - seg0);
                                 a = next;
                                 j = 0;
