@@ -33,6 +33,7 @@
 #include "pass_plan.h"
 #include "size_plan.h"
 #include "span_plan.h"
+#include "stream_plan.h"
 #include "stream_tables.h"
 
 namespace {
@@ -426,47 +427,53 @@ int xfer_event(flate_hip_ctx* h, size_t k, hipEvent_t* ev) {
     return FLATE_HIP_OK;
 }
 
-// Levels 4..9, whole-stream pass: tokenizer kernels (kernels_stream.h).  Leaves tokens,
-// histograms and the block table for the shared back end.
-#ifndef FL_STREAM_FIX_MAX
-#define FL_STREAM_FIX_MAX 3u  // fix launches of a grouped whole-stream pass before it is handed to the sort / match tiles
-#endif
-int compress_stream_pass(flate_hip_ctx* h, const uint8_t* d_in, const fl_params& prm, uint32_t nc, uint32_t nb,
-                         const StreamTables& t, const fl_chunk* hch /* the pass's chunks, host copy */) {
-    hipStream_t st = h->stream;
+// ---- Levels 4..9, whole-stream pass: the tokenizer kernels (kernels_stream.h).  What a pass does is decided in
+// stream_plan.h; compress_stream_pass below carries it out, stage by stage, over one record per pass.
+struct StreamPass {
+    flate_hip_ctx* h;
+    hipStream_t st;
+    const uint8_t* d_in;
+    const fl_params& prm;
+    uint32_t nc, nb;
+    const StreamTables& t;
+    const fl_chunk* hch;  // the pass's chunks, host copy
+    fl_stream_dims dims;
+    bool windows = false;    // the pass is on the windows of k_lz_parse<true> / k_lz_walk<true, true> (until it gives them up)
+    fl_stream_win win;       // ... its window and group tables
+    uint32_t round_cap = 0;  // ... rounds of a window's stitch after which the pass is given to the tiles (0: never)
+    // the tables on the device
+    const fl_chunk* dch = nullptr;  // the streams
+    const fl_chunk* dwc = nullptr;  // the windows
+    const fl_seg* dsg = nullptr;
+    const fl_piece* dpc = nullptr;
+    const uint32_t* dfp = nullptr;
+    uint32_t *d_wexit = nullptr, *d_gexit = nullptr, *d_gentry = nullptr, *d_dirty = nullptr;  // fl_wexit_layout
+};
+
+// the handle's buffer behind each name of stream_plan.h (in the order of fl_ws_buf)
+DevBuf& stream_ws_buf(flate_hip_ctx* h, fl_ws_buf id) {
+    DevBuf* const bufs[] = {&h->tiles,   &h->segs,  &h->pieces, &h->fpts,    &h->zones,   &h->nsorted, &h->cflag,
+                            &h->S,       &h->desc,  &h->tokens, &h->marks,   &h->entry,   &h->segtok,  &h->tokbase,
+                            &h->bound,   &h->ntok,  &h->wchunks, &h->swins,  &h->links,   &h->wexit,   &h->NC,
+                            &h->rec,     &h->jmp,   &h->exitmap, &h->sgroups, &h->sgroup0, &h->gmap,   &h->gentry};
+    static_assert(sizeof bufs / sizeof bufs[0] == FL_WS_COUNT, "a buffer per fl_ws_buf");
+    return *bufs[id];
+}
+int ensure_stream_ws(flate_hip_ctx* h, const fl_ws_list& need) {
     int rc;
-    const uint32_t nseg = (uint32_t)t.segs.size(), npc = (uint32_t)t.pieces.size();
-    const uint64_t npos = t.npos;
-    const size_t tile_limit = h->knobs.max_pass_chunks;
-    const size_t tiles_per_launch = std::min(t.tiles.size(), tile_limit);
-    if ((rc = ensure(h, h->tiles, sizeof(fl_tile) * t.tiles.size()))) return rc;
-    if ((rc = ensure(h, h->segs, sizeof(fl_seg) * (t.segs.size() + 1)))) return rc;
-    if ((rc = ensure(h, h->pieces, sizeof(fl_piece) * npc))) return rc;
-    if ((rc = ensure(h, h->fpts, sizeof(uint32_t) * (t.fpts.size() + 1)))) return rc;
-    if ((rc = ensure(h, h->zones, sizeof(uint32_t) * (t.zones.size() + 1)))) return rc;
-    if ((rc = ensure(h, h->nsorted, sizeof(uint32_t) * tiles_per_launch))) return rc;
-    if ((rc = ensure(h, h->cflag, sizeof(uint32_t) * tiles_per_launch))) return rc;
-    if ((rc = ensure(h, h->S, tiles_per_launch * FL_CHUNK_STRIDE * sizeof(uint16_t)))) return rc;
-    if ((rc = ensure(h, h->desc, npos * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(h, h->tokens, npos * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(h, h->marks, npos / 8))) return rc;
-    // what only the sort / match tiles and the stitch over records need (about 14 bytes per input byte): not reserved for a
-    // pass that takes the windows of k_lz_parse<true>
-    auto ensure_tile_workspace = [&]() -> int {
-        int r;
-        if ((r = ensure(h, h->NC, tiles_per_launch * FL_CHUNK_STRIDE * sizeof(uint32_t)))) return r;
-        if ((r = ensure(h, h->rec, npos * 2 * sizeof(uint32_t) + 64))) return r;
-        if ((r = ensure(h, h->jmp, npos * sizeof(uint16_t)))) return r;
-        if ((r = ensure(h, h->exitmap, ((size_t)nseg + 1) * FL_SEG_ENTRIES * sizeof(uint16_t)))) return r;
-        // positions a flush keeps out of the hash table get no record from the match finder
-        if (t.any_flush && hipMemsetAsync(h->rec.p, 0, npos * 2 * sizeof(uint32_t), st) != hipSuccess) return FLATE_HIP_E_LAUNCH;
-        return 0;
-    };
-    if ((rc = ensure(h, h->entry, sizeof(uint32_t) * (nseg + 1)))) return rc;
-    if ((rc = ensure(h, h->segtok, sizeof(uint32_t) * (nseg + 1)))) return rc;
-    if ((rc = ensure(h, h->tokbase, sizeof(uint32_t) * (nseg + 1)))) return rc;
-    if ((rc = ensure(h, h->bound, sizeof(uint32_t) * 2 * nb))) return rc;  // [nb] window positions + [nb] Q1 gaps (k_st_emit)
-    if ((rc = ensure(h, h->ntok, sizeof(uint32_t) * npc))) return rc;
+    for (uint32_t i = 0; i < need.n; i++)
+        if ((rc = ensure(h, stream_ws_buf(h, need.v[i].buf), need.v[i].bytes))) return rc;
+    return FLATE_HIP_OK;
+}
+
+// what every pass needs, reserved; its tables on the device; histograms and anchor bits cleared
+int upload_stream_tables(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const StreamTables& t = sp.t;
+    const uint32_t nseg = sp.dims.nseg, npc = sp.dims.npc;
+    int rc;
+    if ((rc = ensure_stream_ws(h, fl_stream_ws_common(sp.dims)))) return rc;
     HIP_OK(h, hipMemcpyAsync(h->tiles.p, t.tiles.data(), sizeof(fl_tile) * t.tiles.size(), hipMemcpyHostToDevice, st));
     if (nseg) HIP_OK(h, hipMemcpyAsync(h->segs.p, t.segs.data(), sizeof(fl_seg) * nseg, hipMemcpyHostToDevice, st));
     HIP_OK(h, hipMemcpyAsync(h->pieces.p, t.pieces.data(), sizeof(fl_piece) * npc, hipMemcpyHostToDevice, st));
@@ -474,264 +481,241 @@ int compress_stream_pass(flate_hip_ctx* h, const uint8_t* d_in, const fl_params&
         HIP_OK(h, hipMemcpyAsync(h->fpts.p, t.fpts.data(), sizeof(uint32_t) * t.fpts.size(), hipMemcpyHostToDevice, st));
     if (!t.zones.empty())
         HIP_OK(h, hipMemcpyAsync(h->zones.p, t.zones.data(), sizeof(uint32_t) * t.zones.size(), hipMemcpyHostToDevice, st));
-    HIP_OK(h, hipMemsetAsync(h->hist.p, 0, sizeof(uint32_t) * 320 * (size_t)nb, st));
-    HIP_OK(h, hipMemsetAsync(h->marks.p, 0, npos / 8, st));
+    HIP_OK(h, hipMemsetAsync(h->hist.p, 0, sizeof(uint32_t) * 320 * (size_t)sp.nb, st));
+    HIP_OK(h, hipMemsetAsync(h->marks.p, 0, sp.dims.npos / 8, st));
     HIP_OK(h, hipStreamSynchronize(st));  // the host vectors must outlive the async copies
+    sp.dch = (const fl_chunk*)h->chunks.p;
+    sp.dsg = (const fl_seg*)h->segs.p;
+    sp.dpc = (const fl_piece*)h->pieces.p;
+    sp.dfp = (const uint32_t*)h->fpts.p;
+    return FLATE_HIP_OK;
+}
 
-    const fl_chunk* dch = (const fl_chunk*)h->chunks.p;
-    const fl_seg* dsg = (const fl_seg*)h->segs.p;
-    const fl_piece* dpc = (const fl_piece*)h->pieces.p;
-    const uint32_t* dfp = (const uint32_t*)h->fpts.p;
-    // Round 5: many streams, none of them with flush points, levels 4-7: the demand-driven tokenizer of the chunk path walks
-    // every stream's windows in order, a workgroup per stream (kernels_parse.h, k_lz_parse<true>) -- no sort, no records for
-    // every position.  A window costs a workgroup about 0.28 ms, the sort / match pair about 0.061 ms per MiB of all CUs.
-    // Round 6: levels 8 and 9 the same way on k_lz_links / k_lz_walk<true, true> (kernels_walk.h).
-    const bool deep_walk = prm.chain >= FL_BULK_MIN_CHAIN;
-    // (sync-flush points: levels 4-7 only -- k_lz_chain keeps the three positions before a flush point out of the table and
-    // k_lz_parse<true> ends every match there; the run logic of k_lz_walk counts on runs whose every position is in the table)
-    bool windows = !(t.any_flush && deep_walk) && h->knobs.stream_windows != 0 && nseg;
-    std::vector<fl_chunk> wch;
-    std::vector<fl_swin> sws;
-    bool grouped = false;  // some stream is split into groups of windows: a fix launch follows (kernels_parse.h)
-    uint32_t round_cap = 0;  // rounds of a window's stitch after which the pass is given to the tiles (0: never)
-    if (windows) {
-        const uint32_t n_cu = device_cu_count(h);
-        uint64_t bytes = 0, total_win = 0;
-        for (uint32_t i = 0; i < nc; i++) {
-            bytes += hch[i].in_len;
-            total_win += hch[i].n_slides + 1u;
-        }
-        // Many streams: a workgroup walks a whole stream (no guess, no fix).  Fewer than the chip holds workgroups at a time (one a
-        // CU; levels 8-9: two): groups of G windows, as many groups as it holds, so that they all end together and the fix launch
-        // -- which parses one window (a sub-pass) per group again -- is one round: G + 1 window times.  (Round 5 took four groups
-        // per CU of at least four windows: one 1 MiB stream at level 6 cost 1.9 ms against 1.05 as 32 groups of one window, and
-        // 1.34 on the sort / match tiles; one 177 MB stream at level 9 as 675 groups of 8 took 2 x 8 + 2 window times, as 491
-        // groups of 11 it takes 11 + 1.  tools/small_stream_round.sh)
-        const uint64_t slots = deep_walk ? 2ull * n_cu : (uint64_t)n_cu;
-        uint32_t G = ~0u;
-        if (nc < slots) G = (uint32_t)std::max<uint64_t>(1, (total_win + slots - 1) / slots);
-        if (h->knobs.stream_group) G = h->knobs.stream_group;
-        for (uint32_t i = 0; i < nc; i++) {
-            const fl_chunk& c = hch[i];
-            const uint32_t nw = c.n_slides + 1u, w0 = (uint32_t)wch.size();
-            for (uint32_t j = 0; j < nw; j++) {
-                fl_chunk w{};
-                w.in_off = c.in_off + (uint64_t)FL_SEG * j;
-                w.in_len = (uint32_t)std::min<uint64_t>(65536u, (uint64_t)c.in_len - (uint64_t)FL_SEG * j);
-                w.pad_ = 1u;  // (a window: k_lz_chain builds its chains whatever it holds)
-                w.piece0 = FL_SEG * j;  // the window's position in its stream, and the stream's flush points (k_lz_chain)
-                w.flush_off = c.flush_off;
-                w.n_flush = c.n_flush;
-                // (+ the bytes behind the window that the lazy calls of its last anchor look at: kernels_parse.h, kernels_walk.h)
-                w.pad_ |= (uint32_t)std::min<uint64_t>(264u, (uint64_t)c.in_len - (uint64_t)FL_SEG * j - w.in_len) << 8;
-                wch.push_back(w);
-            }
-            uint32_t prev = ~0u;
-            for (uint32_t j = 0; j < nw; j += G) {
-                fl_swin sw{};
-                sw.chunk = i;
-                sw.win0 = w0 + j;
-                sw.nwin = std::min(G, nw - j);
-                sw.wfirst = j;
-                sw.prev = prev;
-                prev = (uint32_t)sws.size();
-                if (j) grouped = true;
-                sws.push_back(sw);
-                if (G == ~0u) break;
-            }
-        }
-        const uint32_t ng = (uint32_t)sws.size();
-        const uint32_t gmax = G == ~0u ? (uint32_t)0 : G;
-        uint32_t max_win = 0;
-        for (const fl_swin& sw : sws) max_win = std::max(max_win, sw.nwin);
-        (void)gmax;
-        // A window costs a workgroup about 0.28 ms (levels 8-9: 1.2, text 1.1, TAR-like 1.6), the fix launch one more per round and
-        // a host wait; sort / match cost about 0.061 ms per MiB on all CUs (levels 8-9: 0.11 text, 0.20 TAR-like) and 0.8 (1.3) ms
-        // of kernel latencies whatever the size.
-        if (bytes < (64ull << 20) && nc < slots) round_cap = 24u;
-        const uint64_t rounds = (ng + slots - 1) / slots;
-        const double win_ms = deep_walk ? 1.5 : 0.28;
-        const double est_new = (double)rounds * max_win * win_ms + (grouped ? (double)rounds * win_ms + 0.1 : 0.0);
-        const double est_old = (double)bytes / 1048576.0 * (deep_walk ? 0.11 : 0.061) + (deep_walk ? 1.3 : 0.8);
-        if (h->knobs.stream_windows < 0 && est_new >= est_old) windows = false;
-        if (wch.size() > tile_limit) windows = false;  // (the chain links of all windows at once: 128 KiB each)
-        // (levels 8-9: 512 KiB of links a window -- 16 GiB for a 1 GiB stream; a device that cannot give them: the tiles)
-        if (windows && deep_walk && ensure(h, h->links, wch.size() * FL_CHUNK_STRIDE * 4 * sizeof(uint16_t))) {
-            (void)hipGetLastError();
-            windows = false;
-        }
+// windows or tiles (stream_plan.h: the rules and why); the one thing decided here is what only the device can say
+void plan_stream_windows(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    const bool deep_walk = sp.dims.deep_walk;
+    sp.windows = fl_stream_windows_allowed(sp.t.any_flush, deep_walk, h->knobs.stream_windows, sp.dims.nseg);
+    if (!sp.windows) return;
+    fl_stream_windows(sp.hch, sp.nc, h->knobs.stream_group, device_cu_count(h), deep_walk, sp.win);
+    const fl_stream_choice choice = fl_stream_estimate(sp.win, sp.nc, deep_walk, h->knobs.stream_windows, h->knobs.max_pass_chunks);
+    sp.round_cap = choice.round_cap;
+    sp.windows = choice.windows;
+    // (levels 8-9: a device that cannot give the windows' links: the tiles)
+    if (sp.windows && deep_walk && !room(h, h->links, fl_stream_links_bytes((uint32_t)sp.win.wch.size()))) sp.windows = false;
+}
+
+// the windows' workspace, reserved; the window and group tables on the device
+int upload_stream_windows(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const uint32_t nw = (uint32_t)sp.win.wch.size(), ng = (uint32_t)sp.win.sws.size();
+    int rc;
+    if ((rc = ensure_stream_ws(h, fl_stream_ws_windows(sp.dims, nw, ng)))) return rc;
+    const fl_wexit_layout x = fl_wexit_offsets(nw, ng);
+    sp.d_wexit = (uint32_t*)h->wexit.p + x.wexit;
+    sp.d_gexit = (uint32_t*)h->wexit.p + x.gexit;
+    sp.d_gentry = (uint32_t*)h->wexit.p + x.gentry;
+    sp.d_dirty = (uint32_t*)h->wexit.p + x.dirty;
+    HIP_OK(h, hipMemcpyAsync(h->wchunks.p, sp.win.wch.data(), sizeof(fl_chunk) * nw, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->swins.p, sp.win.sws.data(), sizeof(fl_swin) * ng, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));  // the host vectors must outlive the async copies
+    sp.dwc = (const fl_chunk*)h->wchunks.p;
+    return FLATE_HIP_OK;
+}
+
+// the tokenizer over the groups of windows: the first launch (fix = 0), or one from the groups' true entries (fix = 1)
+void launch_stream_tokenizer(StreamPass& sp, uint32_t fix) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const uint32_t ng = (uint32_t)sp.win.sws.size();
+    fix |= sp.round_cap << 8;
+    if (sp.dims.deep_walk) {
+        ProfScope ps(h, K_LZ_WALK);
+        wk_stream ws{(const fl_swin*)h->swins.p, sp.dch, (const uint32_t*)h->zones.p, sp.d_gexit, sp.d_gentry, sp.d_wexit, sp.d_dirty, fix};
+        hipLaunchKernelGGL((k_lz_walk<true, true>), dim3(ng), dim3(WK_THREADS), 0, st, sp.d_in, sp.dwc, sp.prm, (const uint16_t*)h->links.p,
+                           (const uint32_t*)h->cflag.p, (uint32_t*)h->desc.p, (uint32_t*)h->marks.p, ws);
+    } else {
+        ProfScope ps(h, K_LZ_PARSE);
+        hipLaunchKernelGGL(k_lz_parse<true>, dim3(ng), dim3(PZ_THREADS), 0, st, sp.d_in, sp.dwc, sp.prm,
+                           (const uint16_t*)h->S.p, (const uint32_t*)h->cflag.p, (uint32_t*)h->desc.p, (uint32_t*)h->marks.p,
+                           (const fl_swin*)h->swins.p, sp.dch, (const uint32_t*)h->zones.p, sp.d_gexit, sp.d_gentry, sp.d_wexit, sp.d_dirty, fix,
+                           sp.t.any_flush ? sp.dfp : (const uint32_t*)nullptr);
     }
-    if (windows) {
-        const uint32_t nw = (uint32_t)wch.size(), ng = (uint32_t)sws.size();
-        if ((rc = ensure(h, h->wchunks, sizeof(fl_chunk) * nw))) return rc;
-        if ((rc = ensure(h, h->swins, sizeof(fl_swin) * ng))) return rc;
-        if (deep_walk) {
-            if ((rc = ensure(h, h->links, (size_t)nw * FL_CHUNK_STRIDE * 4 * sizeof(uint16_t)))) return rc;
-        } else {
-            if ((rc = ensure(h, h->S, (size_t)nw * FL_CHUNK_STRIDE * sizeof(uint16_t)))) return rc;
-        }
-        if ((rc = ensure(h, h->cflag, sizeof(uint32_t) * nw))) return rc;
-        if ((rc = ensure(h, h->wexit, sizeof(uint32_t) * (2 * (size_t)nw + 2 * (size_t)ng + 4)))) return rc;
-        uint32_t* d_wexit = (uint32_t*)h->wexit.p;
-        uint32_t* d_gexit = d_wexit + 2 * (size_t)nw;
-        uint32_t* d_gentry = d_gexit + ng;
-        uint32_t* d_dirty = d_gentry + ng;
-        HIP_OK(h, hipMemcpyAsync(h->wchunks.p, wch.data(), sizeof(fl_chunk) * nw, hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipMemcpyAsync(h->swins.p, sws.data(), sizeof(fl_swin) * ng, hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipStreamSynchronize(st));  // the host vectors must outlive the async copies
-        const fl_chunk* dwc = (const fl_chunk*)h->wchunks.p;
-        // the tokenizer over the groups of windows: the first launch (fix = 0), or one from the groups' true entries (fix = 1)
-        // (a small pass of few streams -- where round 5 took the tiles -- gives a window up after 24 rounds of its stitch: periodic data)
-        auto launch_tokenizer = [&](uint32_t fix) {
-            fix |= round_cap << 8;
-            if (deep_walk) {
-                ProfScope ps(h, K_LZ_WALK);
-                wk_stream sp{(const fl_swin*)h->swins.p, dch, (const uint32_t*)h->zones.p, d_gexit, d_gentry, d_wexit, d_dirty, fix};
-                hipLaunchKernelGGL((k_lz_walk<true, true>), dim3(ng), dim3(WK_THREADS), 0, st, d_in, dwc, prm, (const uint16_t*)h->links.p,
-                                   (const uint32_t*)h->cflag.p, (uint32_t*)h->desc.p, (uint32_t*)h->marks.p, sp);
-            } else {
-                ProfScope ps(h, K_LZ_PARSE);
-                hipLaunchKernelGGL(k_lz_parse<true>, dim3(ng), dim3(PZ_THREADS), 0, st, d_in, dwc, prm,
-                                   (const uint16_t*)h->S.p, (const uint32_t*)h->cflag.p, (uint32_t*)h->desc.p, (uint32_t*)h->marks.p,
-                                   (const fl_swin*)h->swins.p, dch, (const uint32_t*)h->zones.p, d_gexit, d_gentry, d_wexit, d_dirty, fix,
-                                   t.any_flush ? dfp : (const uint32_t*)nullptr);
-            }
-        };
-        if (deep_walk) {
-            ProfScope ps(h, K_LZ_LINKS);
-            hipLaunchKernelGGL(k_lz_links<0>, dim3(nw), dim3(64 * FL_CHAIN_WAVES), 0, st, d_in, dwc, (uint16_t*)h->links.p, (uint32_t*)h->cflag.p);
-            hipLaunchKernelGGL(k_lz_links<1>, dim3(nw), dim3(64 * FL_CHAIN_WAVES), 0, st, d_in, dwc, (uint16_t*)h->links.p, (uint32_t*)h->cflag.p);
-            hipLaunchKernelGGL(k_lz_links<2>, dim3(nw), dim3(64 * FL_CHAIN_WAVES), 0, st, d_in, dwc, (uint16_t*)h->links.p, (uint32_t*)h->cflag.p);
-            hipLaunchKernelGGL(k_lz_links<3>, dim3(nw), dim3(64 * FL_CHAIN_WAVES), 0, st, d_in, dwc, (uint16_t*)h->links.p, (uint32_t*)h->cflag.p);
-        } else {
-            ProfScope ps(h, K_LZ_CHAIN);
-            if (t.any_flush)
-                hipLaunchKernelGGL(k_lz_chain<true>, dim3(nw), dim3(64 * FL_CHAIN_WAVES), 0, st, d_in, dwc,
-                                   (uint16_t*)h->S.p, (uint32_t*)h->cflag.p, (uint32_t*)nullptr, dfp);
-            else
-                hipLaunchKernelGGL(k_lz_chain<false>, dim3(nw), dim3(64 * FL_CHAIN_WAVES), 0, st, d_in, dwc,
-                                   (uint16_t*)h->S.p, (uint32_t*)h->cflag.p, (uint32_t*)nullptr, (const uint32_t*)nullptr);
-        }
-        HIP_OK(h, hipMemsetAsync(d_dirty, 0, sizeof(uint32_t), st));
-        launch_tokenizer(0u);
-        // the groups that were parsed from a guess: again from where the group before them leaves, until nothing moves any more
-        // (one launch in practice: a parse falls in step within a few bytes; the loop is what makes it exact).  NOT on
-        // periodic data: in a stream of one repeated byte every anchor is a 258-byte match, a parse from a guessed entry never
-        // meets the true one, and every launch settles one more group (about ng launches).  After FL_STREAM_FIX_MAX
-        // launches the pass is given to the sort / match tiles, which cost the same whatever the data.
-        bool gave_up = false;
-        {
-            // (bit 31: some window's stitch did not settle within the round cap -- periodic data -- and its workgroup has stopped)
-            uint32_t flag = 0;
-            HIP_OK(h, hipMemcpyAsync(&flag, d_dirty, sizeof flag, hipMemcpyDeviceToHost, st));
-            HIP_OK(h, hipStreamSynchronize(st));
-            gave_up = (flag & 0x80000000u) != 0;
-        }
-        for (uint32_t it = 0; grouped && !gave_up; it++) {
-            HIP_OK(h, hipMemsetAsync(d_dirty, 0, sizeof(uint32_t), st));
-            launch_tokenizer(1u);
-            uint32_t flag = 0;
-            HIP_OK(h, hipMemcpyAsync(&flag, d_dirty, sizeof flag, hipMemcpyDeviceToHost, st));
-            HIP_OK(h, hipStreamSynchronize(st));
-            if (!flag) break;
-            // (`flag` = the groups that were parsed to their end with a new exit.  Text: none after the first fix launch.  More than
-            // an eighth of them: periodic data -- every launch settles one group per stream -- and no reason to try twice more)
-            if (it + 1 >= FL_STREAM_FIX_MAX || flag > ng / 8 + 1) {  // (incl. bit 31: a window that does not settle)
-                gave_up = true;
-                break;
-            }
-        }
-        if (gave_up) {
-            windows = false;  // the tiles below; the anchors marked so far go
-            HIP_OK(h, hipMemsetAsync(h->marks.p, 0, npos / 8, st));
-            if ((rc = ensure(h, h->nsorted, sizeof(uint32_t) * tiles_per_launch))) return rc;
-            if ((rc = ensure(h, h->cflag, sizeof(uint32_t) * tiles_per_launch))) return rc;
-            if ((rc = ensure(h, h->S, tiles_per_launch * FL_CHUNK_STRIDE * sizeof(uint16_t)))) return rc;
-        } else {
-            ProfScope ps(h, K_ST_PARSE);
-            hipLaunchKernelGGL(k_st_count, dim3(nseg), dim3(FL_PARSE_THREADS), 0, st, dch, dpc, dsg, (const uint32_t*)h->desc.p,
-                               (const uint32_t*)h->marks.p, (uint32_t*)h->segtok.p);
-        }
+}
+
+// the chains of every window: the four link arrays of levels 8-9, or the one of levels 4-7
+void build_stream_chains(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const dim3 grid((uint32_t)sp.win.wch.size()), block(64 * FL_CHAIN_WAVES);
+    if (sp.dims.deep_walk) {
+        ProfScope ps(h, K_LZ_LINKS);
+        void (*const links[4])(const uint8_t*, const fl_chunk*, uint16_t*, uint32_t*) = {k_lz_links<0>, k_lz_links<1>, k_lz_links<2>, k_lz_links<3>};
+        for (auto k : links) hipLaunchKernelGGL(k, grid, block, 0, st, sp.d_in, sp.dwc, (uint16_t*)h->links.p, (uint32_t*)h->cflag.p);
+    } else {
+        ProfScope ps(h, K_LZ_CHAIN);
+        if (sp.t.any_flush)
+            hipLaunchKernelGGL(k_lz_chain<true>, grid, block, 0, st, sp.d_in, sp.dwc, (uint16_t*)h->S.p, (uint32_t*)h->cflag.p,
+                               (uint32_t*)nullptr, sp.dfp);
+        else
+            hipLaunchKernelGGL(k_lz_chain<false>, grid, block, 0, st, sp.d_in, sp.dwc, (uint16_t*)h->S.p, (uint32_t*)h->cflag.p,
+                               (uint32_t*)nullptr, (const uint32_t*)nullptr);
     }
-    if (!windows && (rc = ensure_tile_workspace())) return rc;
-    for (size_t t0 = 0; !windows && t0 < t.tiles.size(); t0 += tiles_per_launch) {
+}
+
+// the dirty word behind the launch just enqueued, and what it means (fl_fix_verdict)
+int read_fix_verdict(StreamPass& sp, uint32_t it, fl_fix& verdict) {
+    flate_hip_ctx* h = sp.h;
+    uint32_t flag = 0;
+    HIP_OK(h, hipMemcpyAsync(&flag, sp.d_dirty, sizeof flag, hipMemcpyDeviceToHost, sp.st));
+    HIP_OK(h, hipStreamSynchronize(sp.st));
+    verdict = fl_fix_verdict(it, flag, (uint32_t)sp.win.sws.size());
+    return FLATE_HIP_OK;
+}
+
+// The tokenizer over the windows, and for a grouped pass its fix launches until nothing moves any more.  A pass that gives
+// up goes to the tiles (the anchors marked so far go); one that settles counts its segments' tokens.
+int run_stream_windows(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    int rc;
+    if ((rc = upload_stream_windows(sp))) return rc;
+    build_stream_chains(sp);
+    HIP_OK(h, hipMemsetAsync(sp.d_dirty, 0, sizeof(uint32_t), st));
+    launch_stream_tokenizer(sp, 0u);
+    fl_fix verdict;
+    if ((rc = read_fix_verdict(sp, FL_FIX_FIRST, verdict))) return rc;
+    for (uint32_t it = 0; sp.win.grouped && verdict == FL_FIX_AGAIN; it++) {
+        HIP_OK(h, hipMemsetAsync(sp.d_dirty, 0, sizeof(uint32_t), st));
+        launch_stream_tokenizer(sp, 1u);
+        if ((rc = read_fix_verdict(sp, it, verdict))) return rc;
+    }
+    if (verdict == FL_FIX_GIVE_UP) {
+        sp.windows = false;
+        // (the tiles' sort scratch is what upload_stream_tables reserved: buffers only grow)
+        HIP_OK(h, hipMemsetAsync(h->marks.p, 0, sp.dims.npos / 8, st));
+    } else {
+        ProfScope ps(h, K_ST_PARSE);
+        hipLaunchKernelGGL(k_st_count, dim3(sp.dims.nseg), dim3(FL_PARSE_THREADS), 0, st, sp.dch, sp.dpc, sp.dsg, (const uint32_t*)h->desc.p,
+                           (const uint32_t*)h->marks.p, (uint32_t*)h->segtok.p);
+    }
+    return FLATE_HIP_OK;
+}
+
+// sort / match over the 64 KiB tiles: a record for every position
+int run_stream_tiles(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const StreamTables& t = sp.t;
+    const size_t tiles_per_launch = sp.dims.tiles_per_launch;
+    int rc;
+    if ((rc = ensure_stream_ws(h, fl_stream_ws_tiles(sp.dims)))) return rc;
+    // positions a flush keeps out of the hash table get no record from the match finder
+    if (t.any_flush && hipMemsetAsync(h->rec.p, 0, fl_stream_rec_bytes(sp.dims.npos), st) != hipSuccess) return FLATE_HIP_E_LAUNCH;
+    for (size_t t0 = 0; t0 < t.tiles.size(); t0 += tiles_per_launch) {
         const uint32_t nt = (uint32_t)std::min(tiles_per_launch, t.tiles.size() - t0);
         const fl_tile* dti = (const fl_tile*)h->tiles.p + t0;
         {
             ProfScope ps(h, K_LZ_SORT);
-            hipLaunchKernelGGL(k_lz_sort<true>, dim3(nt), dim3(FL_SORT_THREADS), 0, st, d_in, dch, dti, dfp,
+            hipLaunchKernelGGL(k_lz_sort<true>, dim3(nt), dim3(FL_SORT_THREADS), 0, st, sp.d_in, sp.dch, dti, sp.dfp,
                                (uint32_t*)h->nsorted.p, (uint16_t*)h->S.p,
                                (uint32_t*)h->cflag.p);
         }
         {
             ProfScope ps(h, K_LZ_MATCH);
             const uint32_t* cf = (const uint32_t*)h->cflag.p;
-            hipLaunchKernelGGL((k_lz_match<true, true, false>), dim3(nt), dim3(FL_MATCH_THREADS), 0, st, d_in, dch, dti,
-                               dfp, (const uint32_t*)h->nsorted.p, prm, (const uint16_t*)h->S.p, (uint32_t*)h->NC.p,
+            hipLaunchKernelGGL((k_lz_match<true, true, false>), dim3(nt), dim3(FL_MATCH_THREADS), 0, st, sp.d_in, sp.dch, dti,
+                               sp.dfp, (const uint32_t*)h->nsorted.p, sp.prm, (const uint16_t*)h->S.p, (uint32_t*)h->NC.p,
                                (uint32_t*)h->rec.p, cf);
             // the tiles k_lz_sort marked runny
-            hipLaunchKernelGGL((k_lz_match<true, true, true>), dim3(nt), dim3(FL_MATCH_THREADS), 0, st, d_in, dch,
-                               dti, dfp, (const uint32_t*)h->nsorted.p, prm, (const uint16_t*)h->S.p,
+            hipLaunchKernelGGL((k_lz_match<true, true, true>), dim3(nt), dim3(FL_MATCH_THREADS), 0, st, sp.d_in, sp.dch,
+                               dti, sp.dfp, (const uint32_t*)h->nsorted.p, sp.prm, (const uint16_t*)h->S.p,
                                (uint32_t*)h->NC.p, (uint32_t*)h->rec.p, cf);
         }
     }
-    if (nseg && !windows) {
-        ProfScope ps(h, K_ST_PARSE);
-        hipLaunchKernelGGL(k_st_parse1, dim3(nseg), dim3(FL_PARSE_THREADS), 0, st, dch, dpc, dsg, prm,
-                           (const uint32_t*)h->rec.p, (uint32_t*)h->desc.p, (uint16_t*)h->jmp.p,
-                           (uint16_t*)h->exitmap.p);
-        // the walk from segment to segment: directly for short pieces, over groups of segments
-        // when some piece is long (kernels_stream.h)
-        uint32_t max_seg = 0;
-        for (const fl_piece& pc : t.pieces) max_seg = std::max(max_seg, pc.n_seg);
-        if (max_seg <= 4 * FL_STITCH_GROUP) {
-            hipLaunchKernelGGL(k_st_stitch, dim3((npc + 63) / 64), dim3(64), 0, st, dpc, npc, dsg,
-                               (const uint16_t*)h->exitmap.p, (uint32_t*)h->entry.p);
-        } else {
-            std::vector<fl_sgroup> groups;
-            std::vector<uint32_t> group0(npc);
-            for (uint32_t i = 0; i < npc; i++) {
-                group0[i] = (uint32_t)groups.size();
-                for (uint32_t g = 0; g * FL_STITCH_GROUP < t.pieces[i].n_seg; g++) groups.push_back(fl_sgroup{i, g});
-            }
-            const uint32_t ngr = (uint32_t)groups.size();
-            if ((rc = ensure(h, h->sgroups, sizeof(fl_sgroup) * (ngr + 1)))) return rc;
-            if ((rc = ensure(h, h->sgroup0, sizeof(uint32_t) * npc))) return rc;
-            if ((rc = ensure(h, h->gmap, ((size_t)ngr + 1) * FL_SEG_ENTRIES * sizeof(uint16_t)))) return rc;
-            if ((rc = ensure(h, h->gentry, sizeof(uint32_t) * (ngr + 1)))) return rc;
-            HIP_OK(h, hipMemcpyAsync(h->sgroups.p, groups.data(), sizeof(fl_sgroup) * ngr, hipMemcpyHostToDevice, st));
-            HIP_OK(h, hipMemcpyAsync(h->sgroup0.p, group0.data(), sizeof(uint32_t) * npc, hipMemcpyHostToDevice, st));
-            HIP_OK(h, hipStreamSynchronize(st));
-            if (ngr) {
-                hipLaunchKernelGGL(k_st_stitch_a, dim3(ngr), dim3(FL_SEG_ENTRIES), 0, st, dpc,
-                                   (const fl_sgroup*)h->sgroups.p, dsg, (const uint16_t*)h->exitmap.p,
-                                   (uint16_t*)h->gmap.p);
-                hipLaunchKernelGGL(k_st_stitch_b, dim3((npc + 63) / 64), dim3(64), 0, st, dpc, npc,
-                                   (const uint32_t*)h->sgroup0.p, dsg, (const uint16_t*)h->gmap.p,
-                                   (uint32_t*)h->gentry.p);
-                hipLaunchKernelGGL(k_st_stitch_c, dim3((ngr + 63) / 64), dim3(64), 0, st, dpc,
-                                   (const fl_sgroup*)h->sgroups.p, ngr, dsg, (const uint16_t*)h->exitmap.p,
-                                   (const uint32_t*)h->gentry.p, (uint32_t*)h->entry.p);
-            }
-        }
-        hipLaunchKernelGGL(k_st_parse2, dim3(nseg), dim3(FL_PARSE_THREADS), 0, st, dch, dpc, dsg,
-                           (const uint32_t*)h->desc.p, (const uint16_t*)h->jmp.p, (const uint32_t*)h->entry.p,
-                           (uint32_t*)h->marks.p, (uint32_t*)h->segtok.p);
+    return FLATE_HIP_OK;
+}
+
+// the walk from segment to segment over groups of segments (fl_stitch_plan: some piece is long)
+int stitch_stream_groups(StreamPass& sp, const fl_stitch_tables& s) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const uint32_t npc = sp.dims.npc, ngr = (uint32_t)s.groups.size();
+    int rc;
+    if ((rc = ensure_stream_ws(h, fl_stream_ws_stitch(ngr, npc)))) return rc;
+    HIP_OK(h, hipMemcpyAsync(h->sgroups.p, s.groups.data(), sizeof(fl_sgroup) * ngr, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->sgroup0.p, s.group0.data(), sizeof(uint32_t) * npc, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));
+    if (!ngr) return FLATE_HIP_OK;
+    hipLaunchKernelGGL(k_st_stitch_a, dim3(ngr), dim3(FL_SEG_ENTRIES), 0, st, sp.dpc,
+                       (const fl_sgroup*)h->sgroups.p, sp.dsg, (const uint16_t*)h->exitmap.p,
+                       (uint16_t*)h->gmap.p);
+    hipLaunchKernelGGL(k_st_stitch_b, dim3((npc + 63) / 64), dim3(64), 0, st, sp.dpc, npc,
+                       (const uint32_t*)h->sgroup0.p, sp.dsg, (const uint16_t*)h->gmap.p,
+                       (uint32_t*)h->gentry.p);
+    hipLaunchKernelGGL(k_st_stitch_c, dim3((ngr + 63) / 64), dim3(64), 0, st, sp.dpc,
+                       (const fl_sgroup*)h->sgroups.p, ngr, sp.dsg, (const uint16_t*)h->exitmap.p,
+                       (const uint32_t*)h->gentry.p, (uint32_t*)h->entry.p);
+    return FLATE_HIP_OK;
+}
+
+// the tiles' records into anchors: every segment for each entry it can be handed, the stitch, every segment from its own
+int parse_stream_records(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const uint32_t nseg = sp.dims.nseg, npc = sp.dims.npc;
+    int rc;
+    ProfScope ps(h, K_ST_PARSE);
+    hipLaunchKernelGGL(k_st_parse1, dim3(nseg), dim3(FL_PARSE_THREADS), 0, st, sp.dch, sp.dpc, sp.dsg, sp.prm,
+                       (const uint32_t*)h->rec.p, (uint32_t*)h->desc.p, (uint16_t*)h->jmp.p,
+                       (uint16_t*)h->exitmap.p);
+    fl_stitch_tables stitch;
+    fl_stitch_plan(sp.t.pieces.data(), npc, stitch);
+    if (stitch.direct) {
+        hipLaunchKernelGGL(k_st_stitch, dim3((npc + 63) / 64), dim3(64), 0, st, sp.dpc, npc, sp.dsg,
+                           (const uint16_t*)h->exitmap.p, (uint32_t*)h->entry.p);
+    } else if ((rc = stitch_stream_groups(sp, stitch))) {
+        return rc;
     }
-    {
-        ProfScope ps(h, K_ST_EMIT);
-        hipLaunchKernelGGL(k_st_scan, dim3(npc), dim3(64), 0, st, dpc, (const uint32_t*)h->segtok.p,
-                           (uint32_t*)h->tokbase.p, (uint32_t*)h->ntok.p);
-        if (nseg)
-            hipLaunchKernelGGL(k_st_emit, dim3(nseg), dim3(FL_EMIT_THREADS), 0, st, d_in, dch, dpc, dsg, prm,
-                               (const uint32_t*)h->desc.p, (const uint32_t*)h->marks.p,
-                               (const uint32_t*)h->tokbase.p, (uint32_t*)h->tokens.p, (uint32_t*)h->hist.p,
-                               (uint32_t*)h->bound.p, (uint32_t*)h->bound.p + nb);
-        hipLaunchKernelGGL(k_st_blocks, dim3(npc), dim3(64), 0, st, dch, dpc, (const uint32_t*)h->ntok.p,
-                           (const uint32_t*)h->bound.p, (const uint32_t*)h->bound.p + nb, prm.flags & FL_PRM_REPAIR_Q1,
-                           (const uint32_t*)h->zones.p, (fl_block_plan*)h->plans.p);
+    hipLaunchKernelGGL(k_st_parse2, dim3(nseg), dim3(FL_PARSE_THREADS), 0, st, sp.dch, sp.dpc, sp.dsg,
+                       (const uint32_t*)h->desc.p, (const uint16_t*)h->jmp.p, (const uint32_t*)h->entry.p,
+                       (uint32_t*)h->marks.p, (uint32_t*)h->segtok.p);
+    return FLATE_HIP_OK;
+}
+
+// tokens numbered through every piece, written with their histograms, cut into blocks
+void emit_stream_tokens(StreamPass& sp) {
+    flate_hip_ctx* h = sp.h;
+    hipStream_t st = sp.st;
+    const uint32_t nseg = sp.dims.nseg, npc = sp.dims.npc, nb = sp.nb;
+    ProfScope ps(h, K_ST_EMIT);
+    hipLaunchKernelGGL(k_st_scan, dim3(npc), dim3(64), 0, st, sp.dpc, (const uint32_t*)h->segtok.p,
+                       (uint32_t*)h->tokbase.p, (uint32_t*)h->ntok.p);
+    if (nseg)
+        hipLaunchKernelGGL(k_st_emit, dim3(nseg), dim3(FL_EMIT_THREADS), 0, st, sp.d_in, sp.dch, sp.dpc, sp.dsg, sp.prm,
+                           (const uint32_t*)h->desc.p, (const uint32_t*)h->marks.p,
+                           (const uint32_t*)h->tokbase.p, (uint32_t*)h->tokens.p, (uint32_t*)h->hist.p,
+                           (uint32_t*)h->bound.p, (uint32_t*)h->bound.p + nb);
+    hipLaunchKernelGGL(k_st_blocks, dim3(npc), dim3(64), 0, st, sp.dch, sp.dpc, (const uint32_t*)h->ntok.p,
+                       (const uint32_t*)h->bound.p, (const uint32_t*)h->bound.p + nb, sp.prm.flags & FL_PRM_REPAIR_Q1,
+                       (const uint32_t*)h->zones.p, (fl_block_plan*)h->plans.p);
+}
+
+// Leaves tokens, histograms and the block table for the shared back end.
+int compress_stream_pass(flate_hip_ctx* h, const uint8_t* d_in, const fl_params& prm, uint32_t nc, uint32_t nb,
+                         const StreamTables& t, const fl_chunk* hch /* the pass's chunks, host copy */) {
+    StreamPass sp{h, h->stream, d_in, prm, nc, nb, t, hch};
+    sp.dims = fl_stream_dims_of(t, nb, h->knobs.max_pass_chunks, fl_stream_deep_walk(prm.chain));
+    int rc;
+    if ((rc = upload_stream_tables(sp))) return rc;
+    plan_stream_windows(sp);
+    if (sp.windows && (rc = run_stream_windows(sp))) return rc;  // (may hand the pass to the tiles)
+    if (!sp.windows) {
+        if ((rc = run_stream_tiles(sp))) return rc;
+        if (sp.dims.nseg && (rc = parse_stream_records(sp))) return rc;
     }
-    (void)nc;
+    emit_stream_tokens(sp);
     return FLATE_HIP_OK;
 }
 

@@ -57,6 +57,31 @@ struct fl_seg {
     uint32_t h0;  // multiple of 32768
 };
 
+// Levels whose chain budget reaches this value keep the match finder of kernels_lz.h on the chunk path and take the
+// sparse-chain kernels (kernels_walk.h) for a whole-stream pass's windows (flate_hip.hip, stream_plan.h).
+#ifndef FL_BULK_MIN_CHAIN
+#define FL_BULK_MIN_CHAIN 1024u
+#endif
+
+// A whole-stream pass on the windows of k_lz_parse<true> / k_lz_walk<true, true> (kernels_parse.h, STREAM): a workgroup's
+// share is a group of consecutive windows of one stream (stream_plan.h builds the table).
+struct fl_swin {
+    uint32_t chunk;   // the stream (index into schunks)
+    uint32_t win0;    // the group's first window (index into chunks / the chain links)
+    uint32_t nwin;    // windows in the group
+    uint32_t wfirst;  // number of the group's first window in its stream
+    uint32_t prev;    // the group before it in the stream (index into swins), ~0u: the stream's first
+    uint32_t pad_[3];
+};
+
+#define FL_SEG_ENTRIES 512u  // next anchor <= previous + 254 literals + 258: hand-over offsets < 512
+// the stitch over groups of segments (kernels_stream.h, k_st_stitch_a / _b / _c)
+#define FL_STITCH_GROUP 64u
+struct fl_sgroup {
+    uint32_t piece;
+    uint32_t g;  // group number inside the piece
+};
+
 // huffman-only / store-only streams with sync-flush points (flate_hip_compress_flush): the block
 // table is built on the host, one entry per plan slot; ordinary batches compute the same from
 // the chunk length (block j = bytes [65535 j, ...), deflate.zig:498-511).

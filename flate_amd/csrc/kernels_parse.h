@@ -54,10 +54,7 @@ __device__ __forceinline__ uint32_t fl_lds_mskor_rtn(uint32_t* lds_word, uint32_
     return old;
 }
 
-// Levels whose chain budget reaches this value keep the match finder of kernels_lz.h (flate_hip.hip).
-#ifndef FL_BULK_MIN_CHAIN
-#define FL_BULK_MIN_CHAIN 1024u
-#endif
+// (FL_BULK_MIN_CHAIN, the chain budget from which a level keeps the match finder of kernels_lz.h: flate_layout.h)
 
 // FL_CHAIN_WAVES (8) waves per chunk.  Wave w prepares block 8 k + w (1024 positions: loads, staging, hashes) while the others
 // prepare theirs; the exchanges themselves are issued block after block -- wave 0, barrier, wave 1, barrier, ... --
@@ -435,14 +432,7 @@ __device__ __forceinline__ uint32_t pz_lds4(const uint32_t* win32, uint32_t off)
 // until a sub-pass leaves where it left before: from there on the anchors of the first launch stand (a parse from any entry
 // falls in step with the true one within a few bytes, so this is the first sub-pass of the group's first window).  A group that
 // had to be parsed to its end with a new exit sets `dirty`: the host launches the fix again (never seen).
-struct fl_swin {
-    uint32_t chunk;   // the stream (index into schunks)
-    uint32_t win0;    // the group's first window (index into chunks / the chain links)
-    uint32_t nwin;    // windows in the group
-    uint32_t wfirst;  // number of the group's first window in its stream
-    uint32_t prev;    // the group before it in the stream (index into swins), ~0u: the stream's first
-    uint32_t pad_[3];
-};
+// (fl_swin, a group's table entry: flate_layout.h; the table and the fix-launch policy: stream_plan.h)
 template <bool STREAM>
 __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const uint8_t* __restrict__ in,
                                                            const fl_chunk* __restrict__ chunks, fl_params prm,

@@ -25,8 +25,6 @@
 #pragma once
 #include "kernels_lz.h"
 
-#define FL_SEG_ENTRIES 512u  // next anchor <= previous + 254 literals + 258: hand-over offsets < 512
-
 // How many window slides the reference has done when `written` bytes of the stream have gone
 // into the window: slide j happens as soon as the window is full for the j-th time
 // (65536 + 32768 (j-1) bytes, deflate.zig:306-311).
@@ -124,12 +122,7 @@ __global__ __launch_bounds__(64) void k_st_stitch(const fl_piece* __restrict__ p
 // the pass, so it is done in three short steps over groups of FL_STITCH_GROUP segments: every
 // group composes its segments' exit maps for all 512 possible entries (k_st_stitch_a), one thread
 // per piece walks the groups (k_st_stitch_b), one thread per group walks its segments from the
-// group's now known entry (k_st_stitch_c).
-#define FL_STITCH_GROUP 64u
-struct fl_sgroup {
-    uint32_t piece;
-    uint32_t g;  // group number inside the piece
-};
+// group's now known entry (k_st_stitch_c).  (FL_STITCH_GROUP, fl_sgroup: flate_layout.h; the group tables: stream_plan.h)
 // one step of the walk: anchor `a` (stream position) enters segment s of the piece
 __device__ __forceinline__ uint32_t fl_stitch_step(const fl_piece& pc, const fl_seg* __restrict__ segs,
                                                    const uint16_t* __restrict__ exitmap, uint32_t s, uint32_t a) {

@@ -42,6 +42,24 @@ def test_pass_plan_under_the_sanitizers():
     assert "ok" in r.stdout
 
 
+def test_stream_plan_under_the_sanitizers():
+    """tests/host_cpp/test_stream_plan.cpp: a program of its own, built with AddressSanitizer and UBSan, that pushes random
+    and hostile whole-stream passes (zero-length streams, a stream at the length limit, thousands of tiny streams, groups of
+    one window, flush points on top of each other) through every rule of flate_amd/csrc/stream_plan.h.  It checks that the
+    groups partition every stream's windows in order, that no window looks beyond its stream, that the stitch groups cover
+    every segment once, that the regions of the wexit buffer do not overlap and that the fix loop ends; what the rules
+    decide is tests/test_stream_plan_cpu.py's business."""
+    src = os.path.join(ROOT, "tests", "host_cpp", "test_stream_plan.cpp")
+    exe = os.path.join(ROOT, "tests", "host_cpp", "test_stream_plan")
+    deps = [src] + [os.path.join(ROOT, "flate_amd", "csrc", h) for h in ("stream_plan.h", "stream_tables.h", "flate_layout.h", "flate_common.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-o", exe, src],
+                       check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ok" in r.stdout
+
+
 @pytest.mark.gpu
 def test_facade_public_interface_on_gpu():
     import torch

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Which HIP calls and kernels the compress entry points make, in order: five small calls that between them take every
-way through compress_impl, for comparing two builds of the library (a change to its host code should leave both lists
-as they are).
+way through compress_impl and seven whole-stream calls that take every way through compress_stream_pass (windows
+ungrouped, grouped with a fix launch, given up to the tiles; tiles with the direct and the grouped stitch; the windows
+of levels 8-9; a flush call at level 9), for comparing two builds of the library (a change to its host code should
+leave both lists as they are).
 
   rocprofv3 --hip-runtime-trace --kernel-trace -f csv -d DIR -- python tools/compress_calls.py run
   python tools/compress_calls.py list DIR > calls.txt        (once per build; then diff the two files)
@@ -17,7 +19,10 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["pinned in and out, three sub-batches", "pageable, just above 8 MiB", "planned device batch of two passes",
-         "flush call at level 6", "pinned, short inputs and one of 65536 bytes"]
+         "flush call at level 6", "pinned, short inputs and one of 65536 bytes",
+         "300 streams of 70000 bytes, level 6: windows, a workgroup per stream", "one 6 MiB stream, level 6, groups of 4 windows: one fix launch",
+         "3 MiB and 5 MiB of zeros round an x, groups of 4: given up to the tiles", "1 MiB on the tiles: direct stitch",
+         "9 MiB on the tiles: grouped stitch", "300 KiB, level 9, groups of 2 windows", "flush call at level 9"]
 REPEATS = 3
 
 
@@ -74,13 +79,22 @@ def run():
             assert not d_st.any().item() and d_len.all().item()
         return call, knobs, [d_in, d_out, d_len, d_st]
 
-    def flush_call():
+    def flush_call(level=6):
         text = synth.text(synth.SEED_TEXT, 4 * 65535 + 1234).tobytes()
 
         def call():
-            out, st = eng.compress_flush(text, [70000, 200000], True, 1, 6)
+            out, st = eng.compress_flush(text, [70000, 200000], True, 1, level)
             assert st == 0 and out
         return call, {}, []
+
+    def stream_call(datas, level, knobs):   # whole-stream passes: every input longer than 65535 bytes
+        def call():
+            outs, st = eng.compress_many(datas, 0, level)
+            assert not any(st) and all(outs)
+        return call, knobs, []
+
+    text = synth.text(synth.SEED_TEXT, 9 << 20).tobytes()
+    groups_of_4 = {"FLATE_HIP_STREAM_WINDOWS": "1", "FLATE_HIP_STREAM_GROUP": "4"}
 
     calls = [
         host_call([65535] * 40, True, {"FLATE_HIP_HOST_PASS_CHUNKS": "16"}),      # 16 + 16 + 8 chunks
@@ -88,6 +102,13 @@ def run():
         planned_call(),
         flush_call(),
         host_call([3000] * 20 + [65536] + [65535] * 20, True, {}),
+        stream_call([text[70000 * i: 70000 * (i + 1)] for i in range(100)] * 3, 6, {}),
+        stream_call([text[: 6 << 20]], 6, groups_of_4),
+        stream_call([bytes(3 << 20) + b"x" + bytes(5 << 20)], 6, groups_of_4),   # periodic: a window's stitch does not settle
+        stream_call([text[: 1 << 20]], 6, {"FLATE_HIP_STREAM_WINDOWS": "0"}),
+        stream_call([text], 6, {"FLATE_HIP_STREAM_WINDOWS": "0"}),                # 288 segments in one piece
+        stream_call([text[: 300 << 10]], 9, {"FLATE_HIP_STREAM_WINDOWS": "1", "FLATE_HIP_STREAM_GROUP": "2"}),
+        flush_call(9),
     ]
     for call, knobs, _keep in calls:
         os.environ.update(knobs)
@@ -132,7 +153,7 @@ def listing(d):
         launched = []
         for r in api[a:b]:
             print("  " + r["Function"])
-            launched += kern.get(int(r["Correlation_Id"]), [])
+            launched += sorted(kern.get(int(r["Correlation_Id"]), []))  # (a memset may be two fill kernels: in no fixed order)
         print("  ---- %d kernels" % len(launched))
         for s in launched:
             print("  " + s)
