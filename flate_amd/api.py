@@ -580,7 +580,30 @@ class ContainerModule:
         self.store = _Simple(container, _capi.MODE_STORE)
         self.Options, self.Level = Options, Level
 
-    def compress(self, reader, writer, options=None, engine=None, *, piece=None):
+    def compress(self, reader, writer, options=None, engine=None, *, piece=None, zdict=None):
+        """zdict=: a preset dictionary (flate and zlib only, gzip raises ValueError): the stream is what
+        zlib.decompressobj(wbits, zdict=zdict) and decompress(..., zdict=zdict) inflate (flate_hip_compress_batch_dict).
+        Its last min(len, 32768) bytes and the input may be 65535 bytes together, else ValueError."""
+        zdict = _zdict_for(self._container, zdict)  # (gzip: ValueError, before an engine is made)
+        if zdict is not None:
+            if piece is not None:
+                raise ValueError("piece= takes no zdict=")
+            options = options or Options()
+            data = _read_all(reader)
+            if min(len(zdict), 32768) + len(data) > _capi.DICT_MAX_STREAM:
+                raise ValueError("with zdict= the dictionary's last 32768 bytes and the input may be %d bytes together: "
+                                 "got %d + %d" % (_capi.DICT_MAX_STREAM, min(len(zdict), 32768), len(data)))
+            eng = engine or default_engine()
+            if options.repair_q1:  # (the flag is the handle's: set for this call only, as _Compressor does)
+                eng.set_flags(_capi.DEFLATE_REPAIR_Q1)
+            try:
+                outs, st = eng.compress_many_dict([data], [zdict], None, self._container, int(options.level))
+            finally:
+                if options.repair_q1:
+                    eng.set_flags(0)
+            _compress_status(st[0])
+            writer.write(outs[0])
+            return
         c = self.compressor(writer, options, engine, piece=piece)
         c.compress(reader)
         c.finish()

@@ -20,7 +20,9 @@
 #include "../../include/flate_hip.h"
 #include "kernels_block.h"
 #include "kernels_common.h"
+#include "dict_compress_plan.h"
 #include "kernels_deflater.h"
+#include "kernels_dict.h"
 #include "kernels_inflate.h"
 #include "kernels_inflate_par.h"
 #include "kernels_inflate_size.h"
@@ -69,6 +71,7 @@ enum KernelId {
     K_INFLATER,
     K_DEFLATER,
     K_INFLATE_DICT,
+    K_DICT_STAGE,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
@@ -77,7 +80,7 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_offsets",  "k_encode",    "k_inflate",  "k_inflate_par", "k_span_scan", "k_inflate_span",
                                            "k_inflate_size", "k_inflate_size_span",
                                            "k_member_scan", "k_member_chain", "k_member_walk", "k_member_pack", "k_member_fold",
-                                           "k_gather", "k_inflater", "k_deflater", "k_inflate_dict"};
+                                           "k_gather", "k_inflater", "k_deflater", "k_inflate_dict", "k_dict_stage"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -174,6 +177,9 @@ struct flate_hip_ctx {
     DevBuf dbg_par_handed;
     // flate_hip_decompress_batch_dict: the table of the call's dictionaries, and for host callers their bytes and dict_of
     DevBuf dc_tab, dc_bytes, dc_of;
+    // flate_hip_compress_batch_dict, per pass of staged streams: history and record of every stream side by side, the staging
+    // kernel's table, the chunk table of the records alone (the checksum's) -- dict_compress_plan.h
+    DevBuf dcc_stage, dcc_jobs, dcc_chunks;
     // flate_hip_decompressed_sizes: the span table and the span records of its long streams, and for
     // flate_hip_debug_size_paths the streams of the last call whose size came from a closed chain / from one wave
     DevBuf sz_spans, sz_recs;
@@ -1369,7 +1375,8 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->tokens, &h->ntok, &h->cflag, &h->links, &h->wchunks, &h->swins, &h->wexit, &h->shard_sz, &h->tiles, &h->segs, &h->pieces, &h->fpts, &h->zones, &h->nsorted, &h->jmp,
                       &h->exitmap, &h->entry, &h->segtok, &h->tokbase, &h->bound, &h->sgroups, &h->sgroup0, &h->gmap, &h->gentry,
                       &h->sblocks, &h->st_in, &h->st_out, &h->st_inoff, &h->st_outlen, &h->st_status,
-                      &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed, &h->dc_tab, &h->dc_bytes, &h->dc_of})
+                      &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed, &h->dc_tab, &h->dc_bytes, &h->dc_of, &h->dcc_stage,
+                      &h->dcc_jobs, &h->dcc_chunks})
         if (b->p) (void)hipFree(b->p);
     h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
@@ -1491,6 +1498,15 @@ struct Mirror {
     }
 };
 
+// The dictionaries of a flate_hip_compress_batch_dict call, as compress_impl is handed them: the offsets are on the host
+// already, the dictionaries' bytes and their table (Adler-32s filled) on the device.
+struct DictCall {
+    std::vector<uint64_t> hin, hout;
+    std::vector<fl_dictc_stream> streams;  // one per chunk
+    const uint8_t* d_dict = nullptr;
+    const fl_dict_ent* d_tab = nullptr;
+};
+
 // What the stages of one compress_impl call share.
 struct CompressCall {
     flate_hip_ctx* h = nullptr;
@@ -1502,6 +1518,7 @@ struct CompressCall {
     uint32_t n_chunks = 0;
     int container = 0, mode = 0, memkind = 0;
     const FlushSpec* fs = nullptr;
+    const DictCall* dc = nullptr;  // flate_hip_compress_batch_dict: streams with preset dictionaries (never mirrored, pinned or planned)
     // pl: the batch's layout is known (plan): no offsets are fetched; while the plan is being built
     // (!pl->ready, `planning`) the per-pass tables are made and kept and nothing is launched, afterwards
     // (`planned_run`) they are used as they are and the call only enqueues work
@@ -1540,6 +1557,9 @@ struct PassRun {
     uint32_t c0 = 0, nc = 0, nb = 0;
     size_t index = 0;
     bool stream = false;           // a whole-stream pass
+    bool staged = false;           // ... of streams with preset dictionaries: its kernels read the staging workspace
+    std::vector<fl_dictc_job> jobs;    // ... the staging kernel's table
+    std::vector<fl_chunk> rec_chunks;  // ... and the chunk table of the records alone (the checksum covers no dictionary)
     bool sliced = false;           // this pass's tables: a slice of their own, filled on the input stream
     hipEvent_t ev_in = nullptr;    // its input (and tables) are on the device
     hipStream_t stp = nullptr;     // the compute stream its kernels run on
@@ -1596,7 +1616,7 @@ struct WsShift {  // a pass's view of the two-slice workspace: every buffer from
 
 int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container,
                   int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind,
-                  const FlushSpec* fs, flate_hip_plan* pl = nullptr, Mirror* mirror = nullptr);
+                  const FlushSpec* fs, flate_hip_plan* pl = nullptr, Mirror* mirror = nullptr, const DictCall* dc = nullptr);
 
 // Pageable host buffers of some size (what every caller of the facade's compress(reader, writer) has): a
 // staged hipMemcpy each way moves about 10 GB/s and nothing overlaps.  Instead a few host threads copy the
@@ -1609,7 +1629,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
 int run_on_mirrors(CompressCall& cc, const uint64_t* in_off, const uint64_t* out_off, bool* taken) {
     flate_hip_ctx* h = cc.h;
     *taken = false;
-    if (!(cc.memkind == FLATE_HIP_MEM_HOST && !cc.fs && !cc.pl && (cc.in_hi - cc.in_lo) >= (8ull << 20) && cc.in && cc.out && !cc.mirror &&
+    if (!(cc.memkind == FLATE_HIP_MEM_HOST && !cc.fs && !cc.dc && !cc.pl && (cc.in_hi - cc.in_lo) >= (8ull << 20) && cc.in && cc.out && !cc.mirror &&
           !is_pinned_host(cc.in + cc.in_lo) && !is_pinned_host(cc.out + cc.out_lo) && !h->knobs.no_pin_mirror))
         return FLATE_HIP_OK;
     const size_t want_in = (cc.in_hi - cc.in_lo) + 16, want_out = (cc.out_hi - cc.out_lo) + 16;
@@ -1654,8 +1674,8 @@ int stage_host_buffers(CompressCall& cc) {
         if ((rc = ensure(h, h->st_status, sizeof(int32_t) * cc.n_chunks))) return rc;
         // Pinned host buffers (hipHostMalloc / hipHostRegister, torch pin_memory): the copies are real DMA
         // and run on their own streams, a sub-batch at a time (below).  Pageable: one staged copy each way.
-        cc.pin_in = !cc.fs && is_pinned_host(cc.in + cc.in_lo);
-        cc.pin_out = !cc.fs && is_pinned_host(cc.out + cc.out_lo);
+        cc.pin_in = !cc.fs && !cc.dc && is_pinned_host(cc.in + cc.in_lo);
+        cc.pin_out = !cc.fs && !cc.dc && is_pinned_host(cc.out + cc.out_lo);
         if ((cc.pin_in && !h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) ||
             (cc.pin_out && !h->s_out && create_copy_stream(&h->s_out, false) != hipSuccess))
             return FLATE_HIP_E_ALLOC;
@@ -1754,7 +1774,7 @@ int size_two_slices(flate_hip_ctx* h, const fl_params& prm, uint64_t nc, uint64_
 // Slices that cannot be had: the passes one after the other on the caller's stream (round 5's way).
 void setup_two_streams(CompressCall& cc) {
     flate_hip_ctx* h = cc.h;
-    cc.two = fl_two_eligible(cc.pcfg, cc.pinned_passes, cc.planned_run ? cc.pl->passes.size() : 0, cc.mode, cc.fs != nullptr,
+    cc.two = fl_two_eligible(cc.pcfg, cc.pinned_passes, cc.planned_run ? cc.pl->passes.size() : 0, cc.mode, cc.fs != nullptr || cc.dc != nullptr,
                              h->knobs.one_stream, cc.chunks.data());
     if (cc.two && !h->s_c2) cc.two = side_stream(h->s_c2, h->c2_ev0, h->c2_ev1);
     if (!cc.two) return;
@@ -1896,24 +1916,62 @@ int keep_pass_in_plan(CompressCall& cc, const PassRun& p) {
     return FLATE_HIP_OK;
 }
 
+// A pass of streams with preset dictionaries (dict_compress_plan.h decides, this carries out): every stream's history
+// and record side by side in the staging workspace (k_dict_stage), the pass's chunks turned into those staged streams,
+// its whole-stream tables, and the chunk table of the records alone for the checksum.  The table uploads are waited for
+// in upload_pass.
+int stage_dict_pass(CompressCall& cc, PassRun& p) {
+    flate_hip_ctx* h = cc.h;
+    int rc;
+    fl_chunk* ch = &cc.chunks[p.c0];
+    const uint32_t nc = p.nc;
+    const uint64_t stage_bytes = fl_dictc_stage(ch, &cc.dc->streams[p.c0], nc, p.jobs);
+    fl_dictc_staged_chunks(ch, p.jobs.data(), nc, cc.container);
+    p.nb = fl_dictc_pass_tables(ch, p.jobs.data(), nc, p.tabs, *p.blk_chunk);
+    p.rec_chunks.assign(ch, ch + nc);
+    for (uint32_t i = 0; i < nc; i++) {
+        p.rec_chunks[i].in_off = p.jobs[i].src;
+        p.rec_chunks[i].in_len = p.jobs[i].n;
+    }
+    if ((rc = ensure(h, h->dcc_stage, stage_bytes)) || (rc = ensure(h, h->dcc_jobs, sizeof(fl_dictc_job) * nc)) ||
+        (rc = ensure(h, h->dcc_chunks, sizeof(fl_chunk) * nc)))
+        return rc;
+    HIP_OK(h, hipMemcpyAsync(h->dcc_jobs.p, p.jobs.data(), sizeof(fl_dictc_job) * nc, hipMemcpyHostToDevice, cc.st));
+    HIP_OK(h, hipMemcpyAsync(h->dcc_chunks.p, p.rec_chunks.data(), sizeof(fl_chunk) * nc, hipMemcpyHostToDevice, cc.st));
+    {
+        ProfScope ps(h, K_DICT_STAGE);
+        hipLaunchKernelGGL(k_dict_stage, dim3(nc), dim3(FL_DSTG_THREADS), 0, cc.st, cc.d_in, cc.dc->d_dict,
+                           (const fl_dictc_job*)h->dcc_jobs.p, (uint8_t*)h->dcc_stage.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    return FLATE_HIP_OK;
+}
+
 // a whole-stream pass: its checksum, its tokenizer (compress_stream_pass), the shared back end
 int enqueue_stream_pass(CompressCall& cc, const PassRun& p) {
     flate_hip_ctx* h = cc.h;
     int rc;
     hipStream_t st = cc.st;
     const uint32_t c0 = p.c0, nc = p.nc, nb = p.nb;
+    // (staged streams: the tokenizer and the back end read the staging workspace, the checksum the records where they lie)
+    const uint8_t* d_in = p.staged ? (const uint8_t*)h->dcc_stage.p : cc.d_in;
     if (cc.container != 0) {
         ProfScope ps(h, K_CHECKSUM);
-        hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(64), 0, st, cc.d_in, p.dch, p.dbc, p.dsb, cc.prm, h->crc,
-                           (uint32_t*)h->cks.p);
+        hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(64), 0, st, cc.d_in, p.staged ? (const fl_chunk*)h->dcc_chunks.p : p.dch, p.dbc,
+                           p.dsb, cc.prm, h->crc, (uint32_t*)h->cks.p);
     }
-    if ((rc = compress_stream_pass(h, cc.d_in, cc.prm, nc, nb, p.tabs, &cc.chunks[c0]))) return rc;
+    if ((rc = compress_stream_pass(h, d_in, cc.prm, nc, nb, p.tabs, &cc.chunks[c0]))) return rc;
     h->dbg_pass_chunks = nc;
     h->dbg_first_chunk = c0;
     h->dbg_pos_off.clear();
     h->dbg_chunks.assign(cc.chunks.begin() + c0, cc.chunks.begin() + c0 + nc);
     h->dbg_pieces = p.tabs.pieces;
-    if ((rc = enqueue_back_end(h, cc.prm, nc, nb, c0, p.dch, p.dbc, p.dsb, cc.d_in, cc.d_out, cc.d_outlen, cc.d_status))) return rc;
+    if ((rc = enqueue_back_end(h, cc.prm, nc, nb, c0, p.dch, p.dbc, p.dsb, d_in, cc.d_out, cc.d_outlen, cc.d_status))) return rc;
+    if (p.staged && cc.container == FLATE_HIP_ZLIB) {  // 78 bb and the DICTID in front of what the back end wrote
+        hipLaunchKernelGGL(k_dict_header, dim3((nc + 63) / 64), dim3(64), 0, st, p.dch, (const fl_dictc_job*)h->dcc_jobs.p, nc, cc.dc->d_tab,
+                           cc.d_out, cc.d_outlen + c0, cc.d_status + c0);
+        HIP_OK(h, hipGetLastError());
+    }
     if (cc.pinned_passes) {
         // A whole-stream pass keeps its tables at the START of the table buffers (its block count is not known when
         // the slices are laid out), where the slices of the chunk passes lie: its kernels are only enqueued here, so
@@ -2015,9 +2073,9 @@ int finish_call(CompressCall& cc, PassGuard& pass_guard) {
 
 int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container,
                   int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind,
-                  const FlushSpec* fs, flate_hip_plan* pl, Mirror* mirror) {
+                  const FlushSpec* fs, flate_hip_plan* pl, Mirror* mirror, const DictCall* dc) {
     const bool planning = pl && !pl->ready;
-    if (!h || (!pl && (!in_off || !out_off)) || (!planning && (!out_len || !status))) return FLATE_HIP_E_INVALID_ARG;
+    if (!h || (!pl && !dc && (!in_off || !out_off)) || (!planning && (!out_len || !status))) return FLATE_HIP_E_INVALID_ARG;
     if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
     // The record is declared before the guards, so whatever way the call ends the guards' destructors run first, in this
     // order, and the record's vectors -- which copies on the input stream may still read -- are freed after them:
@@ -2041,6 +2099,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     cc.mode = mode;
     cc.memkind = memkind;
     cc.fs = fs;
+    cc.dc = dc;
     cc.pl = pl;
     cc.planning = planning;
     cc.planned_run = pl && pl->ready;
@@ -2048,14 +2107,14 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     cc.st = h->stream;
 
     int rc = 0;
-    if (!pl) {
+    if (!pl && !dc) {
         rc = fetch_offsets(h, in_off, n_chunks, memkind, cc.hin_);
         if (rc) return rc;
         rc = fetch_offsets(h, out_off, n_chunks, memkind, cc.hout_);
         if (rc) return rc;
     }
-    cc.hin = pl ? &pl->hin : &cc.hin_;
-    cc.hout = pl ? &pl->hout : &cc.hout_;
+    cc.hin = pl ? &pl->hin : dc ? &dc->hin : &cc.hin_;
+    cc.hout = pl ? &pl->hout : dc ? &dc->hout : &cc.hout_;
     cc.in_lo = (*cc.hin)[0], cc.in_hi = (*cc.hin)[n_chunks];
     cc.out_lo = (*cc.hout)[0], cc.out_hi = (*cc.hout)[n_chunks];
 
@@ -2097,7 +2156,17 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
 
     size_t pass_count = 0;
     for (uint32_t c0 = 0, nc = 0; c0 < n_chunks; c0 += nc) {
-        const fl_pass_pick pk = fl_pass_next(cc.pcfg, cc.chunks.data(), c0, pass_count, mode, fs != nullptr, h->knobs.stream_pass_bytes);
+        fl_pass_pick pk;
+        bool staged = false;
+        if (dc) {  // (dict_compress_plan.h: the streams with a dictionary in passes of their own)
+            const fl_dictc_pick dpk = fl_dictc_pass_next(cc.pcfg, cc.chunks.data(), dc->streams.data(), c0, pass_count, mode,
+                                                         h->knobs.stream_pass_bytes, FL_DICTC_PASS_STREAMS);
+            pk.nc = dpk.nc;
+            pk.stream = dpk.kind != FL_DICTC_CHUNK;
+            staged = dpk.kind == FL_DICTC_STAGED;
+        } else {
+            pk = fl_pass_next(cc.pcfg, cc.chunks.data(), c0, pass_count, mode, fs != nullptr, h->knobs.stream_pass_bytes);
+        }
         nc = pk.nc;
         if (pl && pk.stream) return FLATE_HIP_E_UNSUPPORTED;  // (whole-stream passes build more tables per call)
         PassRun p;
@@ -2105,6 +2174,7 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
         p.nc = nc;
         p.index = pass_count++;
         p.stream = pk.stream;
+        p.staged = staged;
         p.sliced = cc.pinned_passes && !pk.stream;
         if (mirror) mirror->copy_in(c0, nc);
         cc.pass_c0.push_back(c0);
@@ -2118,7 +2188,11 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
         cc.keep_sb.emplace_back();
         p.blk_chunk = &cc.keep_blk.back();
         p.sblocks = &cc.keep_sb.back();
-        p.nb = fl_pass_tables(&cc.chunks[c0], nc, p.stream, mode, fs, p.tabs, *p.blk_chunk, *p.sblocks);
+        if (p.staged) {
+            if ((rc = stage_dict_pass(cc, p))) return rc;
+        } else {
+            p.nb = fl_pass_tables(&cc.chunks[c0], nc, p.stream, mode, fs, p.tabs, *p.blk_chunk, *p.sblocks);
+        }
         if ((rc = upload_pass(cc, p))) return rc;
         if (planning) {
             if ((rc = keep_pass_in_plan(cc, p))) return rc;
@@ -2163,6 +2237,68 @@ int flate_hip_compress_flush(flate_hip_handle h, const uint8_t* in, uint64_t n, 
     const uint64_t in_off[2] = {0, n}, out_off[2] = {0, out_cap};
     const FlushSpec fs{flush_pos, n_flush, finish != 0};
     return compress_impl(h, in, in_off, 1, container, mode, out, out_off, out_len, status, memkind, &fs);
+}
+
+// Records against preset dictionaries (include/flate_hip.h: what the bytes are; dict_compress_plan.h: every decision).
+// Here: the offsets and dict_of on the host, the dictionaries and their table on the device, their Adler-32s; the rest is
+// compress_impl with the streams' dictionaries beside it.
+int flate_hip_compress_batch_dict(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
+                                  int container, int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                                  int32_t* status, int memkind, const uint8_t* dict, const uint64_t* dict_off,
+                                  uint32_t n_dicts, const uint32_t* dict_of) {
+    if (!h || !in_off || !out_off || !out_len || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    // (what can be said without reading anything back: a wrong container or mode is an error of an empty batch too)
+    if (!fl_dictc_args_ok(container, mode, nullptr, 0, nullptr, true, 0) || (n_dicts && !dict_off) || (!dict_of && n_dicts != 1))
+        return FLATE_HIP_E_INVALID_ARG;
+    if (n_chunks == 0) return FLATE_HIP_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    DictCall dc;
+    std::vector<uint64_t> hdoff(1, 0);
+    std::vector<uint32_t> hof;
+    int rc;
+    if ((rc = fetch_offsets(h, in_off, n_chunks, memkind, dc.hin))) return rc;
+    if ((rc = fetch_offsets(h, out_off, n_chunks, memkind, dc.hout))) return rc;
+    if (n_dicts && (rc = fetch_offsets(h, dict_off, n_dicts, memkind, hdoff))) return rc;
+    if (dict_of) {
+        hof.resize(n_chunks);
+        if (memkind == FLATE_HIP_MEM_HOST) {
+            memcpy(hof.data(), dict_of, sizeof(uint32_t) * n_chunks);
+        } else {
+            HIP_OK(h, hipMemcpyAsync(hof.data(), dict_of, sizeof(uint32_t) * n_chunks, hipMemcpyDeviceToHost, st));
+            HIP_OK(h, hipStreamSynchronize(st));
+        }
+    }
+    if (!fl_dictc_args_ok(container, mode, hdoff.data(), n_dicts, dict_of ? hof.data() : nullptr, dict_of != nullptr, n_chunks))
+        return FLATE_HIP_E_INVALID_ARG;
+    const uint64_t d_lo = hdoff[0], d_hi = hdoff[n_dicts];
+    if (d_hi > d_lo && !dict) return FLATE_HIP_E_INVALID_ARG;
+    std::vector<fl_dict_ent> tab;
+    fl_dict_table(hdoff.data(), n_dicts, tab);
+    if (memkind == FLATE_HIP_MEM_HOST)  // (the dictionaries are staged from their first byte on)
+        for (fl_dict_ent& e : tab) {
+            e.start -= d_lo;
+            e.end -= d_lo;
+        }
+    if ((rc = fl_dictc_streams(dc.hin.data(), n_chunks, tab, dict_of ? hof.data() : nullptr, dc.streams))) return rc;
+    dc.d_dict = dict;
+    if ((rc = ensure(h, h->dc_tab, sizeof(fl_dict_ent) * ((size_t)n_dicts + 1)))) return rc;
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        if ((rc = ensure(h, h->dc_bytes, (d_hi - d_lo) + 16))) return rc;
+        if (d_hi > d_lo) HIP_OK(h, hipMemcpyAsync(h->dc_bytes.p, dict + d_lo, d_hi - d_lo, hipMemcpyHostToDevice, st));
+        dc.d_dict = (const uint8_t*)h->dc_bytes.p;
+    }
+    fl_dict_ent* d_tab = (fl_dict_ent*)h->dc_tab.p;
+    dc.d_tab = d_tab;
+    if (n_dicts) {
+        HIP_OK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(fl_dict_ent) * n_dicts, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipStreamSynchronize(st));  // (the table is on the host's stack)
+        // (the DICTIDs of zlib streams: once per call and dictionary)
+        if (container == FLATE_HIP_ZLIB) hipLaunchKernelGGL(k_dict_adler, dim3(n_dicts), dim3(64), 0, st, dc.d_dict, d_tab, n_dicts);
+        HIP_OK(h, hipGetLastError());
+    }
+    return compress_impl(h, in, in_off, n_chunks, container, mode, out, out_off, out_len, status, memkind, nullptr, nullptr, nullptr, &dc);
 }
 
 int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,

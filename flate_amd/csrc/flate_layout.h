@@ -26,7 +26,11 @@ struct fl_chunk {
     uint32_t zone_off;     // whole-stream passes: the chunk's entries in the slide table ...
     uint32_t n_slides;     // ... = how often the reference slides its window over this stream
     uint32_t unfinished;   // the stream ends with a sync-flush marker: no final block, no container footer
-    uint32_t pad_;
+    union {
+        uint32_t pad_;  // a window of a stream (stream_plan.h, fl_stream_windows): bit 0 set, bits 8.. the bytes behind it
+        uint32_t hist;  // a stream of a whole-stream pass: its first `hist` bytes are history only -- a preset dictionary
+                        // (dict_compress_plan.h): never parsed, in no piece; the stream has a flush point there
+    };
 };
 
 // Whole-stream passes (levels 4..9; inputs longer than 65535 bytes, or any input with sync-flush
@@ -36,7 +40,7 @@ struct fl_chunk {
 struct fl_tile {
     uint32_t chunk;  // index into the pass's chunk table
     uint32_t w0;     // stream-relative position of the window start (multiple of 32768)
-    uint32_t tgt0;   // window-relative position of the first target (0 or 32768)
+    uint32_t tgt0;   // window-relative position of the first target (0 or 32768; a stream's first tile: its fl_chunk::hist)
     uint32_t zone;   // window-relative: targets at or beyond it are visited after the next slide (65536 = none)
 };
 // A piece = the stream positions between two sync-flush points (the whole stream when there are

@@ -540,6 +540,9 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
     if (STREAM) {
         const uint32_t* zone = zones + sck.zone_off;
         if (ws) t_first = zone[ws - 1] - FL_MAX_DIST * ws;
+        // (a stream whose first bytes are history only -- a preset dictionary, fl_chunk::hist: its first window's targets and the
+        // path begin behind them; no lane walks a position of the history)
+        else carry = t_first = sck.hist;
         if (ws < sck.n_slides) t_last = zone[ws] - FL_MAX_DIST * ws;
         if (wi) __syncthreads();  // the window before is done with the LDS tables
         if (guessed && wi == 0) {

@@ -27,8 +27,14 @@ struct StreamTables {
 };
 
 // Adds chunk `i` (pass-local index) to the tables; fills the chunk's stream fields and n_blocks.
-inline void add_stream_chunk(StreamTables& t, fl_chunk& c, uint32_t i, uint32_t first_block, const FlushSpec* fs) {
+// hist: the stream's first `hist` bytes are history only (a preset dictionary, dict_compress_plan.h; fs has a flush point
+// at `hist`, in_len <= 65535): the flush point stays in the table -- the three positions before it never enter the hash
+// table --, but the run [0, hist) is no piece (no segments, no blocks, no marker, no output) and its positions are no
+// targets of the stream's tile.
+inline void add_stream_chunk(StreamTables& t, fl_chunk& c, uint32_t i, uint32_t first_block, const FlushSpec* fs,
+                             uint32_t hist = 0) {
     const uint32_t N = c.in_len;
+    c.hist = hist;
     c.pos_off = t.npos;
     t.npos += ((uint64_t)N + FL_SEG - 1) / FL_SEG * FL_SEG + FL_SEG;
     // flush points
@@ -54,7 +60,7 @@ inline void add_stream_chunk(StreamTables& t, fl_chunk& c, uint32_t i, uint32_t 
         if (j > c.n_slides) return 65536u;
         return t.zones[c.zone_off + j - 1] - w0;
     };
-    t.tiles.push_back(fl_tile{i, 0u, 0u, zone_of(1, 0)});
+    t.tiles.push_back(fl_tile{i, 0u, hist, zone_of(1, 0)});
     for (uint32_t w0 = FL_SEG; w0 + FL_SEG < N; w0 += FL_SEG)
         t.tiles.push_back(fl_tile{i, w0, FL_SEG, zone_of(w0 / FL_SEG + 1, w0)});
     // pieces, their blocks and segments
@@ -76,9 +82,10 @@ inline void add_stream_chunk(StreamTables& t, fl_chunk& c, uint32_t i, uint32_t 
         nb += pc.n_blocks;
         t.pieces.push_back(pc);
     };
-    uint32_t prev = 0;
+    uint32_t prev = hist;
     for (uint32_t k = 0; k < c.n_flush; k++) {
         const uint32_t f = t.fpts[c.flush_off + k];
+        if (hist && f <= hist) continue;  // (the flush that ends the history: nothing goes out for it)
         add_piece(prev, f, 2u);
         prev = f;
     }

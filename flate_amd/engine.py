@@ -293,6 +293,44 @@ class Engine:
         res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
         return res, [int(s) for s in status], [int(c) for c in consumed]
 
+    def compress_many_dict(self, chunks, dicts, dict_of=None, container=0, mode=6, caps=None):
+        """Records compressed against preset dictionaries (flate_hip_compress_batch_dict; raw or zlib, levels 4..9): the
+        streams decompress_many_dict and zlib.decompressobj(wbits, zdict=...) inflate.  dicts: sequence of bytes-like.
+        dict_of: per record the index of its dictionary or None (it has none); default None: there is exactly one
+        dictionary and every record uses it.  The last min(len, 32768) bytes of a dictionary and the record may be 65535
+        bytes together; a longer one raises FlateHipError (FLATE_HIP_E_UNSUPPORTED).  caps: slot size per record
+        (default: compress_bound + 4).  Returns (list of bytes, list of status codes)."""
+        self._sync_env()
+        if container == _capi.GZIP:
+            raise ValueError("gzip has no preset dictionaries")
+        n = len(chunks)
+        if dict_of is None and len(dicts) != 1:
+            raise ValueError("dict_of may be left out only with exactly one dictionary")
+        if n == 0:
+            return [], []
+        blob, in_off = self._host_input(chunks)
+        dblob, d_off = self._host_input(dicts)
+        of = None
+        if dict_of is not None:
+            if len(dict_of) != n:
+                raise ValueError("dict_of wants one entry per record")
+            of = np.array([_capi.DICT_NONE if d is None else int(d) for d in dict_of], dtype=np.uint32)
+        if caps is None:
+            caps = [(self.compress_bound(len(c), container, mode) + 4 + 7) & ~7 for c in chunks]
+        caps = np.array([int(c) for c in caps], dtype=np.uint64)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(caps, out=out_off[1:])
+        out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int32)
+        rc = self._L.flate_hip_compress_batch_dict(self._h, blob.ctypes.data, in_off.ctypes.data, n, container, mode,
+                                                   out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                                   status.ctypes.data, MEM_HOST, dblob.ctypes.data, d_off.ctypes.data,
+                                                   len(dicts), None if of is None else of.ctypes.data)
+        self._check(rc, "flate_hip_compress_batch_dict")
+        res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
+        return res, [int(s) for s in status]
+
     # ---- device buffers (raw pointers; everything already in HBM) ----
     def compress_device(self, in_ptr, in_off_ptr, n_chunks, container, mode, out_ptr, out_off_ptr, out_len_ptr,
                         status_ptr):
@@ -337,6 +375,20 @@ class Engine:
                                                      out_off_ptr, out_len_ptr, status_ptr, consumed_ptr, MEM_DEVICE,
                                                      dict_ptr, dict_off_ptr, n_dicts, dict_of_ptr)
         self._check(rc, "flate_hip_decompress_batch_dict")
+
+    def compress_dict_device(self, in_ptr, in_off_ptr, n_chunks, container, mode, out_ptr, out_off_ptr, out_len_ptr,
+                             status_ptr, dict_ptr, dict_off_ptr, n_dicts, dict_of_ptr=None):
+        """flate_hip_compress_batch_dict on device memory (n_dicts + 1 dictionary offsets; dict_of: n_chunks uint32 or
+        None with one dictionary).  Returns the call's return code where it is FLATE_HIP_E_INVALID_ARG or
+        FLATE_HIP_E_UNSUPPORTED -- the call has done nothing then --, raises on every other failure."""
+        self._sync_env()
+        rc = self._L.flate_hip_compress_batch_dict(self._h, in_ptr, in_off_ptr, n_chunks, container, mode, out_ptr,
+                                                   out_off_ptr, out_len_ptr, status_ptr, MEM_DEVICE, dict_ptr,
+                                                   dict_off_ptr, n_dicts, dict_of_ptr)
+        if rc in (_capi.E_INVALID_ARG, _capi.E_UNSUPPORTED):
+            return rc
+        self._check(rc, "flate_hip_compress_batch_dict")
+        return 0
 
     def decompressed_sizes_device(self, in_ptr, in_off_ptr, n_chunks, container, flags, sizes_ptr, status_ptr,
                                   consumed_ptr=None):

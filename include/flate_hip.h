@@ -224,13 +224,53 @@ int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint
  * Every stream of such a call is decoded by the wave-per-stream kernel: there are no spans and no workgroup-per-stream
  * kernel here, so a LONG stream with a dictionary runs at the speed of one wave.  The shape this call is made for is a
  * large batch of short records that share a few dictionaries.  The Adler-32 of every dictionary is computed once per call.
- * Not covered: compressing with a dictionary, the size probe, flate_hip_decompress_members, the sharded entry points.
+ * Not covered: the size probe, flate_hip_decompress_members, the sharded entry points.  (Compressing with a dictionary:
+ * flate_hip_compress_batch_dict, below.)
  * flate_hip_decompress_batch itself is unchanged: it knows nothing of FDICT.
  */
 int flate_hip_decompress_batch_dict(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
                                     int container, int flags, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
                                     int32_t* status, uint64_t* consumed, int memkind, const uint8_t* dict,
                                     const uint64_t* dict_off, uint32_t n_dicts, const uint32_t* dict_of);
+
+/*
+ * Compress n_chunks independent records against preset dictionaries, levels 4..9: the streams that
+ * flate_hip_decompress_batch_dict (and zlib.decompressobj(wbits, zdict=...)) inflate.  The first eleven arguments are
+ * those of flate_hip_compress_batch, the four dictionary arguments exactly those of flate_hip_decompress_batch_dict (any
+ * dictionary length, 0 included; dict_of[i] == 0xffffffff: no dictionary; dict_of == NULL only with n_dicts == 1; all
+ * arrays live where memkind says; dict_off and dict_of are read back once, as the other offsets are).
+ *
+ * What "compressed against a dictionary" means.  The reference has no dictionaries, but its Compressor keeps the LZ77
+ * history across a sync flush and a flush ends on a byte boundary.  With T the last min(length, 32768) bytes of the
+ * dictionary and R the record: a raw-container reference compressor does  write(T); flush();  -- L bytes so far, ending
+ * in 00 00 ff ff --  write(R); finish();  and the stream of R is its output FROM BYTE L ON.
+ *   raw (container 0)    that stream.
+ *   zlib (container 2)   78 bb (the reference's 78 9c with FDICT set and FCHECK made good), DICTID = the Adler-32 of
+ *                        the WHOLE dictionary, big endian, that stream, the big-endian Adler-32 of R alone.
+ *   gzip                 has no dictionaries: FLATE_HIP_E_INVALID_ARG.  So are modes 0 and 1.
+ * A stream without a dictionary: bytes and status exactly those of flate_hip_compress_batch (zlib: 78 9c, no DICTID).
+ * A stream with a dictionary, an empty one included (zlib: FDICT set, DICTID 00 00 00 01): status 0, or 100 when the slot is
+ * too small; 102 and FLATE_HIP_DEFLATE_REPAIR_Q1 as in flate_hip_compress_batch (a record needs more than 32768
+ * tokens for that: next to no history).  flate_hip_compress_bound(n, container, mode) + 4 bytes are always enough.
+ * One difference from zlib's deflateSetDictionary: the tokenizer ran dry at the flush, so the last three positions of the
+ * dictionary never enter the hash table (zlib inserts them when the record's first bytes arrive).  A match can begin at
+ * any other position of T and run on into the record; none begins at its last three.  The streams are valid either way.
+ * Limit: min(dictionary length, 32768) + record length <= 65535 for every stream with a dictionary -- the reference's
+ * window never slides on such a stream --, else the whole call returns FLATE_HIP_E_UNSUPPORTED and writes nothing.
+ * n_chunks == 0: FLATE_HIP_OK.
+ * The dictionary costs a record a copy, not a parse: history and record are written side by side into a workspace of the
+ * handle (bounded per pass: at most 2048 such streams at a time, however many the call has), the tokenizer's targets
+ * begin behind the history, and nothing is emitted for it.  The Adler-32 of every dictionary is computed once per call.
+ * Waits: the call reads its offset arrays and dict_of back first, and the host waits for the stream several times per
+ * pass (the tables of a whole-stream pass, the tokenizer's verdict).  It cannot be captured in a graph, as is true of
+ * any whole-stream pass.
+ * Not covered: records beyond the limit, the resumable deflater, flate_hip_compress_flush with a dictionary, planned and
+ * sharded calls, sharing one dictionary's hash chains between records (every stream builds the chains of its own copy).
+ */
+int flate_hip_compress_batch_dict(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
+                                  int container, int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                                  int32_t* status, int memkind, const uint8_t* dict, const uint64_t* dict_off,
+                                  uint32_t n_dicts, const uint32_t* dict_of);
 
 /*
  * Size probe: how many bytes each of n_chunks independent streams inflates to, without inflating it.  The arguments have
