@@ -24,6 +24,7 @@ ST_WRONG_DICT = 107            # ... its DICTID is not the Adler-32 of the dicti
 INFLATER_NEED_DICT = 2         # inflater create flag: report ST_NEED_DICT instead of ignoring FDICT
 DICT_NONE = 0xFFFFFFFF         # dict_of entry: this stream has no dictionary
 DICT_MAX_STREAM = 65535        # compress with a dictionary: its last min(len, 32768) bytes + the record, at most
+JOIN_MAX_PIECE = 65535         # joined compress: the largest piece (flate_hip_compress_joined)
 E_INVALID_ARG, E_UNSUPPORTED = -2, -5  # return codes of a call that has done nothing
 FEED_MORE, FEED_FLUSH, FEED_FINISH = 0, 1, 2  # deflater feed ops
 
@@ -46,6 +47,7 @@ SYMBOLS = [
     "flate_hip_decompress_members", "flate_hip_debug_member_paths",
     "flate_hip_decompress_batch_dict", "flate_hip_inflater_set_dictionary",
     "flate_hip_compress_batch_dict",
+    "flate_hip_joined_bound", "flate_hip_compress_joined",
 ]
 
 
@@ -178,6 +180,10 @@ def lib():
     L.flate_hip_compress_batch_dict.argtypes = [vp, vp, u64p, C.c_uint32, C.c_int, C.c_int, vp, u64p, u64p, i32p, C.c_int,
                                                 vp, u64p, C.c_uint32, vp]
     L.flate_hip_compress_batch_dict.restype = C.c_int
+    L.flate_hip_joined_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_int]
+    L.flate_hip_joined_bound.restype = C.c_size_t
+    L.flate_hip_compress_joined.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, u64p, u64p, i32p, C.c_int]
+    L.flate_hip_compress_joined.restype = C.c_int
     L.flate_hip_inflater_set_dictionary.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_int, vp]
     L.flate_hip_inflater_set_dictionary.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]

@@ -556,7 +556,9 @@ class _Simple:
     def __init__(self, container, mode):
         self._container, self._mode = container, mode
 
-    def compress(self, reader, writer, engine=None, *, piece=None):
+    def compress(self, reader, writer, engine=None, *, piece=None, joined=None):
+        if joined is not None and joined is not False:
+            raise ValueError("joined= is for levels 4..9: the huffman and store namespaces have no joined streams")
         c = self.compressor(writer, engine, piece=piece)
         c.compress(reader)
         c.finish()
@@ -580,11 +582,32 @@ class ContainerModule:
         self.store = _Simple(container, _capi.MODE_STORE)
         self.Options, self.Level = Options, Level
 
-    def compress(self, reader, writer, options=None, engine=None, *, piece=None, zdict=None):
+    def compress(self, reader, writer, options=None, engine=None, *, piece=None, zdict=None, joined=None):
         """zdict=: a preset dictionary (flate and zlib only, gzip raises ValueError): the stream is what
         zlib.decompressobj(wbits, zdict=zdict) and decompress(..., zdict=zdict) inflate (flate_hip_compress_batch_dict).
-        Its last min(len, 32768) bytes and the input may be 65535 bytes together, else ValueError."""
+        Its last min(len, 32768) bytes and the input may be 65535 bytes together, else ValueError.
+        joined=True, or a piece size of 1..65535: ONE stream of independent pieces (65535 bytes for True) at the rate of
+        the chunk path, whatever the input's length (flate_hip_compress_joined); exclusive with piece= and zdict=."""
         zdict = _zdict_for(self._container, zdict)  # (gzip: ValueError, before an engine is made)
+        if joined is not None and joined is not False:
+            if piece is not None or zdict is not None:
+                raise ValueError("joined= takes neither piece= nor zdict=")
+            size = _capi.JOIN_MAX_PIECE if joined is True else int(joined)
+            if not 1 <= size <= _capi.JOIN_MAX_PIECE:
+                raise ValueError("joined= is True or a piece size of 1..%d" % _capi.JOIN_MAX_PIECE)
+            options = options or Options()
+            data = _read_all(reader)
+            eng = engine or default_engine()
+            if options.repair_q1:  # (the flag is the handle's: set for this call only, as _Compressor does)
+                eng.set_flags(_capi.DEFLATE_REPAIR_Q1)
+            try:
+                outs, st = eng.compress_joined([data], self._container, int(options.level), piece=size)
+            finally:
+                if options.repair_q1:
+                    eng.set_flags(0)
+            _compress_status(st[0])
+            writer.write(outs[0])
+            return
         if zdict is not None:
             if piece is not None:
                 raise ValueError("piece= takes no zdict=")

@@ -21,11 +21,13 @@
 #include "kernels_block.h"
 #include "kernels_common.h"
 #include "dict_compress_plan.h"
+#include "join_plan.h"
 #include "kernels_deflater.h"
 #include "kernels_dict.h"
 #include "kernels_inflate.h"
 #include "kernels_inflate_par.h"
 #include "kernels_inflate_size.h"
+#include "kernels_join.h"
 #include "kernels_lz.h"
 #include "kernels_members.h"
 #include "kernels_parse.h"
@@ -72,6 +74,9 @@ enum KernelId {
     K_DEFLATER,
     K_INFLATE_DICT,
     K_DICT_STAGE,
+    K_JOIN_OPEN,
+    K_JOIN_SCAN,
+    K_JOIN_PACK,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
@@ -80,7 +85,8 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_offsets",  "k_encode",    "k_inflate",  "k_inflate_par", "k_span_scan", "k_inflate_span",
                                            "k_inflate_size", "k_inflate_size_span",
                                            "k_member_scan", "k_member_chain", "k_member_walk", "k_member_pack", "k_member_fold",
-                                           "k_gather", "k_inflater", "k_deflater", "k_inflate_dict", "k_dict_stage"};
+                                           "k_gather", "k_inflater", "k_deflater", "k_inflate_dict", "k_dict_stage",
+                                           "k_join_open", "k_join_scan", "k_join_pack"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -89,6 +95,16 @@ struct DevBuf {
 struct PinBuf {  // pinned host memory the handle keeps (pin_grow)
     void* p = nullptr;
     size_t cap = 0;
+};
+
+// The pieces of a flate_hip_compress_joined call, as compress_impl is handed them: a batch of raw chunks whose offsets are
+// on the host already (input offsets of the pieces, their scratch slots), and what k_join_open needs behind every pass.
+struct JoinCall {
+    std::vector<uint64_t> hin, hout;
+    int container = 0;  // of the joined streams (the pieces are raw)
+    const uint32_t* d_piece_stream = nullptr;
+    const fl_join_stream* d_streams = nullptr;
+    uint32_t* d_piece_cks = nullptr;
 };
 
 }  // namespace
@@ -180,6 +196,11 @@ struct flate_hip_ctx {
     // flate_hip_compress_batch_dict, per pass of staged streams: history and record of every stream side by side, the staging
     // kernel's table, the chunk table of the records alone (the checksum's) -- dict_compress_plan.h
     DevBuf dcc_stage, dcc_jobs, dcc_chunks;
+    // flate_hip_compress_joined: the pieces' scratch slots, the streams' table, and per piece its stream, its slot, its
+    // length, status and checksum part, its place in its stream's slot; per stream the checksum -- join_plan.h.
+    // `join`: such a call is running and its pieces are in compress_impl (enqueue_pass appends k_join_open to every pass)
+    DevBuf jn_scratch, jn_streams, jn_pstream, jn_slot, jn_len, jn_status, jn_cks, jn_dst, jn_scks;
+    const JoinCall* join = nullptr;
     // flate_hip_decompressed_sizes: the span table and the span records of its long streams, and for
     // flate_hip_debug_size_paths the streams of the last call whose size came from a closed chain / from one wave
     DevBuf sz_spans, sz_recs;
@@ -902,13 +923,33 @@ int enqueue_back_end(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32
     return FLATE_HIP_OK;
 }
 
+// flate_hip_compress_joined: behind the back end of a pass of pieces, on the pass's stream and over the pass's slice of the
+// workspace -- the plans still hold the pass's blocks.  The pass took the joined container's checksum, a unit per piece, where
+// every pass takes its checksum (enqueue_pass); the pieces are raw streams, so k_offsets left it alone: k_join_open moves it out.
+int enqueue_join_open(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t nb, uint32_t c0, const fl_chunk* dch,
+                      uint8_t* d_out, uint64_t* d_outlen, int32_t* d_status) {
+    const JoinCall& jc = *h->join;
+    hipStream_t st = h->stream;
+    {
+        ProfScope ps(h, K_JOIN_OPEN);
+        hipLaunchKernelGGL(k_join_open, dim3((nc + 255) / 256), dim3(256), 0, st, dch, (const fl_block_plan*)h->plans.p, nc, c0,
+                           jc.d_piece_stream, jc.d_streams, d_out, d_outlen, d_status,
+                           jc.container != 0 ? (const uint32_t*)h->cks.p : (const uint32_t*)nullptr, jc.d_piece_cks);
+    }
+    HIP_OK(h, hipGetLastError());
+    return FLATE_HIP_OK;
+}
+
 // one pass of the chunk path (levels 4..9, inputs <= 65535 bytes) or of a simple mode: checksums,
 // tokenizer / histograms, back end.  Only enqueues.
 int enqueue_pass(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t nb, uint32_t c0, const fl_chunk* dch,
                  const uint32_t* dbc, const fl_sblock* dsb, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_outlen,
                  int32_t* d_status) {
     hipStream_t st = h->stream;
-    const int mode = prm.mode, container = prm.container;
+    // (the pieces of a joined call are raw chunks, and the pass takes the checksum of the container they are joined in: ckp)
+    const int mode = prm.mode, container = h->join ? h->join->container : prm.container;
+    fl_params ckp = prm;
+    ckp.container = container;
     int rc;
     fl_block_plan* dpl = (fl_block_plan*)h->plans.p;
     uint32_t* dhist = (uint32_t*)h->hist.p;
@@ -918,10 +959,10 @@ int enqueue_pass(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t n
     // wait for the same memory system (config #3: 9.95 -> 11.9 ms): there it runs first, on the compute stream.
     if (container != 0 && ((mode >= 4 && prm.chain >= FL_BULK_MIN_CHAIN) || (mode < 4 && h->knobs.simple_ck_inline))) {
         ProfScope ps(h, K_CHECKSUM);
-        hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(64), 0, st, d_in, dch, dbc, dsb, prm, h->crc, (uint32_t*)h->cks.p);
+        hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(64), 0, st, d_in, dch, dbc, dsb, ckp, h->crc, (uint32_t*)h->cks.p);
     }
     // simple modes: beside the histograms and the planner, which are short chains of latency (config #4: 0.15 of 1.2 ms in line)
-    if (container != 0 && mode < 4 && !h->knobs.simple_ck_inline && (rc = launch_checksum_side(h, nb, d_in, dch, dbc, dsb, prm))) return rc;
+    if (container != 0 && mode < 4 && !h->knobs.simple_ck_inline && (rc = launch_checksum_side(h, nb, d_in, dch, dbc, dsb, ckp))) return rc;
     if (mode >= 4) {
         if ((rc = ensure_lz_workspace(h, nc, prm.chain))) return rc;
         if (prm.chain >= FL_BULK_MIN_CHAIN) {
@@ -954,7 +995,7 @@ int enqueue_pass(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t n
                 hipLaunchKernelGGL(k_lz_chain<false>, dim3(nc), dim3(64 * FL_CHAIN_WAVES), 0, st, d_in, dch, (uint16_t*)h->S.p,
                                    (uint32_t*)h->cflag.p, (uint32_t*)h->marks.p, (const uint32_t*)nullptr);
             }
-            if (container != 0 && (rc = launch_checksum_side(h, nb, d_in, dch, dbc, dsb, prm))) return rc;
+            if (container != 0 && (rc = launch_checksum_side(h, nb, d_in, dch, dbc, dsb, ckp))) return rc;
             {
                 ProfScope ps(h, K_LZ_PARSE);
                 hipLaunchKernelGGL(k_lz_parse<false>, dim3(nc), dim3(PZ_THREADS), 0, st, d_in, dch, prm, (const uint16_t*)h->S.p,
@@ -978,7 +1019,8 @@ int enqueue_pass(flate_hip_ctx* h, const fl_params& prm, uint32_t nc, uint32_t n
         ProfScope ps(h, K_BYTE_HIST);
         hipLaunchKernelGGL(k_byte_hist, dim3(nb), dim3(256), 0, st, d_in, dch, dbc, dsb, dhist);
     }
-    return enqueue_back_end(h, prm, nc, nb, c0, dch, dbc, dsb, d_in, d_out, d_outlen, d_status);
+    if ((rc = enqueue_back_end(h, prm, nc, nb, c0, dch, dbc, dsb, d_in, d_out, d_outlen, d_status)) || !h->join) return rc;
+    return enqueue_join_open(h, prm, nc, nb, c0, dch, d_out, d_outlen, d_status);
 }
 
 
@@ -1376,7 +1418,8 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->exitmap, &h->entry, &h->segtok, &h->tokbase, &h->bound, &h->sgroups, &h->sgroup0, &h->gmap, &h->gentry,
                       &h->sblocks, &h->st_in, &h->st_out, &h->st_inoff, &h->st_outlen, &h->st_status,
                       &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed, &h->dc_tab, &h->dc_bytes, &h->dc_of, &h->dcc_stage,
-                      &h->dcc_jobs, &h->dcc_chunks})
+                      &h->dcc_jobs, &h->dcc_chunks, &h->jn_scratch, &h->jn_streams, &h->jn_pstream, &h->jn_slot, &h->jn_len,
+                      &h->jn_status, &h->jn_cks, &h->jn_dst, &h->jn_scks})
         if (b->p) (void)hipFree(b->p);
     h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
@@ -1422,7 +1465,12 @@ size_t flate_hip_compress_bound(size_t n, int container, int mode) {
     const size_t hdr = container == 1 ? 18 : (container == 2 ? 6 : 0);
     // stored blocks: 5 bytes per 65535 (+ a possibly empty trailing one); a Huffman block never
     // beats that bound by more than its header; slack for the Q1 seam.
-    return n + (n / 32768 + 2) * 16 + hdr + 64 + n / 64;
+    return (size_t)fl_raw_bound(n) + hdr;
+}
+
+size_t flate_hip_joined_bound(uint64_t n, uint32_t piece_bytes, int container, int mode) {
+    (void)mode;
+    return (size_t)fl_join_bound(n, fl_join_piece_bytes(piece_bytes > FL_JOIN_MAX_PIECE ? 0u : piece_bytes), container);
 }
 
 int flate_hip_profile_enable(flate_hip_handle h, int enable) {
@@ -1616,7 +1664,8 @@ struct WsShift {  // a pass's view of the two-slice workspace: every buffer from
 
 int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container,
                   int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind,
-                  const FlushSpec* fs, flate_hip_plan* pl = nullptr, Mirror* mirror = nullptr, const DictCall* dc = nullptr);
+                  const FlushSpec* fs, flate_hip_plan* pl = nullptr, Mirror* mirror = nullptr, const DictCall* dc = nullptr,
+                  const JoinCall* jc = nullptr);
 
 // Pageable host buffers of some size (what every caller of the facade's compress(reader, writer) has): a
 // staged hipMemcpy each way moves about 10 GB/s and nothing overlaps.  Instead a few host threads copy the
@@ -2065,7 +2114,7 @@ int finish_call(CompressCall& cc, PassGuard& pass_guard) {
             HIP_OK(h, hipStreamSynchronize(h->s_out));
         else if ((rc = copy_out_host(h, cc.d_out, cc.d_outlen, n_chunks, *cc.hout, cc.out_shift, cc.out, cc.out_len)))
             return rc;
-    } else if (h->sync) {
+    } else if (h->sync && !h->join) {  // (the pieces of a joined call: the call goes on behind them)
         HIP_OK(h, hipStreamSynchronize(st));
     }
     return FLATE_HIP_OK;
@@ -2073,9 +2122,9 @@ int finish_call(CompressCall& cc, PassGuard& pass_guard) {
 
 int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container,
                   int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind,
-                  const FlushSpec* fs, flate_hip_plan* pl, Mirror* mirror, const DictCall* dc) {
+                  const FlushSpec* fs, flate_hip_plan* pl, Mirror* mirror, const DictCall* dc, const JoinCall* jc) {
     const bool planning = pl && !pl->ready;
-    if (!h || (!pl && !dc && (!in_off || !out_off)) || (!planning && (!out_len || !status))) return FLATE_HIP_E_INVALID_ARG;
+    if (!h || (!pl && !dc && !jc && (!in_off || !out_off)) || (!planning && (!out_len || !status))) return FLATE_HIP_E_INVALID_ARG;
     if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
     // The record is declared before the guards, so whatever way the call ends the guards' destructors run first, in this
     // order, and the record's vectors -- which copies on the input stream may still read -- are freed after them:
@@ -2107,14 +2156,14 @@ int compress_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off,
     cc.st = h->stream;
 
     int rc = 0;
-    if (!pl && !dc) {
+    if (!pl && !dc && !jc) {
         rc = fetch_offsets(h, in_off, n_chunks, memkind, cc.hin_);
         if (rc) return rc;
         rc = fetch_offsets(h, out_off, n_chunks, memkind, cc.hout_);
         if (rc) return rc;
     }
-    cc.hin = pl ? &pl->hin : dc ? &dc->hin : &cc.hin_;
-    cc.hout = pl ? &pl->hout : dc ? &dc->hout : &cc.hout_;
+    cc.hin = pl ? &pl->hin : dc ? &dc->hin : jc ? &jc->hin : &cc.hin_;
+    cc.hout = pl ? &pl->hout : dc ? &dc->hout : jc ? &jc->hout : &cc.hout_;
     cc.in_lo = (*cc.hin)[0], cc.in_hi = (*cc.hin)[n_chunks];
     cc.out_lo = (*cc.hout)[0], cc.out_hi = (*cc.hout)[n_chunks];
 
@@ -2299,6 +2348,100 @@ int flate_hip_compress_batch_dict(flate_hip_handle h, const uint8_t* in, const u
         HIP_OK(h, hipGetLastError());
     }
     return compress_impl(h, in, in_off, n_chunks, container, mode, out, out_off, out_len, status, memkind, nullptr, nullptr, nullptr, &dc);
+}
+
+// One gzip / zlib / raw stream from independent pieces (include/flate_hip.h: what the bytes are; join_plan.h: every
+// decision).  Here: the offsets on the host, the streams' and pieces' tables on the device, the pieces through
+// compress_impl as raw chunks into scratch slots (k_join_open behind every pass: enqueue_pass), then the scan and the pack.
+// Host buffers are staged whole.
+int flate_hip_compress_joined(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                              uint32_t piece_bytes, int container, int mode, uint8_t* out, const uint64_t* out_off,
+                              uint64_t* out_len, int32_t* status, int memkind) {
+    if (!h || !in_off || !out_off || !out_len || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    if (!fl_join_args_ok(piece_bytes, container, mode)) return FLATE_HIP_E_INVALID_ARG;
+    if (n_streams == 0) return FLATE_HIP_OK;
+    if (h->join) return FLATE_HIP_E_INVALID_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    const uint32_t piece = fl_join_piece_bytes(piece_bytes);
+    const bool host = memkind == FLATE_HIP_MEM_HOST;
+    hipStream_t st = h->stream;
+    int rc;
+    std::vector<uint64_t> hin, hout;
+    if ((rc = fetch_offsets(h, in_off, n_streams, memkind, hin))) return rc;
+    if ((rc = fetch_offsets(h, out_off, n_streams, memkind, hout))) return rc;
+    const uint64_t in_lo = hin[0], in_hi = hin[n_streams], out_lo = hout[0], out_hi = hout[n_streams];
+    if ((in_hi > in_lo && !in) || (out_hi > out_lo && !out)) return FLATE_HIP_E_INVALID_ARG;
+    // (host buffers are staged from their first byte on)
+    std::vector<fl_join_stream> streams;
+    const uint64_t total = fl_join_layout(hin.data(), hout.data(), n_streams, piece, host ? in_lo : 0, host ? out_lo : 0, streams);
+    if (total > FL_JOIN_MAX_PIECES) return FLATE_HIP_E_UNSUPPORTED;
+    const uint32_t np = (uint32_t)total;
+    JoinCall jc;
+    std::vector<uint32_t> piece_stream;
+    const uint64_t scratch_bytes = fl_join_tables(streams, piece, total, piece_stream, jc.hin, jc.hout);
+    jc.container = container;
+
+    if ((rc = ensure(h, h->jn_scratch, scratch_bytes + 16)) || (rc = ensure(h, h->jn_streams, sizeof(fl_join_stream) * (size_t)n_streams)) ||
+        (rc = ensure(h, h->jn_pstream, sizeof(uint32_t) * (size_t)np)) || (rc = ensure(h, h->jn_slot, sizeof(uint64_t) * ((size_t)np + 1))) ||
+        (rc = ensure(h, h->jn_len, sizeof(uint64_t) * (size_t)np)) || (rc = ensure(h, h->jn_status, sizeof(int32_t) * (size_t)np)) ||
+        (rc = ensure(h, h->jn_cks, sizeof(uint32_t) * (size_t)np)) || (rc = ensure(h, h->jn_dst, sizeof(uint64_t) * (size_t)np)) ||
+        (rc = ensure(h, h->jn_scks, sizeof(uint32_t) * (size_t)n_streams)))
+        return rc;
+    const uint8_t* d_in = in;
+    uint8_t* d_out = out;
+    uint64_t* d_outlen = out_len;
+    int32_t* d_status = status;
+    if (host) {
+        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16)) || (rc = ensure(h, h->st_out, (out_hi - out_lo) + 16)) ||
+            (rc = ensure(h, h->st_outlen, sizeof(uint64_t) * (size_t)n_streams)) || (rc = ensure(h, h->st_status, sizeof(int32_t) * (size_t)n_streams)))
+            return rc;
+        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+        d_in = (const uint8_t*)h->st_in.p;
+        d_out = (uint8_t*)h->st_out.p;
+        d_outlen = (uint64_t*)h->st_outlen.p;
+        d_status = (int32_t*)h->st_status.p;
+    }
+    HIP_OK(h, hipMemcpyAsync(h->jn_streams.p, streams.data(), sizeof(fl_join_stream) * (size_t)n_streams, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->jn_pstream.p, piece_stream.data(), sizeof(uint32_t) * (size_t)np, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->jn_slot.p, jc.hout.data(), sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));  // (the tables are this call's vectors)
+    jc.d_piece_stream = (const uint32_t*)h->jn_pstream.p;
+    jc.d_streams = (const fl_join_stream*)h->jn_streams.p;
+    jc.d_piece_cks = (uint32_t*)h->jn_cks.p;
+
+    // the pieces: raw chunks of the chunk path into their scratch slots, k_join_open behind every pass
+    struct JoinGuard {
+        flate_hip_ctx* h;
+        ~JoinGuard() { h->join = nullptr; }
+    } join_guard{h};
+    h->join = &jc;
+    rc = compress_impl(h, d_in, nullptr, np, FLATE_HIP_RAW, mode, (uint8_t*)h->jn_scratch.p, nullptr, (uint64_t*)h->jn_len.p,
+                       (int32_t*)h->jn_status.p, FLATE_HIP_MEM_DEVICE, nullptr, nullptr, nullptr, nullptr, &jc);
+    h->join = nullptr;
+    if (rc) return rc;
+    {
+        ProfScope ps(h, K_JOIN_SCAN);
+        hipLaunchKernelGGL(k_join_scan, dim3(n_streams), dim3(256), 0, st, jc.d_streams, piece, container, h->crc,
+                           (const uint64_t*)h->jn_len.p, (const int32_t*)h->jn_status.p, (const uint32_t*)h->jn_cks.p,
+                           (uint64_t*)h->jn_dst.p, d_outlen, d_status, (uint32_t*)h->jn_scks.p);
+    }
+    {
+        ProfScope ps(h, K_JOIN_PACK);
+        hipLaunchKernelGGL(k_join_pack, gather_grid(np), dim3(256), 0, st, (const uint8_t*)h->jn_scratch.p, (const uint64_t*)h->jn_slot.p,
+                           (const uint64_t*)h->jn_len.p, (const uint64_t*)h->jn_dst.p, jc.d_piece_stream, jc.d_streams, container,
+                           (const uint64_t*)d_outlen, (const int32_t*)d_status, (const uint32_t*)h->jn_scks.p, d_out);
+    }
+    HIP_OK(h, hipGetLastError());
+    if (host) {
+        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+        if ((rc = copy_out_host(h, d_out, d_outlen, n_streams, hout, out_lo, out, out_len))) return rc;
+    } else if (h->sync) {
+        HIP_OK(h, hipStreamSynchronize(st));
+    }
+    return FLATE_HIP_OK;
 }
 
 int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,

@@ -331,7 +331,44 @@ class Engine:
         res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
         return res, [int(s) for s in status]
 
+    def joined_bound(self, n, piece=65535, container=0, mode=6):
+        return int(self._L.flate_hip_joined_bound(int(n), int(piece), container, mode))
+
+    def compress_joined(self, streams, container, mode, piece=65535, caps=None):
+        """Every input as ONE gzip / zlib / raw stream of independent pieces of `piece` bytes (flate_hip_compress_joined;
+        levels 4..9, piece 1..65535): the pieces are compressed with no history at the rate of the chunk path and joined
+        with sync-flush markers, one header and one footer around them -- any inflater reads the result.  caps: slot
+        size per stream (default: joined_bound).  Returns (list of bytes, list of status codes)."""
+        self._sync_env()
+        if not 1 <= int(piece) <= _capi.JOIN_MAX_PIECE:
+            raise ValueError("piece must be 1..%d" % _capi.JOIN_MAX_PIECE)
+        n = len(streams)
+        if n == 0:
+            return [], []
+        blob, in_off = self._host_input(streams)
+        if caps is None:
+            caps = [(self.joined_bound(len(c), piece, container, mode) + 7) & ~7 for c in streams]
+        caps = np.array([int(c) for c in caps], dtype=np.uint64)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(caps, out=out_off[1:])
+        out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int32)
+        rc = self._L.flate_hip_compress_joined(self._h, blob.ctypes.data, in_off.ctypes.data, n, int(piece), container, mode,
+                                               out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                               status.ctypes.data, MEM_HOST)
+        self._check(rc, "flate_hip_compress_joined")
+        res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
+        return res, [int(s) for s in status]
+
     # ---- device buffers (raw pointers; everything already in HBM) ----
+    def compress_joined_device(self, in_ptr, in_off_ptr, n_streams, piece, container, mode, out_ptr, out_off_ptr,
+                               out_len_ptr, status_ptr):
+        self._sync_env()
+        rc = self._L.flate_hip_compress_joined(self._h, in_ptr, in_off_ptr, n_streams, int(piece), container, mode, out_ptr,
+                                               out_off_ptr, out_len_ptr, status_ptr, MEM_DEVICE)
+        self._check(rc, "flate_hip_compress_joined")
+
     def compress_device(self, in_ptr, in_off_ptr, n_chunks, container, mode, out_ptr, out_off_ptr, out_len_ptr,
                         status_ptr):
         self._sync_env()
@@ -466,7 +503,7 @@ class Engine:
 
     def profile_read(self):
         """{kernel name: (total_ms, launches)}"""
-        cap = 32
+        cap = 64
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         cnt = (C.c_uint64 * cap)()

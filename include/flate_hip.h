@@ -273,6 +273,53 @@ int flate_hip_compress_batch_dict(flate_hip_handle h, const uint8_t* in, const u
                                   uint32_t n_dicts, const uint32_t* dict_of);
 
 /*
+ * Joined compress, levels 4..9: every input becomes ONE valid gzip / zlib / raw stream made of independent pieces, at the
+ * rate of the batched chunk path -- what pigz -i and zlib's Z_FULL_FLUSH give.  The argument shape, the memory kinds and
+ * the rules for the slots are those of flate_hip_compress_batch (stream i is in[in_off[i] .. in_off[i+1]), its slot
+ * out[out_off[i] .. out_off[i+1])); piece_bytes is 1..65535, 0 means 65535.
+ *   pieces   stream i has N bytes and P = max(1, ceil(N / piece_bytes)) pieces; piece k is its bytes
+ *            [k * piece_bytes, min((k + 1) * piece_bytes, N)).  Every piece is compressed with no history.
+ *   bytes    the container's header, F(piece_0) .. F(piece_{P-2}), L(piece_{P-1}), the container's footer, where
+ *            L(x) is what flate_hip_compress_batch writes for x as a raw stream, and
+ *            F(x) is what a fresh raw reference compressor has written after write(x); flush() (deflate.zig:335-337,
+ *            276-278): L(x) with the final-block bit of its last block cleared, then the sync-flush marker -- 00 00 ff ff
+ *            when 1..5 padding bits stand in the last byte of that block, 00 00 00 ff ff when it ends 0, 6 or 7 bits into
+ *            a byte (a stored block ends at 0).
+ *            The footer covers the WHOLE stream: gzip CRC-32 and ISIZE = N mod 2^32, zlib the big-endian Adler-32.
+ *            With P == 1 the stream is byte for byte that of flate_hip_compress_batch with the same container.
+ *            N may exceed 4 GiB: a joined stream has no 32-bit stream positions.
+ *   status   0; FLATE_HIP_ST_OUTPUT_TOO_SMALL (100) when the slot is too small -- only that stream is affected, nothing is
+ *            written into its slot and out_len is 0 --; FLATE_HIP_ST_REFERENCE_Q1_STREAM (102) when any piece is such a
+ *            stream: the bytes are still as defined above (the first non-zero piece status is reported).  With
+ *            FLATE_HIP_DEFLATE_REPAIR_Q1 on the handle every piece is repaired and 102 does not occur.
+ *   bound    flate_hip_joined_bound(N, piece_bytes, container, mode) = header + the sum over the pieces of
+ *            (flate_hip_compress_bound(length, FLATE_HIP_RAW, mode) + 5) + footer always suffices.
+ * Modes 0 and 1, a container outside 0..2 or piece_bytes above 65535: FLATE_HIP_E_INVALID_ARG, nothing is written.
+ * n_streams == 0: FLATE_HIP_OK.  A call may have at most 2^31 - 1 pieces, else FLATE_HIP_E_UNSUPPORTED.
+ * What it costs in ratio: no match reaches back over a piece's start and every piece has its own Huffman tables
+ * (DESIGN.md 4b'''': 256 MiB of text at level 6, 65535-byte pieces against the whole-stream path).
+ * How: the pieces go through the chunk passes of flate_hip_compress_batch as raw chunks (no kernel of those changes);
+ * behind every pass k_join_open clears the final-block bits and writes the markers while the pass's block plans are
+ * valid, and k_checksum takes the container's checksum a piece at a time; then k_join_scan gives every piece its place
+ * (a scan of the piece lengths per stream) and combines the pieces' checksums on the device, and k_join_pack copies the
+ * pieces behind the header (16-byte stores) and writes header and footer.  No byte outside a stream's slot is written.
+ * Workspace: the pieces are compressed into a scratch region of the handle that holds ALL pieces of the call -- the
+ * simple call-wide layout, not a per-pass one: per piece its raw bound + 5 rounded up to 16 bytes with 16 to spare (about
+ * 1.02 x the input + 170 bytes a piece) and 36 bytes of tables, besides the workspace of a chunk-path pass;
+ * flate_hip_debug_workspace_bytes counts it.
+ * Waits: those of a chunk-path batch on the same memory kind -- the offsets are read back once, and the host waits once per
+ * pass for the pass's tables -- and one more for the call's own tables.  Not capturable in a graph.
+ * FLATE_HIP_MEM_HOST: input and slots are staged whole (no pinned sub-batch pipeline); a slot's bytes beyond out_len[i]
+ * are unspecified.
+ * Not covered: planned, sharded and dictionary calls, pieces above 65535 bytes or pieces that keep history, the resumable
+ * deflater.
+ */
+size_t flate_hip_joined_bound(uint64_t n, uint32_t piece_bytes, int container, int mode);
+int flate_hip_compress_joined(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                              uint32_t piece_bytes, int container, int mode, uint8_t* out, const uint64_t* out_off,
+                              uint64_t* out_len, int32_t* status, int memkind);
+
+/*
  * Size probe: how many bytes each of n_chunks independent streams inflates to, without inflating it.  The arguments have
  * the shape of flate_hip_decompress_batch without `out` and `out_off`; flags bit 0 = FLATE_HIP_INFLATE_STRICT_Q6;
  * consumed may be NULL.

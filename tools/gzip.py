@@ -2,7 +2,9 @@
 """gzip <file>: writes <file>.gz with the MI355X engine -- the reference's bin/gzip.zig:20
 (`gzip.compress(input_file.reader(), output_file.writer(), .{})`, comparable to `gzip -kfn`).
 Options beyond the reference's tool: -l LEVEL (4..9), --huffman, --store, and --piece N (with --huffman or --store):
-bounded memory -- the file is read N bytes at a time and compressed by a resumable compressor as it arrives."""
+bounded memory -- the file is read N bytes at a time and compressed by a resumable compressor as it arrives;
+--joined [N] (levels 4..9): one gzip stream of independent pieces of N bytes (1..65535, default 65535) at the rate of the
+batched chunk path, as pigz -i writes it -- a file of any length, a little larger than the whole-stream output."""
 import argparse
 import os
 os.environ.setdefault("FLATE_HIP_PRELOAD_TORCH_HIP", "1")  # one HIP runtime per process: torch, imported later, brings its own (flate_amd/_capi.py)
@@ -18,7 +20,10 @@ def main(argv=None):
     ap.add_argument("--huffman", action="store_true")
     ap.add_argument("--store", action="store_true")
     ap.add_argument("--piece", type=int, default=None)
+    ap.add_argument("--joined", type=int, nargs="?", const=65535, default=None, metavar="N")
     a = ap.parse_args(argv)
+    if a.joined is not None and (a.huffman or a.store or a.piece is not None or not 1 <= a.joined <= 65535):
+        ap.error("--joined [N] needs 1 <= N <= 65535 and takes none of --huffman, --store, --piece")
     if a.piece is not None and (a.piece < 1 or not (a.huffman or a.store)):
         ap.error("--piece N needs N >= 1 and --huffman or --store (levels 4..9 are not resumable)")
     from flate_amd import gzip
@@ -27,6 +32,8 @@ def main(argv=None):
             gzip.huffman.compress(src, dst, piece=a.piece)
         elif a.store:
             gzip.store.compress(src, dst, piece=a.piece)
+        elif a.joined is not None:
+            gzip.compress(src, dst, gzip.Options(level=a.level), joined=a.joined)
         else:
             gzip.compress(src, dst, gzip.Options(level=a.level))
     return 0
