@@ -48,6 +48,9 @@ SYMBOLS = [
     "flate_hip_decompress_batch_dict", "flate_hip_inflater_set_dictionary",
     "flate_hip_compress_batch_dict",
     "flate_hip_joined_bound", "flate_hip_compress_joined",
+    "flate_hip_index_build", "flate_hip_index_destroy", "flate_hip_index_stream_info", "flate_hip_index_points",
+    "flate_hip_index_export_size", "flate_hip_index_export", "flate_hip_index_import", "flate_hip_decompress_ranges",
+    "flate_hip_debug_index_passes", "flate_hip_debug_index_paths",
 ]
 
 
@@ -186,6 +189,28 @@ def lib():
     L.flate_hip_compress_joined.restype = C.c_int
     L.flate_hip_inflater_set_dictionary.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, C.c_int, vp]
     L.flate_hip_inflater_set_dictionary.restype = C.c_int
+    L.flate_hip_index_build.argtypes = [vp, vp, u64p, C.c_uint32, C.c_int, C.c_int, vp, u64p, u64p, i32p, u64p, C.c_int,
+                                        C.c_uint64, C.POINTER(C.c_void_p)]
+    L.flate_hip_index_build.restype = C.c_int
+    L.flate_hip_index_destroy.argtypes = [vp, vp]
+    L.flate_hip_index_destroy.restype = C.c_int
+    L.flate_hip_index_stream_info.argtypes = [vp, vp, C.c_uint32, u64p, i32p, u64p]
+    L.flate_hip_index_stream_info.restype = C.c_int
+    L.flate_hip_index_points.argtypes = [vp, vp, C.c_uint32, u64p, u64p, C.c_uint64]
+    L.flate_hip_index_points.restype = C.c_int64
+    L.flate_hip_index_export_size.argtypes = [vp, vp, u64p]
+    L.flate_hip_index_export_size.restype = C.c_int
+    L.flate_hip_index_export.argtypes = [vp, vp, vp, C.c_uint64]
+    L.flate_hip_index_export.restype = C.c_int
+    L.flate_hip_index_import.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.flate_hip_index_import.restype = C.c_int
+    L.flate_hip_decompress_ranges.argtypes = [vp, vp, vp, u64p, C.c_uint32, C.c_uint32, vp, u64p, u64p, vp, u64p, u64p, i32p,
+                                              C.c_int]
+    L.flate_hip_decompress_ranges.restype = C.c_int
+    L.flate_hip_debug_index_passes.argtypes = [vp, u64p]
+    L.flate_hip_debug_index_passes.restype = C.c_int
+    L.flate_hip_debug_index_paths.argtypes = [vp, u64p]
+    L.flate_hip_debug_index_paths.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.flate_hip_debug_tokens.restype = C.c_int64
     _lib = L

@@ -7,6 +7,7 @@ behaviour, over the C ABI of libflate_hip.so.
   decompress(reader, writer)            flate.zig:10-12
   Decompressor / decompressor(reader)   flate.zig:15-22   (decompress / next / read / reader / reset / set_reader)
   decompress_members(data)              -- (not in the reference: all concatenated members in one GPU call)
+  build_index(data, spacing=None)       -- (not in the reference: a seek index; StreamIndex.read_at(offset, n))
   huffman.{compress,Compressor,compressor}   flate.zig:44-56
   store.{compress,Compressor,compressor}     flate.zig:59-71
   Options(level=Level.default), Level   deflate.zig:15-32
@@ -670,6 +671,58 @@ class ContainerModule:
             break
         raise_for_status(st[0])
         return outs[0]
+
+    def build_index(self, data, spacing=None, engine=None):
+        """A seek index over the first member of `data` (bytes-like, or a reader that is read to its end): the stream is
+        decoded once (flate_hip_index_build) and every `spacing` output bytes or so (default 1 MiB) a block start is kept
+        with the 32 KiB in front of it; StreamIndex.read_at then decodes only from the nearest point.  Raises the stream's
+        error if it does not decode."""
+        eng = engine or default_engine()
+        data = _read_all(data)
+        ix, _, st, _ = eng.build_index([data], self._container, 0, spacing)
+        raise_for_status(st[0])
+        return StreamIndex(ix)
+
+    def index_from_bytes(self, blob, data, engine=None):
+        """the StreamIndex of StreamIndex.to_bytes() and the stream it was built from"""
+        return StreamIndex.from_bytes(blob, data, engine)
+
+
+class StreamIndex:
+    """Random access into one compressed stream (ContainerModule.build_index).  There is no checksum over a part of a
+    stream: the index must be used with the bytes it was built from."""
+
+    def __init__(self, index):
+        self._ix = index
+        self.size = index.info(0)[0]
+
+    @classmethod
+    def from_bytes(cls, blob, data, engine=None):
+        eng = engine or default_engine()
+        ix = eng.index_from_bytes(blob, [_read_all(data)])
+        if ix.n != 1 or ix.info(0)[1] != 0:
+            raise ValueError("not the index of one stream that decoded")
+        return cls(ix)
+
+    def points(self):
+        """[(in_bit, out_pos)]: where decoding can start"""
+        return self._ix.points(0)
+
+    def read_ranges(self, ranges):
+        """[(offset, n)] -> list of bytes, each clipped to the stream's size"""
+        outs, st = self._ix.read_ranges([(0, int(o), int(n)) for o, n in ranges])
+        for s in st:
+            raise_for_status(s)
+        return outs
+
+    def read_at(self, offset, n):
+        return self.read_ranges([(offset, n)])[0]
+
+    def to_bytes(self):
+        return self._ix.to_bytes()
+
+    def close(self):
+        self._ix.close()
 
 
 def compress_bytes(data, container=_capi.RAW, mode=6, engine=None):

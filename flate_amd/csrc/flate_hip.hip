@@ -21,9 +21,11 @@
 #include "kernels_block.h"
 #include "kernels_common.h"
 #include "dict_compress_plan.h"
+#include "index_plan.h"
 #include "join_plan.h"
 #include "kernels_deflater.h"
 #include "kernels_dict.h"
+#include "kernels_index.h"
 #include "kernels_inflate.h"
 #include "kernels_inflate_par.h"
 #include "kernels_inflate_size.h"
@@ -77,6 +79,10 @@ enum KernelId {
     K_JOIN_OPEN,
     K_JOIN_SCAN,
     K_JOIN_PACK,
+    K_INDEX_WALK,
+    K_INDEX_WINDOWS,
+    K_INFLATE_RANGE,
+    K_RANGE_PACK,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
@@ -86,7 +92,8 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_inflate_size", "k_inflate_size_span",
                                            "k_member_scan", "k_member_chain", "k_member_walk", "k_member_pack", "k_member_fold",
                                            "k_gather", "k_inflater", "k_deflater", "k_inflate_dict", "k_dict_stage",
-                                           "k_join_open", "k_join_scan", "k_join_pack"};
+                                           "k_join_open", "k_join_scan", "k_join_pack",
+                                           "k_index_walk", "k_index_windows", "k_inflate_range", "k_range_pack"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -148,6 +155,7 @@ struct fl_knobs {
     int64_t inflate_ring = -1;            // FLATE_HIP_INFLATE_RING: -1 unset
     bool member_scan = true;              // FLATE_HIP_MEMBER_SCAN: 0 = gzip members are walked, not searched for (flate_hip_decompress_members)
     uint32_t member_candidates = FL_MEM_CAND_DEFAULT;  // FLATE_HIP_MEMBER_CANDIDATES: a call with more candidates than this walks
+    uint64_t index_pass_bytes = FL_IDX_PASS_BYTES;     // FLATE_HIP_INDEX_PASS_BYTES: scratch of one pass of flate_hip_decompress_ranges
 };
 
 struct flate_hip_ctx {
@@ -211,6 +219,11 @@ struct flate_hip_ctx {
     DevBuf mb_tiles, mb_tileoff, mb_cand, mb_chunks, mb_psize, mb_pstatus, mb_pcons, mb_succ, mb_chain, mb_taboff, mb_tabn, mb_non,
         mb_tabstart, mb_tabsize, mb_denseoff, mb_dstart, mb_dsize, mb_outlen, mb_status, mb_cons, mb_nmem;
     uint64_t dbg_member[3] = {0, 0, 0};
+    // flate_hip_index_build: the walk jobs, their records, the points as the walkers wrote them, the window copies' table;
+    // flate_hip_decompress_ranges: the range jobs, the pack kernel's table, the scratch of a pass (index_plan.h); for
+    // flate_hip_debug_index_passes the passes of the last ranges call
+    DevBuf ix_jobs, ix_recs, ix_ptbit, ix_ptpos, ix_wtab, ix_rjobs, ix_rtab, ix_scratch;
+    uint64_t dbg_index_passes = 0, dbg_index_spans = 0, dbg_index_whole = 0;
     bool ws_fixed = false;   // the two-stream passes are being enqueued: ensure() may not grow a buffer (compress_impl)
     // last level 4..9 call, for the debug seam
     uint32_t dbg_pass_chunks = 0;
@@ -419,6 +432,7 @@ void read_knobs(fl_knobs& k, uint64_t span_default) {
     if ((e = getenv("FLATE_HIP_INFLATE_PAR"))) k.inflate_par = atoll(e);
     if ((e = getenv("FLATE_HIP_INFLATE_RING"))) k.inflate_ring = atoll(e);
     if ((e = getenv("FLATE_HIP_MEMBER_SCAN"))) k.member_scan = atoi(e) != 0;
+    if ((e = getenv("FLATE_HIP_INDEX_PASS_BYTES")) && atoll(e) > 0) k.index_pass_bytes = (uint64_t)atoll(e);
     if ((e = getenv("FLATE_HIP_MEMBER_CANDIDATES")) && atoll(e) >= 0 && atoll(e) <= 0x7fffffffll) k.member_candidates = (uint32_t)atoll(e);
 }
 bool is_pinned_host(const void* p) {
@@ -1249,14 +1263,19 @@ int try_span_inflate(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std:
 // by size_plan.h), count every span with a wave of its own and follow each stream's chain of span records on the host.
 // A stream whose chain closes gets its size / status / consumed here and chunks[i].skip = 1; every other stream stays for
 // the wave-per-stream launch.  Two host waits.  Returns the number of streams finished, or -1 (a HIP call failed).
-int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::vector<fl_chunk>& chunks, int container, int flags,
-                  uint64_t* d_sizes, int32_t* d_status, uint64_t* d_consumed) {
+// The long streams of a batch cut into spans and every span counted (k_inflate_size<true>): elig gets the streams that
+// were looked at, spans / recs the spans of stream elig[k] at [sp_first[k], sp_first[k + 1]) with their records.  Returns
+// the number of spans, 0 when nothing is cut, -1 when a HIP call fails.  The size probe follows the chains and sums; the
+// index walk (index_walk) walks every span of a closed chain again for its points.
+int size_span_records(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, const std::vector<fl_chunk>& chunks, int container, int flags,
+                      std::vector<uint32_t>& elig, std::vector<fl_size_span>& spans, std::vector<uint32_t>& sp_first,
+                      std::vector<fl_size_rec>& recs) {
     const uint32_t n_chunks = (uint32_t)chunks.size();
     if (flags & 1) return 0;  // (as decompress: the scan's first two steps know the lenient header only)
     const uint32_t n_cu = device_cu_count(h);
     std::vector<uint64_t> lens(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; i++) lens[i] = chunks[i].in_len;
-    std::vector<uint32_t> elig, pieces;
+    for (uint32_t i = 0; i < n_chunks; i++) lens[i] = chunks[i].skip ? 0 : chunks[i].in_len;
+    std::vector<uint32_t> pieces;
     fl_size_eligible(lens.data(), n_chunks, h->knobs.span_min_bytes, n_cu, elig);
     if (elig.empty()) return 0;
     std::vector<uint64_t> elens(elig.size());
@@ -1285,8 +1304,8 @@ int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::ve
     if (const int sc = scan_block_starts(h, st, d_in, flags, points, found); sc <= 0) return sc;
     const fl_chunk* dch = (const fl_chunk*)h->chunks.p;
     // ---- the spans: the stream start, then every distinct position found; a span ends where the next one starts
-    std::vector<fl_size_span> spans;
-    std::vector<uint32_t> sp_first(elig.size() + 1, 0);
+    spans.clear();
+    sp_first.assign(elig.size() + 1, 0);
     for (size_t k = 0; k < elig.size(); k++) {
         fl_size_span s0;
         s0.start_bit = 0;
@@ -1311,9 +1330,18 @@ int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::ve
         hipLaunchKernelGGL(k_inflate_size<true>, dim3(nsp), dim3(64), 0, st, d_in, dch, container, flags, (uint64_t*)nullptr,
                            (int32_t*)nullptr, (uint64_t*)nullptr, (const fl_size_span*)h->sz_spans.p, (fl_size_rec*)h->sz_recs.p);
     }
-    std::vector<fl_size_rec> recs(nsp);
+    recs.resize(nsp);
     if (hipMemcpyAsync(recs.data(), h->sz_recs.p, sizeof(fl_size_rec) * nsp, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
     if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    return (int)nsp;
+}
+
+int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::vector<fl_chunk>& chunks, int container, int flags,
+                  uint64_t* d_sizes, int32_t* d_status, uint64_t* d_consumed) {
+    std::vector<uint32_t> elig, sp_first;
+    std::vector<fl_size_span> spans;
+    std::vector<fl_size_rec> recs;
+    if (const int nsp = size_span_records(h, st, d_in, chunks, container, flags, elig, spans, sp_first, recs); nsp <= 0) return nsp;
     // ---- the chains
     std::vector<fl_span_fin> fin;
     for (size_t k = 0; k < elig.size(); k++) {
@@ -1419,7 +1447,8 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->sblocks, &h->st_in, &h->st_out, &h->st_inoff, &h->st_outlen, &h->st_status,
                       &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed, &h->dc_tab, &h->dc_bytes, &h->dc_of, &h->dcc_stage,
                       &h->dcc_jobs, &h->dcc_chunks, &h->jn_scratch, &h->jn_streams, &h->jn_pstream, &h->jn_slot, &h->jn_len,
-                      &h->jn_status, &h->jn_cks, &h->jn_dst, &h->jn_scks})
+                      &h->jn_status, &h->jn_cks, &h->jn_dst, &h->jn_scks, &h->ix_jobs, &h->ix_recs, &h->ix_ptbit, &h->ix_ptpos, &h->ix_wtab,
+                      &h->ix_rjobs, &h->ix_rtab, &h->ix_scratch})
         if (b->p) (void)hipFree(b->p);
     h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
@@ -4111,6 +4140,466 @@ int flate_hip_debug_inflate_paths(flate_hip_handle h, uint64_t counts[4]) {
     counts[1] = h->dbg_span_taken - h->dbg_span_done;
     counts[2] = h->dbg_par_taken - handed;
     counts[3] = handed;
+    return FLATE_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The seek index (index_plan.h, kernels_index.h): its tables live on the host, its windows on the device.
+struct flate_hip_index {
+    fl_idx_tab tab;
+    uint8_t* d_win = nullptr;  // tab.win_bytes bytes
+};
+
+namespace {
+
+// n values of a caller's array to the host (memkind says where they are)
+template <class T>
+int fetch_array(flate_hip_ctx* h, const T* p, uint64_t n, int memkind, std::vector<T>& host) {
+    host.resize(n);
+    if (!n) return FLATE_HIP_OK;
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        memcpy(host.data(), p, sizeof(T) * n);
+    } else {
+        HIP_OK(h, hipMemcpyAsync(host.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+    }
+    return FLATE_HIP_OK;
+}
+
+int index_alloc_windows(flate_hip_ctx* h, flate_hip_index* ix) {
+    if (!ix->tab.win_bytes) return FLATE_HIP_OK;
+    if (hipMalloc((void**)&ix->d_win, ix->tab.win_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ix->d_win = nullptr;
+        h->last_error = "hipMalloc(" + std::to_string(ix->tab.win_bytes) + "): the index's windows";
+        return FLATE_HIP_E_ALLOC;
+    }
+    return FLATE_HIP_OK;
+}
+
+// The block starts of the streams the build found good, walked a wave per stream -- a long stream a wave per span of
+// the size probe's, where the spans' chain closes; else whole by one wave: always correct, only slow -- and the windows
+// copied out of the decoded bytes.  d_in / d_out:
+// the batch on the device, in_shift / out_shift what their offsets are less than the caller's.
+int index_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const uint8_t* d_out, const std::vector<uint64_t>& hin,
+               const std::vector<uint64_t>& hout, uint64_t in_shift, uint64_t out_shift, int container, int flags) {
+    hipStream_t st = h->stream;
+    fl_idx_tab& t = ix->tab;
+    const uint32_t n = (uint32_t)t.streams.size();
+    int rc;
+    std::vector<fl_chunk> chunks(n);
+    for (uint32_t i = 0; i < n; i++) {
+        fl_chunk c{};
+        c.in_off = hin[i] - in_shift;
+        c.in_len = (uint32_t)t.streams[i].in_len;
+        c.skip = t.streams[i].status != 0;  // (not walked, and not cut below)
+        chunks[i] = c;
+    }
+    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n))) return rc;
+    HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));
+    // ---- long streams: the size probe's spans, and where their chain closes a walk per live span
+    std::vector<std::vector<fl_idx_span_walk>> cut(n);
+    {
+        std::vector<uint32_t> elig, sp_first;
+        std::vector<fl_size_span> spans;
+        std::vector<fl_size_rec> recs;
+        const int nsp = size_span_records(h, st, d_in, chunks, container, flags, elig, spans, sp_first, recs);
+        if (nsp < 0) {
+            h->last_error = std::string("index walk by spans: ") + hipGetErrorString(hipGetLastError());
+            return FLATE_HIP_E_LAUNCH;
+        }
+        for (size_t k = 0; nsp > 0 && k < elig.size(); k++) {
+            const uint32_t a = sp_first[k], b = sp_first[k + 1];
+            if (b - a >= 2) fl_idx_span_walks(spans.data() + a, recs.data() + a, b - a, t.streams[elig[k]].size, t.spacing, cut[elig[k]]);
+        }
+    }
+    std::vector<fl_idx_walk_job> jobs;
+    std::vector<uint32_t> job0(n + 1, 0);  // the jobs of stream i: [job0[i], job0[i + 1])
+    uint64_t cap_total = 0;
+    h->dbg_index_spans = h->dbg_index_whole = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        job0[i] = (uint32_t)jobs.size();
+        if (t.streams[i].status != 0) continue;
+        if (cut[i].empty()) cut[i].push_back(fl_idx_span_walk{0, ~0ull, 0, fl_idx_max_points(t.streams[i].size, t.spacing), 1});
+        (cut[i].size() > 1 ? h->dbg_index_spans : h->dbg_index_whole)++;
+        for (const fl_idx_span_walk& w : cut[i]) {
+            fl_idx_walk_job jb{};
+            jb.start_bit = w.start_bit;
+            jb.stop_bit = w.stop_bit;
+            jb.base = w.base;
+            jb.point0 = cap_total;
+            jb.cap = w.cap;
+            jb.stream = i;
+            jb.first = w.first;
+            cap_total += jb.cap;
+            jobs.push_back(jb);
+        }
+    }
+    job0[n] = (uint32_t)jobs.size();
+    const uint32_t nj = (uint32_t)jobs.size();
+    if (!nj) return FLATE_HIP_OK;
+    if ((rc = ensure(h, h->ix_jobs, sizeof(fl_idx_walk_job) * nj)) || (rc = ensure(h, h->ix_recs, sizeof(fl_idx_walk_rec) * nj)) ||
+        (rc = ensure(h, h->ix_ptbit, sizeof(uint64_t) * cap_total)) || (rc = ensure(h, h->ix_ptpos, sizeof(uint64_t) * cap_total)))
+        return rc;
+    HIP_OK(h, hipMemcpyAsync(h->ix_jobs.p, jobs.data(), sizeof(fl_idx_walk_job) * nj, hipMemcpyHostToDevice, st));
+    {
+        ProfScope ps(h, K_INDEX_WALK);
+        hipLaunchKernelGGL(k_index_walk, dim3(nj), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p, container, flags, t.spacing,
+                           (const fl_idx_walk_job*)h->ix_jobs.p, (fl_idx_walk_rec*)h->ix_recs.p, (uint64_t*)h->ix_ptbit.p,
+                           (uint64_t*)h->ix_ptpos.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    std::vector<fl_idx_walk_rec> recs(nj);
+    std::vector<uint64_t> bit(cap_total), pos(cap_total);
+    HIP_OK(h, hipMemcpyAsync(recs.data(), h->ix_recs.p, sizeof(fl_idx_walk_rec) * nj, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(bit.data(), h->ix_ptbit.p, sizeof(uint64_t) * cap_total, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(pos.data(), h->ix_ptpos.p, sizeof(uint64_t) * cap_total, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipStreamSynchronize(st));
+    // ---- the tables, and where every window comes from and goes
+    std::vector<uint64_t> wtab;  // src | len | dst, a row each
+    for (uint32_t i = 0; i < n; i++) {
+        if (job0[i] == job0[i + 1]) continue;
+        fl_idx_stream& s = t.streams[i];
+        s.point0 = t.points.size();
+        uint64_t total = 0;
+        bool good = true;
+        for (uint32_t k = job0[i]; k < job0[i + 1] && good; k++) {
+            const fl_idx_walk_job& jb = jobs[k];
+            const fl_idx_walk_rec& r = recs[k];
+            good = r.status == 0 && r.n_points <= jb.cap && jb.base == total && (r.final_seen != 0) == (k + 1 == job0[i + 1]);
+            total += r.out_len;
+            for (uint64_t q = 0; good && q < r.n_points; q++) {
+                fl_idx_point p;
+                p.in_bit = bit[jb.point0 + q];
+                p.out_pos = pos[jb.point0 + q];
+                p.win_off = t.win_bytes;
+                t.win_bytes += fl_idx_window_len(p.out_pos);
+                t.points.push_back(p);
+            }
+        }
+        s.n_points = t.points.size() - s.point0;
+        if (!good || total != s.size || s.n_points < 1) {
+            h->last_error = "index walk of stream " + std::to_string(i) + " disagrees with its decode";
+            return FLATE_HIP_E_LAUNCH;
+        }
+    }
+    const uint64_t np = t.points.size();
+    wtab.resize(3 * np);
+    for (uint32_t i = 0; i < n; i++) {
+        const fl_idx_stream& s = t.streams[i];
+        for (uint64_t q = s.point0; q < s.point0 + s.n_points; q++) {
+            const fl_idx_point& p = t.points[q];
+            const uint64_t wl = fl_idx_window_len(p.out_pos);
+            wtab[q] = (hout[i] - out_shift) + p.out_pos - wl;
+            wtab[np + q] = wl;
+            wtab[2 * np + q] = p.win_off;
+        }
+    }
+    if (!t.win_bytes) return FLATE_HIP_OK;
+    if ((rc = index_alloc_windows(h, ix)) || (rc = ensure(h, h->ix_wtab, sizeof(uint64_t) * 3 * np))) return rc;
+    HIP_OK(h, hipMemcpyAsync(h->ix_wtab.p, wtab.data(), sizeof(uint64_t) * 3 * np, hipMemcpyHostToDevice, st));
+    {
+        ProfScope ps(h, K_INDEX_WINDOWS);
+        const uint64_t* w = (const uint64_t*)h->ix_wtab.p;
+        // (the grid's x is a 32-bit count of workgroups: rounds of points)
+        for (uint64_t q0 = 0; q0 < np; q0 += 1u << 20) {
+            const uint32_t nq = (uint32_t)std::min<uint64_t>(np - q0, 1u << 20);
+            hipLaunchKernelGGL(k_index_windows, dim3(nq, FL_IDX_WINDOW / FL_GATHER_SLICE), dim3(256), 0, st, d_out, w + q0, w + np + q0,
+                               ix->d_win, w + 2 * np + q0);
+        }
+    }
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipStreamSynchronize(st));  // (the tables are on this stack; the caller may reuse `out` at once)
+    return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// flate_hip_decompress_batch, then the walk over what it decoded.  The host waits as that call does, then for out_len and
+// status (device memory), for the walkers' records and points, and for the window copies.
+int flate_hip_index_build(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams, int container, int flags,
+                          uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, uint64_t* consumed, int memkind,
+                          uint64_t spacing, flate_hip_index_t* idx) {
+    if (!idx) return FLATE_HIP_E_INVALID_ARG;
+    *idx = nullptr;
+    if (!h || !in_off || !out_off || !out_len || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (!fl_idx_args_ok(container, memkind)) return FLATE_HIP_E_INVALID_ARG;
+    int rc;
+    std::vector<uint64_t> hin(1, 0), hout(1, 0), hlen;
+    std::vector<int32_t> hst;
+    if (n_streams) {
+        if ((rc = flate_hip_decompress_batch(h, in, in_off, n_streams, container, flags, out, out_off, out_len, status, consumed, memkind)))
+            return rc;
+        if ((rc = fetch_offsets(h, in_off, n_streams, memkind, hin)) || (rc = fetch_offsets(h, out_off, n_streams, memkind, hout)) ||
+            (rc = fetch_array(h, out_len, n_streams, memkind, hlen)) || (rc = fetch_array(h, status, n_streams, memkind, hst)))
+            return rc;
+    }
+    flate_hip_index* ix = new flate_hip_index();
+    ix->tab.container = (uint32_t)container;
+    ix->tab.spacing = fl_idx_spacing(spacing);
+    ix->tab.streams.resize(n_streams);
+    for (uint32_t i = 0; i < n_streams; i++) {
+        fl_idx_stream& s = ix->tab.streams[i];
+        s.in_len = hin[i + 1] - hin[i];
+        s.status = hst[i];
+        s.size = hst[i] == 0 ? hlen[i] : 0;
+        s.point0 = s.n_points = 0;
+    }
+    if (n_streams) {
+        // a host caller's batch is still where flate_hip_decompress_batch staged and decoded it
+        const bool host = memkind == FLATE_HIP_MEM_HOST;
+        rc = index_walk(h, ix, host ? (const uint8_t*)h->st_in.p : in, host ? (const uint8_t*)h->st_out.p : out, hin, hout,
+                        host ? hin[0] : 0, host ? hout[0] : 0, container, flags);
+        if (rc) {
+            if (ix->d_win) (void)hipFree(ix->d_win);
+            delete ix;
+            return rc;
+        }
+    }
+    *idx = ix;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_index_destroy(flate_hip_handle h, flate_hip_index_t idx) {
+    if (!h || !idx) return FLATE_HIP_E_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    if (idx->d_win) (void)hipFree(idx->d_win);
+    delete idx;
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_index_stream_info(flate_hip_handle h, flate_hip_index_t idx, uint32_t stream, uint64_t* size, int32_t* status,
+                                uint64_t* n_points) {
+    if (!h || !idx || stream >= idx->tab.streams.size()) return FLATE_HIP_E_INVALID_ARG;
+    const fl_idx_stream& s = idx->tab.streams[stream];
+    if (size) *size = s.size;
+    if (status) *status = s.status;
+    if (n_points) *n_points = s.n_points;
+    return FLATE_HIP_OK;
+}
+
+int64_t flate_hip_index_points(flate_hip_handle h, flate_hip_index_t idx, uint32_t stream, uint64_t* in_bit, uint64_t* out_pos,
+                               uint64_t cap) {
+    if (!h || !idx || stream >= idx->tab.streams.size()) return FLATE_HIP_E_INVALID_ARG;
+    const fl_idx_stream& s = idx->tab.streams[stream];
+    for (uint64_t k = 0; k < s.n_points && k < cap; k++) {
+        if (in_bit) in_bit[k] = idx->tab.points[s.point0 + k].in_bit;
+        if (out_pos) out_pos[k] = idx->tab.points[s.point0 + k].out_pos;
+    }
+    return (int64_t)s.n_points;
+}
+
+int flate_hip_index_export_size(flate_hip_handle h, flate_hip_index_t idx, uint64_t* bytes) {
+    if (!h || !idx || !bytes) return FLATE_HIP_E_INVALID_ARG;
+    *bytes = fl_idx_blob_bytes(idx->tab);
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_index_export(flate_hip_handle h, flate_hip_index_t idx, uint8_t* blob_host, uint64_t cap) {
+    if (!h || !idx || !blob_host || cap < fl_idx_blob_bytes(idx->tab)) return FLATE_HIP_E_INVALID_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    const uint64_t at = fl_idx_blob_write(idx->tab, blob_host);
+    if (idx->tab.win_bytes) {
+        HIP_OK(h, hipMemcpyAsync(blob_host + at, idx->d_win, idx->tab.win_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+    }
+    return FLATE_HIP_OK;
+}
+
+int flate_hip_index_import(flate_hip_handle h, const uint8_t* blob_host, uint64_t bytes, flate_hip_index_t* idx) {
+    if (!idx) return FLATE_HIP_E_INVALID_ARG;
+    *idx = nullptr;
+    if (!h || !blob_host) return FLATE_HIP_E_INVALID_ARG;
+    flate_hip_index* ix = new flate_hip_index();
+    uint64_t at = 0;
+    if (!fl_idx_blob_parse(blob_host, bytes, ix->tab, &at)) {
+        delete ix;
+        return FLATE_HIP_E_INVALID_ARG;
+    }
+    int rc = hipSetDevice(h->device) != hipSuccess ? FLATE_HIP_E_NO_DEVICE : index_alloc_windows(h, ix);
+    if (!rc && ix->tab.win_bytes) {
+        if (hipMemcpyAsync(ix->d_win, blob_host + at, ix->tab.win_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess) {
+            h->last_error = std::string("index import: ") + hipGetErrorString(hipGetLastError());
+            rc = FLATE_HIP_E_LAUNCH;
+        }
+    }
+    if (rc) {
+        if (ix->d_win) (void)hipFree(ix->d_win);
+        delete ix;
+        return rc;
+    }
+    *idx = ix;
+    return FLATE_HIP_OK;
+}
+
+// The host waits for the offsets and the three range arrays (device memory), plans every range (index_plan.h), and waits
+// once more behind the upload of the job tables; a host caller's results come home packed, slot by slot.
+int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                                uint32_t n_ranges, const uint32_t* range_stream, const uint64_t* range_begin, const uint64_t* range_len,
+                                uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind) {
+    if (!h || !idx || !in_off) return FLATE_HIP_E_INVALID_ARG;
+    if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
+    const fl_idx_tab& t = idx->tab;
+    if (n_streams != t.streams.size()) return FLATE_HIP_E_INVALID_ARG;
+    if (n_ranges && (!range_stream || !range_begin || !range_len || !out_off || !out_len || !status)) return FLATE_HIP_E_INVALID_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
+    hipStream_t st = h->stream;
+    int rc;
+    std::vector<uint64_t> hin(1, 0), hout, hbegin, hlen;
+    std::vector<uint32_t> hstream;
+    if (n_streams && (rc = fetch_offsets(h, in_off, n_streams, memkind, hin))) return rc;
+    for (uint32_t i = 0; i < n_streams; i++)
+        if (hin[i + 1] - hin[i] != t.streams[i].in_len) return FLATE_HIP_E_INVALID_ARG;
+    h->dbg_index_passes = 0;
+    if (n_ranges == 0) return FLATE_HIP_OK;
+    if ((rc = fetch_offsets(h, out_off, n_ranges, memkind, hout)) || (rc = fetch_array(h, range_stream, n_ranges, memkind, hstream)) ||
+        (rc = fetch_array(h, range_begin, n_ranges, memkind, hbegin)) || (rc = fetch_array(h, range_len, n_ranges, memkind, hlen)))
+        return rc;
+    for (uint32_t j = 0; j < n_ranges; j++)
+        if (hstream[j] >= n_streams) return FLATE_HIP_E_INVALID_ARG;
+    const uint64_t in_lo = hin[0], in_hi = hin[n_streams], out_lo = hout[0], out_hi = hout[n_ranges];
+    if ((in_hi > in_lo && !in) || (out_hi > out_lo && !out)) return FLATE_HIP_E_INVALID_ARG;
+
+    // ---- every range: its point, what it skips and delivers, its scratch; the passes
+    std::vector<fl_idx_range> plan(n_ranges);
+    std::vector<uint64_t> slot(n_ranges), pass_first, slot_off;
+    for (uint32_t j = 0; j < n_ranges; j++) {
+        plan[j] = fl_idx_plan_range(t, hstream[j], hbegin[j], hlen[j], hout[j + 1] - hout[j]);
+        slot[j] = plan[j].decode ? fl_idx_slot_bytes(plan[j].skip + plan[j].len) : 0;
+    }
+    const uint64_t scratch = fl_idx_passes(slot.data(), n_ranges, h->knobs.index_pass_bytes, pass_first, slot_off);
+
+    const uint8_t* d_in = in;
+    uint8_t* d_out = out;
+    uint64_t* d_outlen = out_len;
+    int32_t* d_status = status;
+    uint64_t in_shift = 0, out_shift = 0;
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16)) || (rc = ensure(h, h->st_out, (out_hi - out_lo) + 16)) ||
+            (rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_ranges)) || (rc = ensure(h, h->st_status, sizeof(int32_t) * n_ranges)))
+            return rc;
+        // Of the input only what the decodes can consume is staged, each byte at its own place: from a range's point to
+        // the first point at or behind its end.  (The bit reader stages and looks ahead beyond that; what it finds there
+        // is never consumed.)
+        std::vector<uint64_t> iv;
+        for (uint32_t j = 0; j < n_ranges; j++)
+            if (plan[j].decode) {
+                iv.push_back(hin[hstream[j]] + plan[j].in_lo);
+                iv.push_back(hin[hstream[j]] + plan[j].in_hi);
+            }
+        fl_idx_merge_intervals(iv, 65536);
+        for (size_t k = 0; k + 1 < iv.size(); k += 2)
+            HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (iv[k] - in_lo), in + iv[k], iv[k + 1] - iv[k], hipMemcpyHostToDevice, st));
+        d_in = (const uint8_t*)h->st_in.p;
+        d_out = (uint8_t*)h->st_out.p;
+        d_outlen = (uint64_t*)h->st_outlen.p;
+        d_status = (int32_t*)h->st_status.p;
+        in_shift = in_lo;
+        out_shift = out_lo;
+    }
+    std::vector<fl_range_job> jobs(n_ranges);
+    std::vector<uint64_t> rtab(2 * (size_t)n_ranges);  // the pack kernel's: source in the scratch | destination
+    for (uint32_t j = 0; j < n_ranges; j++) {
+        const fl_idx_range& p = plan[j];
+        fl_range_job jb{};
+        jb.status = p.status;
+        jb.decode = p.decode;
+        if (p.decode) {
+            const fl_idx_point& pt = t.points[p.point];
+            jb.in_off = hin[hstream[j]] - in_shift;
+            jb.in_len = (uint32_t)t.streams[hstream[j]].in_len;
+            jb.in_bit = pt.in_bit;
+            jb.win_off = pt.win_off;
+            jb.win_len = fl_idx_window_len(pt.out_pos);
+            jb.slot_off = slot_off[j];
+            jb.need = p.skip + p.len;
+            jb.len = p.len;
+        }
+        jobs[j] = jb;
+        rtab[j] = slot_off[j] + p.skip;
+        rtab[n_ranges + j] = hout[j] - out_shift;
+    }
+    if ((rc = ensure(h, h->ix_rjobs, sizeof(fl_range_job) * n_ranges)) || (rc = ensure(h, h->ix_rtab, sizeof(uint64_t) * 2 * n_ranges)) ||
+        (rc = ensure(h, h->ix_scratch, scratch + 16)))
+        return rc;
+    HIP_OK(h, hipMemcpyAsync(h->ix_rjobs.p, jobs.data(), sizeof(fl_range_job) * n_ranges, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->ix_rtab.p, rtab.data(), sizeof(uint64_t) * 2 * n_ranges, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));  // (the tables are on the host's stack)
+
+    // ---- the passes, one after the other in the stream: they share the scratch
+    const fl_range_job* dj = (const fl_range_job*)h->ix_rjobs.p;
+    const uint64_t* dsrc = (const uint64_t*)h->ix_rtab.p;
+    const uint64_t* ddst = dsrc + n_ranges;
+    uint8_t* dscr = (uint8_t*)h->ix_scratch.p;
+    for (size_t k = 0; k + 1 < pass_first.size(); k++) {
+        const uint32_t a = (uint32_t)pass_first[k], nr = (uint32_t)(pass_first[k + 1] - pass_first[k]);
+        uint64_t longest = 0;
+        for (uint32_t j = a; j < a + nr; j++) longest = std::max(longest, plan[j].len);
+        // few ranges: each gets the large LDS ring; many: the small one keeps 20 per CU in flight (as decompress_core)
+        const bool large = h->knobs.inflate_ring >= 0 ? h->knobs.inflate_ring >= (int64_t)FL_INF_RING_LARGE : nr <= 4u * 256u;
+        {
+            ProfScope ps(h, K_INFLATE_RANGE);
+            if (large)
+                hipLaunchKernelGGL(k_inflate_range<FL_INF_RING_LARGE>, dim3(nr), dim3(64), 0, st, d_in, dj + a, 0, (const uint8_t*)idx->d_win,
+                                   dscr, d_outlen + a, d_status + a);
+            else
+                hipLaunchKernelGGL(k_inflate_range<FL_INF_RING_SMALL>, dim3(nr), dim3(64), 0, st, d_in, dj + a, 0, (const uint8_t*)idx->d_win,
+                                   dscr, d_outlen + a, d_status + a);
+        }
+        if (longest) {
+            ProfScope ps(h, K_RANGE_PACK);
+            const uint32_t ny = (uint32_t)std::min<uint64_t>(16, (longest + FL_GATHER_SLICE - 1) / FL_GATHER_SLICE);
+            hipLaunchKernelGGL(k_range_pack, dim3(nr, ny), dim3(256), 0, st, (const uint8_t*)dscr, dsrc + a, (const uint64_t*)(d_outlen + a),
+                               d_out, ddst + a);
+        }
+        HIP_OK(h, hipGetLastError());
+        h->dbg_index_passes++;
+    }
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n_ranges, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_ranges, hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+        // the delivered bytes back to back, then slot by slot: nothing else of the caller's buffer is written
+        std::vector<uint64_t> packoff(n_ranges + 1ull, 0);
+        for (uint32_t j = 0; j < n_ranges; j++) packoff[j + 1] = packoff[j] + out_len[j];
+        const uint64_t total = packoff[n_ranges];
+        if (total) {
+            if ((rc = ensure(h, h->st_pack, total + 16)) || (rc = ensure(h, h->st_packoff, sizeof(uint64_t) * (n_ranges + 1ull)))) return rc;
+            HIP_OK(h, hipMemcpyAsync(h->st_packoff.p, packoff.data(), sizeof(uint64_t) * (n_ranges + 1ull), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_gather_copy, gather_grid(n_ranges), dim3(256), 0, st, (const uint8_t*)d_out, ddst, (const uint64_t*)d_outlen,
+                               (uint8_t*)h->st_pack.p, (const uint64_t*)h->st_packoff.p);
+            HIP_OK(h, hipGetLastError());
+            std::vector<uint8_t> packed(total);
+            HIP_OK(h, hipMemcpyAsync(packed.data(), h->st_pack.p, total, hipMemcpyDeviceToHost, st));
+            HIP_OK(h, hipStreamSynchronize(st));
+            for (uint32_t j = 0; j < n_ranges; j++)
+                if (out_len[j]) memcpy(out + hout[j], packed.data() + packoff[j], out_len[j]);
+        }
+    } else if (h->sync) {
+        HIP_OK(h, hipStreamSynchronize(st));
+    }
+    return FLATE_HIP_OK;
+}
+
+// Debug / test seam: the good streams of the last flate_hip_index_build call that were walked span by span / whole by one wave.
+int flate_hip_debug_index_paths(flate_hip_handle h, uint64_t counts[2]) {
+    if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
+    counts[0] = h->dbg_index_spans;
+    counts[1] = h->dbg_index_whole;
+    return FLATE_HIP_OK;
+}
+
+// Debug / test seam: the passes the last flate_hip_decompress_ranges call took.
+int flate_hip_debug_index_passes(flate_hip_handle h, uint64_t* passes) {
+    if (!h || !passes) return FLATE_HIP_E_INVALID_ARG;
+    *passes = h->dbg_index_passes;
     return FLATE_HIP_OK;
 }
 

@@ -118,16 +118,23 @@ __device__ __forceinline__ int fl_sz_dynamic(fl_bitr& r, FL_LDS fl_inflate_ws16*
 // One member from where the reader stands: the container's header (first), the blocks up to the one with BFINAL (SPAN: or
 // up to the first block that starts at or behind stop_bit) and the footer, which is read, not compared.  Returns the
 // status; cnt has the bytes, end_bit / final_seen what a span's record wants.  k_inflate_size counts one member with it,
-// k_member_walk (kernels_members.h) one after the other.
-template <bool SPAN>
+// k_member_walk (kernels_members.h) one after the other.  HOOK is told every block start and the bytes counted in front
+// of it (a span's stop included): the index walker's point emitter (kernels_index.h); the two kernels above tell nobody
+// and compile as they did without it.
+struct fl_sz_no_hook {
+    enum { ON = 0 };
+    __device__ __forceinline__ void block_start(uint64_t, uint64_t) {}
+};
+template <bool SPAN, class HOOK = fl_sz_no_hook>
 __device__ __forceinline__ int fl_sz_member(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, int container, int flags, uint32_t lane,
                                             bool first, uint64_t stop_bit, uint64_t total_bits, fl_sz_count<SPAN>& cnt,
-                                            uint32_t& final_seen, uint64_t& end_bit) {
+                                            uint32_t& final_seen, uint64_t& end_bit, HOOK* hook = nullptr) {
     int rc = first ? (int)fl_uni((uint32_t)fl_inf_header(r, container)) : 0;
     while (rc == 0) {  // inflate.zig:251-280
-        if (SPAN) {
+        if (SPAN || HOOK::ON) {
             end_bit = total_bits - (uint64_t)r.left;  // a block starts here
-            if (end_bit >= stop_bit) break;
+            if (HOOK::ON) hook->block_start(end_bit, cnt.n);
+            if (SPAN && end_bit >= stop_bit) break;
         }
         uint32_t bfinal, btype;
         if ((rc = (int)fl_uni((uint32_t)fl_br_read(r, 1, bfinal)))) break;

@@ -49,7 +49,7 @@ class Engine:
     _KNOBS = ("FLATE_HIP_MAX_PASS_CHUNKS", "FLATE_HIP_HOST_PASS_CHUNKS", "FLATE_HIP_MAX_STREAM_PASS_MIB",
               "FLATE_HIP_INFLATE_SPANS", "FLATE_HIP_SPAN_DEBUG", "FLATE_HIP_SPAN_TWIN", "FLATE_HIP_NO_PIN_MIRROR",
               "FLATE_HIP_NO_RAMP", "FLATE_HIP_INFLATE_PAR", "FLATE_HIP_INFLATE_RING", "FLATE_HIP_RECT", "FLATE_HIP_STREAM_WINDOWS", "FLATE_HIP_SIMPLE_CK_INLINE", "FLATE_HIP_STREAM_GROUP", "FLATE_HIP_SPAN_TWO_RUNS", "FLATE_HIP_MEMSET_INLINE", "FLATE_HIP_ONE_COMPUTE_STREAM",
-              "FLATE_HIP_MEMBER_SCAN", "FLATE_HIP_MEMBER_CANDIDATES")
+              "FLATE_HIP_MEMBER_SCAN", "FLATE_HIP_MEMBER_CANDIDATES", "FLATE_HIP_INDEX_PASS_BYTES")
 
     def _sync_env(self):
         """The library reads its FLATE_HIP_* tuning variables once, when the handle is made.  Tests and probes change them
@@ -191,6 +191,108 @@ class Engine:
                                                   out_off_ptr, out_len_ptr, status_ptr, consumed_ptr, n_members_ptr,
                                                   MEM_DEVICE)
         self._check(rc, "flate_hip_decompress_members")
+
+    # ---- the seek index ----
+    def build_index(self, streams, container=0, flags=0, spacing=None, caps=None):
+        """Decode the streams as decompress_many does and keep a seek index over them (flate_hip_index_build): for every
+        stream the block starts nearest behind each multiple of `spacing` output bytes (default 1 MiB), each with the 32 KiB
+        in front of it.  caps: output capacity per stream (default: the size probe's answer).
+        Returns (Index, list of bytes, list of status codes, list of consumed input bytes); a stream whose status is not 0
+        has no points."""
+        self._sync_env()
+        n = len(streams)
+        blob, in_off = self._host_input(streams)
+        if caps is None:
+            caps = self._measured_caps(streams, container, flags, [max(1 << 16, len(c) * 1100 + 1024) for c in streams]) if n else []
+        caps = np.array([(int(c) + 7) & ~7 for c in caps], dtype=np.uint64)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(caps, out=out_off[1:])
+        out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
+        out_len = np.zeros(max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        consumed = np.zeros(max(n, 1), dtype=np.uint64)
+        ix = C.c_void_p()
+        rc = self._L.flate_hip_index_build(self._h, blob.ctypes.data, in_off.ctypes.data, n, container, flags, out.ctypes.data,
+                                           out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data, consumed.ctypes.data,
+                                           MEM_HOST, int(spacing or 0), C.byref(ix))
+        self._check(rc, "flate_hip_index_build")
+        res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
+        return Index(self, ix, blob, in_off, n), res, [int(s) for s in status[:n]], [int(c) for c in consumed[:n]]
+
+    def index_from_bytes(self, blob, streams):
+        """An Index from what Index.to_bytes() returned and the streams it was built from (flate_hip_index_import): the blob
+        is validated, the streams only by their lengths -- nothing tells bytes that have changed but still decode."""
+        raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+        ix = C.c_void_p()
+        rc = self._L.flate_hip_index_import(self._h, raw.ctypes.data if raw.size else None, raw.size, C.byref(ix))
+        self._check(rc, "flate_hip_index_import")
+        data, in_off = self._host_input(streams)
+        return Index(self, ix, data, in_off, len(streams))
+
+    def index_build_device(self, in_ptr, in_off_ptr, n_streams, container, flags, out_ptr, out_off_ptr, out_len_ptr, status_ptr,
+                           consumed_ptr=None, spacing=0, memkind=MEM_DEVICE):
+        """flate_hip_index_build on raw pointers (device memory unless memkind says otherwise); returns the index handle for
+        index_* / decompress_ranges_device, to be given to index_destroy."""
+        self._sync_env()
+        ix = C.c_void_p()
+        rc = self._L.flate_hip_index_build(self._h, in_ptr, in_off_ptr, n_streams, container, flags, out_ptr, out_off_ptr,
+                                           out_len_ptr, status_ptr, consumed_ptr, memkind, int(spacing), C.byref(ix))
+        self._check(rc, "flate_hip_index_build")
+        return ix
+
+    def index_destroy(self, ix):
+        self._check(self._L.flate_hip_index_destroy(self._h, ix), "flate_hip_index_destroy")
+
+    def index_info(self, ix, stream):
+        """(size, status, number of points) of one stream of an index"""
+        size, st, npts = C.c_uint64(), C.c_int32(), C.c_uint64()
+        rc = self._L.flate_hip_index_stream_info(self._h, ix, stream, C.addressof(size), C.addressof(st), C.addressof(npts))
+        self._check(rc, "flate_hip_index_stream_info")
+        return int(size.value), int(st.value), int(npts.value)
+
+    def index_points(self, ix, stream):
+        """[(in_bit, out_pos)] of one stream of an index"""
+        n = self.index_info(ix, stream)[2]
+        bit, pos = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        got = self._L.flate_hip_index_points(self._h, ix, stream, bit.ctypes.data, pos.ctypes.data, n)
+        if got != n:
+            raise FlateHipError("flate_hip_index_points returned %d, %d points expected" % (got, n))
+        return [(int(b), int(p)) for b, p in zip(bit[:n], pos[:n])]
+
+    def index_export(self, ix):
+        size = C.c_uint64()
+        self._check(self._L.flate_hip_index_export_size(self._h, ix, C.addressof(size)), "flate_hip_index_export_size")
+        blob = np.zeros(int(size.value), dtype=np.uint8)
+        self._check(self._L.flate_hip_index_export(self._h, ix, blob.ctypes.data, blob.size), "flate_hip_index_export")
+        return blob.tobytes()
+
+    def index_import(self, blob):
+        """the index handle of a blob; raises FlateHipError (code -2) for anything index_export did not write"""
+        raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+        ix = C.c_void_p()
+        rc = self._L.flate_hip_index_import(self._h, raw.ctypes.data if raw.size else None, raw.size, C.byref(ix))
+        self._check(rc, "flate_hip_index_import")
+        return ix
+
+    def decompress_ranges_device(self, ix, in_ptr, in_off_ptr, n_streams, n_ranges, range_stream_ptr, range_begin_ptr,
+                                 range_len_ptr, out_ptr, out_off_ptr, out_len_ptr, status_ptr, memkind=MEM_DEVICE):
+        """flate_hip_decompress_ranges on raw pointers; returns the call's return code (0, or an argument error)"""
+        self._sync_env()
+        return self._L.flate_hip_decompress_ranges(self._h, ix, in_ptr, in_off_ptr, n_streams, n_ranges, range_stream_ptr,
+                                                   range_begin_ptr, range_len_ptr, out_ptr, out_off_ptr, out_len_ptr, status_ptr,
+                                                   memkind)
+
+    def index_paths(self):
+        """(good streams of the last index build walked span by span, walked whole by one wave) (flate_hip_debug_index_paths)"""
+        v = np.zeros(2, dtype=np.uint64)
+        self._check(self._L.flate_hip_debug_index_paths(self._h, v.ctypes.data), "flate_hip_debug_index_paths")
+        return int(v[0]), int(v[1])
+
+    def index_passes(self):
+        """passes the last decompress_ranges call took (flate_hip_debug_index_passes)"""
+        v = C.c_uint64()
+        self._check(self._L.flate_hip_debug_index_passes(self._h, C.addressof(v)), "flate_hip_debug_index_passes")
+        return int(v.value)
 
     def member_paths(self):
         """How the last decompress_members call found its members: (streams by the scan for candidates, streams walked,
@@ -713,6 +815,63 @@ class Deflater:
         if getattr(self, "_d", None) and self._d.value and self._eng._h.value:
             self._eng._L.flate_hip_deflater_destroy(self._eng._h, self._d)
         self._d = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Index:
+    """A seek index over a batch of streams (Engine.build_index / Engine.index_from_bytes) together with the streams' bytes,
+    which every read needs.  The bytes stay in host memory; a read stages only the part of them its ranges can consume, from
+    a range's point to the first point behind its end."""
+
+    def __init__(self, engine, handle, blob, in_off, n):
+        self._e, self._ix, self._blob, self._in_off, self.n = engine, handle, blob, in_off, n
+
+    def info(self, stream=0):
+        """(size, status, number of points) of a stream"""
+        return self._e.index_info(self._ix, stream)
+
+    def points(self, stream=0):
+        """[(in_bit, out_pos)] of a stream"""
+        return self._e.index_points(self._ix, stream)
+
+    def read_ranges(self, ranges):
+        """ranges: [(stream, begin, length)] -> (list of bytes, list of status codes); a range is clipped to its stream's
+        size (flate_hip_decompress_ranges)."""
+        m = len(ranges)
+        if m == 0:
+            return [], []
+        sizes = {}
+        for s, _, _ in ranges:
+            if s not in sizes:
+                sizes[s] = self.info(s)[0]
+        rs = np.array([r[0] for r in ranges], dtype=np.uint32)
+        rb = np.array([min(int(r[1]), (1 << 64) - 1) for r in ranges], dtype=np.uint64)
+        rl = np.array([min(int(r[2]), (1 << 64) - 1) for r in ranges], dtype=np.uint64)
+        caps = np.array([max(0, min(int(r[2]), sizes[r[0]] - min(int(r[1]), sizes[r[0]]))) for r in ranges], dtype=np.uint64)
+        out_off = np.zeros(m + 1, dtype=np.uint64)
+        np.cumsum(caps, out=out_off[1:])
+        out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
+        out_len = np.zeros(m, dtype=np.uint64)
+        status = np.zeros(m, dtype=np.int32)
+        rc = self._e.decompress_ranges_device(self._ix, self._blob.ctypes.data, self._in_off.ctypes.data, self.n, m, rs.ctypes.data,
+                                              rb.ctypes.data, rl.ctypes.data, out.ctypes.data, out_off.ctypes.data,
+                                              out_len.ctypes.data, status.ctypes.data, MEM_HOST)
+        self._e._check(rc, "flate_hip_decompress_ranges")
+        return ([out[int(out_off[j]): int(out_off[j]) + int(out_len[j])].tobytes() for j in range(m)], [int(s) for s in status])
+
+    def to_bytes(self):
+        """the index as one self-contained blob (flate_hip_index_export; the streams' bytes are not in it)"""
+        return self._e.index_export(self._ix)
+
+    def close(self):
+        if self._ix is not None and getattr(self._e, "_h", None) and self._e._h.value:
+            self._e.index_destroy(self._ix)
+        self._ix = None
 
     def __del__(self):
         try:

@@ -10,5 +10,7 @@ decompress = _m.decompress
 decompressor = _m.decompressor
 Decompressor = _m.Decompressor
 decompress_members = _m.decompress_members
+build_index = _m.build_index
+index_from_bytes = _m.index_from_bytes
 huffman = _m.huffman
 store = _m.store

@@ -162,6 +162,50 @@ class Engine {
             return members;
         }
     }
+    // decode `in` into `out` and keep a seek index over it (flate_hip_index_build; spacing 0 = 1 MiB); the caller hands
+    // the index to read_range with the same bytes and to index_destroy when done
+    flate_hip_index_t build_index(const uint8_t* in, size_t n, int container, uint64_t spacing, std::vector<uint8_t>& out) {
+        size_t cap = n * 8 + (1 << 16);
+        for (;;) {
+            const uint64_t in_off[2] = {0, n};
+            const uint64_t out_off[2] = {0, cap};
+            out.assign(cap + 8, 0);
+            uint64_t out_len = 0;
+            int32_t status = 0;
+            const uint8_t dummy = 0;
+            flate_hip_index_t ix = nullptr;
+            const int rc = flate_hip_index_build(h_, n ? in : &dummy, in_off, 1, container, 0, out.data(), out_off, &out_len,
+                                                 &status, nullptr, FLATE_HIP_MEM_HOST, spacing, &ix);
+            if (rc != FLATE_HIP_OK) throw Error(rc, std::string("flate_hip_index_build: ") + flate_hip_last_error(h_));
+            if (status) flate_hip_index_destroy(h_, ix);
+            if (status == FLATE_HIP_ST_OUTPUT_TOO_SMALL && cap < (size_t(1) << 36)) {
+                cap *= 8;
+                continue;
+            }
+            if (status) throw Error(status);
+            out.resize(out_len);
+            return ix;
+        }
+    }
+    // bytes [begin, begin + len) of what `in` inflates to, clipped to its size (flate_hip_decompress_ranges)
+    std::vector<uint8_t> read_range(flate_hip_index_t ix, const uint8_t* in, size_t n, uint64_t begin, uint64_t len) {
+        uint64_t size = 0;
+        if (flate_hip_index_stream_info(h_, ix, 0, &size, nullptr, nullptr) != FLATE_HIP_OK) throw Error(FLATE_HIP_E_INVALID_ARG, "not an index");
+        const uint64_t want = begin >= size ? 0 : (len < size - begin ? len : size - begin);
+        std::vector<uint8_t> out(want + 8);
+        const uint64_t in_off[2] = {0, n}, out_off[2] = {0, want};
+        const uint32_t stream = 0;
+        uint64_t out_len = 0;
+        int32_t status = 0;
+        const uint8_t dummy = 0;
+        const int rc = flate_hip_decompress_ranges(h_, ix, n ? in : &dummy, in_off, 1, 1, &stream, &begin, &len, out.data(), out_off,
+                                                   &out_len, &status, FLATE_HIP_MEM_HOST);
+        if (rc != FLATE_HIP_OK) throw Error(rc, std::string("flate_hip_decompress_ranges: ") + flate_hip_last_error(h_));
+        if (status) throw Error(status);
+        out.resize(out_len);
+        return out;
+    }
+    void index_destroy(flate_hip_index_t ix) { flate_hip_index_destroy(h_, ix); }
 
    private:
     flate_hip_handle h_ = nullptr;

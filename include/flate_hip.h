@@ -390,6 +390,87 @@ int flate_hip_decompress_members(flate_hip_handle h, const uint8_t* in, const ui
                                  int32_t* status, uint64_t* consumed, uint32_t* n_members, int memkind);
 
 /*
+ * Random access: a seek index over a batch of streams, and byte ranges of their output decoded from it.
+ *
+ * A POINT of a stream is a block start with what a decoder needs to begin there: in_bit, the position of the block's
+ * BFINAL bit counted from the stream's first byte (container header included); out_pos, the bytes produced before the
+ * block; and a window, the min(out_pos, 32768) output bytes in front of out_pos.  Which block starts are points is a
+ * rule of the stream and `spacing` (S >= 1; 0 means 1 MiB) alone: the first block is point 0, and block k >= 1 is a point
+ * iff the block before it holds a grid line g * S in (pos[k-1], pos[k]].  So out_pos ascends strictly, a stream of N bytes
+ * has at most 1 + N / S points, and the end of the last block is no point.  Only the first member of a stream is
+ * indexed, as flate_hip_decompress_batch decodes only that.
+ *
+ * flate_hip_index_build: the first twelve arguments are those of flate_hip_decompress_batch, and out, out_len, status and
+ * consumed get exactly what that call writes for them -- it is that call which runs, spans and all.  Then the block
+ * starts of every stream whose status is 0 are walked (the size probe's loop: nothing is decoded a second time) and the
+ * points' windows are copied out of the decoded bytes into device memory the index owns: 32 KiB a point.  A stream whose
+ * status is not 0 (a wrong footer and FLATE_HIP_ST_OUTPUT_TOO_SMALL included) has no points and size 0.  The index
+ * remembers container, spacing, n_streams and per stream in_len, size and status.  Short streams are walked by a wave
+ * each.  Long streams are cut as flate_hip_decompressed_sizes cuts them (same rule, same FLATE_HIP_INFLATE_SPANS) and
+ * walked a wave per span, each span knowing its output base once the spans' chain is followed; the decode path's span
+ * inflater does not run a second time.  A stream whose chain does not close is walked whole by one wave: always
+ * correct, only slow.  flate_hip_debug_index_paths counts the good streams of the last build that went either way.
+ * The call WAITS ON THE HOST as flate_hip_decompress_batch does, then for out_len and status, for the block starts
+ * found and the span records (long streams), for the walkers' points, and for the window copies; a host caller's batch
+ * is read where that call staged it.  The workspace holds 16 bytes per possible point
+ * (1 + out_len / S per stream) besides the decode's.  n_streams == 0 gives an empty index; argument errors as for
+ * decompress, and *idx is NULL whenever the return value is not FLATE_HIP_OK.  An error behind the decode -- no memory
+ * for the walk or the windows, a failed HIP call, or FLATE_HIP_E_LAUNCH with "disagrees with its decode" in
+ * flate_hip_last_error when a walk does not arrive at the size the decode produced (not seen; it would be a fault of the
+ * library) -- leaves out, out_len, status and consumed as flate_hip_decompress_batch wrote them, valid, and no index.
+ *
+ * flate_hip_index_stream_info / flate_hip_index_points: what the index holds for one stream; the arrays are host memory,
+ * at most cap entries are written, the return value is the number of points (negative: an error code).
+ *
+ * flate_hip_index_export / flate_hip_index_import: the index as one self-contained little-endian blob in host memory
+ * (layout: INTEGRATION.md), and back, on any handle.  import believes nothing: counts, offsets, order and window lengths
+ * are checked against `bytes`, and anything else than a blob export wrote gives FLATE_HIP_E_INVALID_ARG.
+ *
+ * flate_hip_decompress_ranges: range j asks for bytes [range_begin[j], range_begin[j] + range_len[j]) of the output of
+ * stream range_stream[j], clipped to the stream's size: L' = min(len, size - begin), 0 when begin >= size.  Its slot is
+ * out[out_off[j] .. out_off[j+1]) (n_ranges + 1 offsets).  n_streams and every in_len must be those of the index
+ * (else FLATE_HIP_E_INVALID_ARG), and `in` must hold the bytes the index was built from.
+ *   out_len[j] = L', status[j] = 0    the bytes are at the start of the slot
+ *   the stream's build status, 0      the stream failed in the build
+ *   FLATE_HIP_ST_OUTPUT_TOO_SMALL, 0  the slot is smaller than L'; nothing is written
+ *   a decoder status, 0               the bytes no longer decode.  THERE IS NO CHECKSUM TO COMPARE: input that differs
+ *                                     from what the index was built from and still decodes gives wrong bytes silently.
+ * No byte outside the first out_len[j] bytes of a slot is written.  Each range is decoded by one wave from the last point
+ * with out_pos <= begin, with the point's window as history, into scratch of the handle (skip + L' + 258 bytes, skip
+ * being begin - out_pos: below S plus the length of the block that holds the grid line, which nothing bounds), and the
+ * requested bytes are copied to the slot.  A call runs in passes of at most FLATE_HIP_INDEX_PASS_BYTES of scratch
+ * (256 MiB by default; a range that needs more is a pass alone); flate_hip_debug_workspace_bytes counts the scratch and
+ * flate_hip_debug_index_passes tells the passes of the last call.  All arrays are where memkind says; the offsets and
+ * the three range arrays are read back once, and the job tables are uploaded behind a wait: the call cannot be captured
+ * in a graph.  Of a host caller's input only the bytes the decodes can consume are staged (from a range's point to the
+ * first point at or behind its end; a stream without a range costs nothing), and the results come home packed.
+ * range_stream[j] >= n_streams gives FLATE_HIP_E_INVALID_ARG; n_ranges == 0 returns FLATE_HIP_OK.
+ *
+ * Not covered: members behind the first of a concatenated stream (split it with flate_hip_decompress_members first);
+ * building an index without decoding into caller memory; compressed windows; an index for the resumable inflater or for
+ * streams with preset dictionaries; the sharded entry points and planned calls; the span path reading an index it is
+ * handed.
+ */
+typedef struct flate_hip_index* flate_hip_index_t;
+int flate_hip_index_build(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams, int container,
+                          int flags, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status,
+                          uint64_t* consumed, int memkind, uint64_t spacing, flate_hip_index_t* idx);
+int flate_hip_index_destroy(flate_hip_handle h, flate_hip_index_t idx);
+int flate_hip_index_stream_info(flate_hip_handle h, flate_hip_index_t idx, uint32_t stream, uint64_t* size, int32_t* status,
+                                uint64_t* n_points);
+int64_t flate_hip_index_points(flate_hip_handle h, flate_hip_index_t idx, uint32_t stream, uint64_t* in_bit, uint64_t* out_pos,
+                               uint64_t cap);
+int flate_hip_index_export_size(flate_hip_handle h, flate_hip_index_t idx, uint64_t* bytes);
+int flate_hip_index_export(flate_hip_handle h, flate_hip_index_t idx, uint8_t* blob_host, uint64_t cap);
+int flate_hip_index_import(flate_hip_handle h, const uint8_t* blob_host, uint64_t bytes, flate_hip_index_t* idx);
+int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const uint8_t* in, const uint64_t* in_off,
+                                uint32_t n_streams, uint32_t n_ranges, const uint32_t* range_stream,
+                                const uint64_t* range_begin, const uint64_t* range_len, uint8_t* out, const uint64_t* out_off,
+                                uint64_t* out_len, int32_t* status, int memkind);
+int flate_hip_debug_index_passes(flate_hip_handle h, uint64_t* passes);
+int flate_hip_debug_index_paths(flate_hip_handle h, uint64_t counts[2]);
+
+/*
  * Pack the n_chunks produced streams back to back (device memory only): copies
  * out[out_off[i] .. out_off[i] + out_len[i]) to dst[dst_off[i] ..) with
  * dst_off[i] = sum of out_len[k] for k < i; dst_off has n_chunks + 1 entries (the last
