@@ -22,6 +22,7 @@
 #include "kernels_common.h"
 #include "dict_compress_plan.h"
 #include "index_plan.h"
+#include "inflate_plan.h"
 #include "join_plan.h"
 #include "kernels_deflater.h"
 #include "kernels_dict.h"
@@ -763,39 +764,159 @@ int compress_stream_pass(flate_hip_ctx* h, const uint8_t* d_in, const fl_params&
 // k_gather_copy: about 4096 workgroups whatever the number of streams (one long stream is cut into slices)
 dim3 gather_grid(uint32_t n) { return dim3(n, std::max(1u, std::min(1024u, 4096u / std::max(n, 1u)))); }
 
-// Host-buffer calls: bring back only what was produced.  The slots are sized for the worst case (an
-// inflate caller may reserve 1000x the input); when the produced bytes are a small part of the slot
-// range they are packed on the device first (k_scan_lens + k_gather_copy), cross PCIe once, and are put
-// into their slots by the host; otherwise the range up to the last produced byte is copied as it is:
-// bytes of a slot beyond out_len[i] are then whatever the staging buffer held there (the callers clear it:
-// zeros), in the packed case they are not touched.
-int copy_out_host(flate_hip_ctx* h, const uint8_t* d_out, const uint64_t* d_outlen, uint32_t n,
-                  const std::vector<uint64_t>& hout, uint64_t out_shift, uint8_t* out, const uint64_t* out_len) {
-    hipStream_t st = h->stream;
-    const uint64_t out_lo = hout[0], out_hi = hout[n];
-    if (out_hi <= out_lo) return FLATE_HIP_OK;
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) total += out_len[i];
-    if (total == 0) return FLATE_HIP_OK;
-    if (total * 2 >= out_hi - out_lo) {
-        // dense: the range from the first slot to the end of the last produced byte
-        uint64_t end = out_lo;
-        for (uint32_t i = 0; i < n; i++)
-            if (out_len[i]) end = std::max(end, hout[i] + out_len[i]);
-        HIP_OK(h, hipMemcpyAsync(out + out_lo, d_out + (out_lo - out_shift), end - out_lo, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-        return FLATE_HIP_OK;
+// n values of a caller's array to the host (memkind says where they are)
+template <class T>
+int fetch_array(flate_hip_ctx* h, const T* p, uint64_t n, int memkind, std::vector<T>& host) {
+    host.resize(n);
+    if (!n) return FLATE_HIP_OK;
+    if (memkind == FLATE_HIP_MEM_HOST) {
+        memcpy(host.data(), p, sizeof(T) * n);
+    } else {
+        HIP_OK(h, hipMemcpyAsync(host.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_OK(h, hipStreamSynchronize(h->stream));
     }
+    return FLATE_HIP_OK;
+}
+
+// Fetch the n+1 offsets to the host (the block tables are built there); they may not go backwards.
+int fetch_offsets(flate_hip_ctx* h, const uint64_t* off, uint32_t n, int memkind, std::vector<uint64_t>& host) {
+    const int rc = fetch_array(h, off, (uint64_t)n + 1, memkind, host);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; i++)
+        if (host[i + 1] < host[i]) return FLATE_HIP_E_INVALID_ARG;
+    return FLATE_HIP_OK;
+}
+
+// ---- The frame of the inflate entry points (decompress_core, the dict batch, the size probe, members, ranges): what the
+// kernels of a call read and write.  Device memory: the caller's own buffers.  Host memory: staged twins in the handle's
+// st_* buffers, whose offsets start at the caller's first byte (the two shifts); the results go home when the call ends.
+// What the calls decide is inflate_plan.h's.
+struct InflateFrame {
+    flate_hip_ctx* h;
+    bool host;   // memkind == FLATE_HIP_MEM_HOST
+    uint32_t n;  // streams (ranges: ranges)
+    uint64_t in_lo = 0, in_hi = 0, out_lo = 0, out_hi = 0;  // the caller's bytes, as offsets into its buffers (no output buffer: 0, 0)
+    // the views (until stage_frame: the caller's pointers)
+    const uint8_t* d_in = nullptr;
+    uint8_t* d_out = nullptr;
+    uint64_t* d_outlen = nullptr;
+    int32_t* d_status = nullptr;
+    uint64_t* d_consumed = nullptr;
+    uint64_t in_shift = 0, out_shift = 0;  // what the views' offsets are less than the caller's
+
+    InflateFrame(flate_hip_ctx* h_, int memkind, uint32_t n_) : h(h_), host(memkind == FLATE_HIP_MEM_HOST), n(n_) {}
+    InflateFrame& input(const uint8_t* in, uint64_t lo, uint64_t hi) {
+        d_in = in, in_lo = lo, in_hi = hi;
+        return *this;
+    }
+    InflateFrame& output(uint8_t* out, uint64_t lo, uint64_t hi) {
+        d_out = out, out_lo = lo, out_hi = hi;
+        return *this;
+    }
+    InflateFrame& results(uint64_t* out_len, int32_t* status, uint64_t* consumed) {
+        d_outlen = out_len, d_status = status, d_consumed = consumed;
+        return *this;
+    }
+};
+// what a call stages beside in / out_len / status
+enum : uint32_t {
+    FRAME_OUT = 1,            // an output buffer
+    FRAME_CONSUMED = 2,       // consumed ...
+    FRAME_NULL_CONSUMED = 4,  // ... but the kernels see nullptr when the caller passed nullptr (else the staged array)
+};
+
+// host memory: the staging buffers of the call, at least as large as it needs them (nothing is copied yet)
+int reserve_frame(const InflateFrame& f, uint32_t what) {
+    if (!f.host) return FLATE_HIP_OK;
+    flate_hip_ctx* h = f.h;
+    int rc;
+    if ((rc = ensure(h, h->st_in, (f.in_hi - f.in_lo) + 16))) return rc;
+    if ((what & FRAME_OUT) && (rc = ensure(h, h->st_out, (f.out_hi - f.out_lo) + 16))) return rc;
+    if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * f.n))) return rc;
+    if ((rc = ensure(h, h->st_status, sizeof(int32_t) * f.n))) return rc;
+    if ((what & FRAME_CONSUMED) && (rc = ensure(h, h->st_consumed, sizeof(uint64_t) * f.n))) return rc;
+    return FLATE_HIP_OK;
+}
+
+// host memory: the input bytes [iv[0], iv[1]), [iv[2], iv[3]), ... (the caller's offsets) go to their places in st_in --
+// the whole input, the intervals a ranges call can consume, or nothing (the pinned path copies sub-batch by sub-batch) --
+// and the views become the staged twins.
+int stage_frame(InflateFrame& f, uint32_t what, const uint64_t* iv, size_t n_iv) {
+    if (!f.host) return FLATE_HIP_OK;
+    flate_hip_ctx* h = f.h;
+    for (size_t k = 0; k + 1 < n_iv; k += 2)
+        HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (iv[k] - f.in_lo), f.d_in + iv[k], iv[k + 1] - iv[k], hipMemcpyHostToDevice,
+                                 h->stream));
+    f.d_in = (const uint8_t*)h->st_in.p;
+    if (what & FRAME_OUT) f.d_out = (uint8_t*)h->st_out.p;
+    f.d_outlen = (uint64_t*)h->st_outlen.p;
+    f.d_status = (int32_t*)h->st_status.p;
+    if (what & FRAME_CONSUMED) f.d_consumed = (f.d_consumed || !(what & FRAME_NULL_CONSUMED)) ? (uint64_t*)h->st_consumed.p : nullptr;
+    f.in_shift = f.in_lo;
+    f.out_shift = f.out_lo;
+    return FLATE_HIP_OK;
+}
+// ... the whole input
+int stage_frame_whole(InflateFrame& f, uint32_t what) {
+    const uint64_t whole[2] = {f.in_lo, f.in_hi};
+    return stage_frame(f, what, whole, f.in_hi > f.in_lo ? 2 : 0);
+}
+
+// (what goes back to a host caller beyond out_len[i] is zeros, never bytes of an earlier call; the copies of the
+// call before are done: it waited for them)
+int clear_staged_out(const InflateFrame& f) {
+    if (f.host && f.out_hi > f.out_lo) HIP_OK(f.h, hipMemsetAsync(f.h->st_out.p, 0, f.out_hi - f.out_lo, f.h->stream));
+    return FLATE_HIP_OK;
+}
+
+// the call's chunk table to the device; the host waits for it (the table is the caller's to change or drop)
+int upload_chunks(flate_hip_ctx* h, const std::vector<fl_chunk>& chunks) {
+    int rc;
+    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * chunks.size()))) return rc;
+    HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * chunks.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return FLATE_HIP_OK;
+}
+
+// The call ends: a host caller's out_len / status / consumed (where it asked for it) are sent home ...
+int results_home(const InflateFrame& f, uint64_t* out_len, int32_t* status, uint64_t* consumed) {
+    flate_hip_ctx* h = f.h;
+    if (!f.host) return FLATE_HIP_OK;
+    HIP_OK(h, hipMemcpyAsync(out_len, f.d_outlen, sizeof(uint64_t) * f.n, hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(h, hipMemcpyAsync(status, f.d_status, sizeof(int32_t) * f.n, hipMemcpyDeviceToHost, h->stream));
+    if (consumed) HIP_OK(h, hipMemcpyAsync(consumed, f.d_consumed, sizeof(uint64_t) * f.n, hipMemcpyDeviceToHost, h->stream));
+    return FLATE_HIP_OK;
+}
+// ... and the host waits for them; a device caller is waited for when the handle is synchronous
+int wait_for_results(const InflateFrame& f) {
+    if (f.host || f.h->sync) HIP_OK(f.h, hipStreamSynchronize(f.h->stream));
+    return FLATE_HIP_OK;
+}
+
+// The produced bytes of n slots packed on the device (k_gather_copy), across PCIe once, and put into their slots by the
+// host; the caller's bytes beyond out_len[i] are not touched.  hout: the slots' offsets in `out` (the caller's); total: the
+// sum of out_len.  d_slot: the slots' offsets in d_out where the device has them already (ranges: the pack kernel's
+// table) -- the packed offsets are then summed here and uploaded; nullptr: hout less out_shift is uploaded and the packed
+// offsets are summed on the device (k_scan_lens).
+int copy_out_packed(flate_hip_ctx* h, const uint8_t* d_out, const uint64_t* d_slot, const uint64_t* d_outlen, uint32_t n,
+                    const std::vector<uint64_t>& hout, uint64_t out_shift, uint8_t* out, const uint64_t* out_len, uint64_t total) {
+    hipStream_t st = h->stream;
     int rc;
     if ((rc = ensure(h, h->st_pack, total + 16))) return rc;
     if ((rc = ensure(h, h->st_packoff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ensure(h, h->st_slot, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    std::vector<uint64_t> slot(n + 1);
-    for (uint32_t i = 0; i <= n; i++) slot[i] = hout[i] - out_shift;
-    HIP_OK(h, hipMemcpyAsync(h->st_slot.p, slot.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, st, d_outlen, n, (uint64_t*)h->st_packoff.p);
-    hipLaunchKernelGGL(k_gather_copy, gather_grid(n), dim3(256), 0, st, d_out, (const uint64_t*)h->st_slot.p, d_outlen,
-                       (uint8_t*)h->st_pack.p, (const uint64_t*)h->st_packoff.p);
+    std::vector<uint64_t> tab((size_t)n + 1, 0);
+    if (d_slot) {
+        for (uint32_t i = 0; i < n; i++) tab[i + 1] = tab[i] + out_len[i];
+        HIP_OK(h, hipMemcpyAsync(h->st_packoff.p, tab.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+    } else {
+        if ((rc = ensure(h, h->st_slot, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+        for (uint32_t i = 0; i <= n; i++) tab[i] = hout[i] - out_shift;
+        HIP_OK(h, hipMemcpyAsync(h->st_slot.p, tab.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, st, d_outlen, n, (uint64_t*)h->st_packoff.p);
+        d_slot = (const uint64_t*)h->st_slot.p;
+    }
+    hipLaunchKernelGGL(k_gather_copy, gather_grid(n), dim3(256), 0, st, d_out, d_slot, d_outlen, (uint8_t*)h->st_pack.p,
+                       (const uint64_t*)h->st_packoff.p);
     HIP_OK(h, hipGetLastError());
     std::vector<uint8_t> packed(total);
     HIP_OK(h, hipMemcpyAsync(packed.data(), h->st_pack.p, total, hipMemcpyDeviceToHost, st));
@@ -808,25 +929,24 @@ int copy_out_host(flate_hip_ctx* h, const uint8_t* d_out, const uint64_t* d_outl
     return FLATE_HIP_OK;
 }
 
-int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint64_t>& hin, uint32_t n_chunks, int container,
-                    int flags, uint8_t* out, const std::vector<uint64_t>& hout, uint64_t* out_len, int32_t* status,
-                    uint64_t* consumed, int memkind);
-
-// Fetch the n+1 offsets to the host (the block tables are built there).
-int fetch_offsets(flate_hip_ctx* h, const uint64_t* off, uint32_t n, int memkind, std::vector<uint64_t>& host) {
-    host.resize((size_t)n + 1);
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        memcpy(host.data(), off, sizeof(uint64_t) * ((size_t)n + 1));
-    } else {
-        HIP_OK(h, hipMemcpyAsync(host.data(), off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost,
-                                 h->stream));
+// Host-buffer calls: bring back only what was produced (fl_copy_out_plan): packed, or the range up to the last produced
+// byte as it is -- bytes of a slot beyond out_len[i] are then whatever the staging buffer held there (the callers clear it:
+// zeros), in the packed case they are not touched.
+int copy_out_host(flate_hip_ctx* h, const uint8_t* d_out, const uint64_t* d_outlen, uint32_t n,
+                  const std::vector<uint64_t>& hout, uint64_t out_shift, uint8_t* out, const uint64_t* out_len) {
+    const fl_copy_out p = fl_copy_out_plan(hout.data(), out_len, n);
+    if (p.kind == FL_COPY_OUT_PACKED) return copy_out_packed(h, d_out, nullptr, d_outlen, n, hout, out_shift, out, out_len, p.total);
+    if (p.kind == FL_COPY_OUT_DENSE) {
+        const uint64_t out_lo = hout[0];
+        HIP_OK(h, hipMemcpyAsync(out + out_lo, d_out + (out_lo - out_shift), p.end - out_lo, hipMemcpyDeviceToHost, h->stream));
         HIP_OK(h, hipStreamSynchronize(h->stream));
     }
-    for (uint32_t i = 0; i < n; i++)
-        if (host[i + 1] < host[i]) return FLATE_HIP_E_INVALID_ARG;
     return FLATE_HIP_OK;
 }
 
+int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint64_t>& hin, uint32_t n_chunks, int container,
+                    int flags, uint8_t* out, const std::vector<uint64_t>& hout, uint64_t* out_len, int32_t* status,
+                    uint64_t* consumed, int memkind);
 
 // workspace of a chunk-path pass of nc chunks (levels 4..9)
 // (pass_plan.h: the bytes per chunk of every buffer)
@@ -2523,52 +2643,27 @@ int flate_hip_decompress_batch_dict(flate_hip_handle h, const uint8_t* in, const
     std::vector<fl_dict_ent> tab;
     fl_dict_table(hdoff.data(), n_dicts, tab);
 
-    const uint64_t in_lo = hin[0], in_hi = hin[n_chunks], out_lo = hout[0], out_hi = hout[n_chunks];
-    const uint8_t* d_in = in;
+    InflateFrame f(h, memkind, n_chunks);
+    f.input(in, hin[0], hin[n_chunks]).output(out, hout[0], hout[n_chunks]).results(out_len, status, consumed);
+    const uint32_t what = FRAME_OUT | FRAME_CONSUMED;
     const uint8_t* d_dict = dict;
     const uint32_t* d_of = dict_of;
-    uint8_t* d_out = out;
-    uint64_t* d_outlen = out_len;
-    int32_t* d_status = status;
-    uint64_t* d_consumed = consumed;
-    uint64_t in_shift = 0, out_shift = 0;
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16)) || (rc = ensure(h, h->st_out, (out_hi - out_lo) + 16)) ||
-            (rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_chunks)) || (rc = ensure(h, h->st_status, sizeof(int32_t) * n_chunks)) ||
-            (rc = ensure(h, h->st_consumed, sizeof(uint64_t) * n_chunks)) || (rc = ensure(h, h->dc_bytes, (d_hi - d_lo) + 16)) ||
-            (rc = ensure(h, h->dc_of, sizeof(uint32_t) * n_chunks)))
+    if (f.host) {
+        if ((rc = reserve_frame(f, what)) || (rc = ensure(h, h->dc_bytes, (d_hi - d_lo) + 16)) ||
+            (rc = ensure(h, h->dc_of, sizeof(uint32_t) * n_chunks)) || (rc = stage_frame_whole(f, what)))
             return rc;
-        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
         if (d_hi > d_lo) HIP_OK(h, hipMemcpyAsync(h->dc_bytes.p, dict + d_lo, d_hi - d_lo, hipMemcpyHostToDevice, st));
         if (dict_of) HIP_OK(h, hipMemcpyAsync(h->dc_of.p, hof.data(), sizeof(uint32_t) * n_chunks, hipMemcpyHostToDevice, st));
-        if (out_hi > out_lo) HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, out_hi - out_lo, st));  // (as decompress_core)
-        d_in = (const uint8_t*)h->st_in.p;
+        if ((rc = clear_staged_out(f))) return rc;  // (here, before the tables go up)
         d_dict = (const uint8_t*)h->dc_bytes.p;
         d_of = dict_of ? (const uint32_t*)h->dc_of.p : nullptr;
-        d_out = (uint8_t*)h->st_out.p;
-        d_outlen = (uint64_t*)h->st_outlen.p;
-        d_status = (int32_t*)h->st_status.p;
-        d_consumed = (uint64_t*)h->st_consumed.p;
-        in_shift = in_lo;
-        out_shift = out_lo;
         for (fl_dict_ent& e : tab) {
             e.start -= d_lo;
             e.end -= d_lo;
         }
     }
-    std::vector<fl_chunk> chunks(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; i++) {
-        fl_chunk& c = chunks[i];
-        const uint64_t len = hin[i + 1] - hin[i];
-        if (len > 0xfffffff0ull) return FLATE_HIP_E_INVALID_ARG;
-        c.in_off = hin[i] - in_shift;
-        c.out_off = hout[i] - out_shift;
-        c.out_cap = hout[i + 1] - hout[i];
-        c.in_len = (uint32_t)len;
-        c.first_block = 0;
-        c.n_blocks = 0;
-        c.skip = 0;
-    }
+    std::vector<fl_chunk> chunks;
+    if (!fl_inflate_chunks(hin.data(), hout.data(), n_chunks, f.in_shift, f.out_shift, chunks)) return FLATE_HIP_E_INVALID_ARG;
     if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n_chunks)) || (rc = ensure(h, h->dc_tab, sizeof(fl_dict_ent) * (n_dicts + 1))))
         return rc;
     HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
@@ -2578,215 +2673,174 @@ int flate_hip_decompress_batch_dict(flate_hip_handle h, const uint8_t* in, const
     if (h->dbg_par_handed.p) HIP_OK(h, hipMemsetAsync(h->dbg_par_handed.p, 0, sizeof(uint32_t), st));
     fl_dict_ent* d_tab = (fl_dict_ent*)h->dc_tab.p;
     if (n_dicts) hipLaunchKernelGGL(k_dict_adler, dim3(n_dicts), dim3(64), 0, st, d_dict, d_tab, n_dicts);
-    const bool large = h->knobs.inflate_ring >= 0 ? h->knobs.inflate_ring >= (int64_t)FL_INF_RING_LARGE : n_chunks <= 4u * 256u;  // (as decompress_core)
     {
         ProfScope ps(h, K_INFLATE_DICT);
-        if (large)
-            hipLaunchKernelGGL(k_inflate_dict<FL_INF_RING_LARGE>, dim3(n_chunks), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p,
-                               container, flags, h->crc, d_out, d_outlen, d_status, d_consumed, d_dict, (const fl_dict_ent*)d_tab, d_of);
-        else
-            hipLaunchKernelGGL(k_inflate_dict<FL_INF_RING_SMALL>, dim3(n_chunks), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p,
-                               container, flags, h->crc, d_out, d_outlen, d_status, d_consumed, d_dict, (const fl_dict_ent*)d_tab, d_of);
+        const auto k = fl_inflate_ring_large(h->knobs.inflate_ring, n_chunks) ? k_inflate_dict<FL_INF_RING_LARGE> : k_inflate_dict<FL_INF_RING_SMALL>;
+        hipLaunchKernelGGL(k, dim3(n_chunks), dim3(64), 0, st, f.d_in, (const fl_chunk*)h->chunks.p, container, flags, h->crc, f.d_out,
+                           f.d_outlen, f.d_status, f.d_consumed, d_dict, (const fl_dict_ent*)d_tab, d_of);
     }
     HIP_OK(h, hipGetLastError());
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        if (consumed) HIP_OK(h, hipMemcpyAsync(consumed, d_consumed, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-        if ((rc = copy_out_host(h, d_out, d_outlen, n_chunks, hout, out_shift, out, out_len))) return rc;
-    } else if (h->sync) {
-        HIP_OK(h, hipStreamSynchronize(st));
-    }
-    return FLATE_HIP_OK;
+    if ((rc = results_home(f, out_len, status, consumed)) || (rc = wait_for_results(f))) return rc;
+    return f.host ? copy_out_host(h, f.d_out, f.d_outlen, n_chunks, hout, f.out_shift, out, out_len) : FLATE_HIP_OK;
 }
 
 }  // extern "C"
 
 namespace {
 
-// flate_hip_decompress_batch behind its offsets: hin / hout are the n_chunks + 1 offsets on the host, everything else is
-// as the entry point got it.  flate_hip_decompress_members runs it over the members it found (device memory).
+// ---- flate_hip_decompress_batch behind its offsets (decompress_core): what a call decides is inflate_plan.h's, the stages
+// below carry it out over one record per call.
+struct InflateCall {
+    flate_hip_ctx* h;
+    hipStream_t st;
+    const uint8_t* in;  // the caller's buffers and offsets
+    uint8_t* out;
+    const std::vector<uint64_t>& hin;
+    const std::vector<uint64_t>& hout;
+    uint32_t n;
+    int container, flags;
+    InflateFrame f;
+    std::vector<fl_chunk> chunks;
+    bool pin_io = false;  // host memory, pinned: sub-batches with the copies on s_in / s_out (fl_inflate_pin_io)
+    uint32_t sub = 0;     // streams per sub-batch (n: one launch)
+    fl_inflate_par par;
+    bool large = false;   // the LDS ring of k_inflate
+};
+
+int stage_inflate_call(InflateCall& ic) {
+    flate_hip_ctx* h = ic.h;
+    InflateFrame& f = ic.f;
+    const uint32_t what = FRAME_OUT | FRAME_CONSUMED;
+    int rc;
+    if (f.host) {
+        if ((rc = reserve_frame(f, what))) return rc;
+        const bool in_pinned = is_pinned_host(ic.in + f.in_lo), out_pinned = in_pinned && is_pinned_host(ic.out + f.out_lo);
+        ic.pin_io = fl_inflate_pin_io(in_pinned, out_pinned, f.in_hi - f.in_lo, f.out_hi - f.out_lo, ic.n, h->knobs.host_pass_chunks);
+        if (ic.pin_io && ((!h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) ||
+                          (!h->s_out && create_copy_stream(&h->s_out, false) != hipSuccess)))
+            return FLATE_HIP_E_ALLOC;
+        if ((rc = ic.pin_io ? stage_frame(f, what, nullptr, 0) : stage_frame_whole(f, what))) return rc;
+    }
+    if (!fl_inflate_chunks(ic.hin.data(), ic.hout.data(), ic.n, f.in_shift, f.out_shift, ic.chunks)) return FLATE_HIP_E_INVALID_ARG;
+    if ((rc = upload_chunks(h, ic.chunks)) || (rc = clear_staged_out(f))) return rc;
+    h->dbg_span_taken = h->dbg_span_done = h->dbg_par_taken = 0;
+    return FLATE_HIP_OK;
+}
+
+// A few long streams: each by many workgroups at once (spans); what comes out whole is skipped by the kernels behind it.
+int inflate_by_spans(InflateCall& ic) {
+    flate_hip_ctx* h = ic.h;
+    const InflateFrame& f = ic.f;
+    if (ic.pin_io) return FLATE_HIP_OK;
+    const int done = try_span_inflate(h, ic.st, f.d_in, ic.chunks, ic.container, ic.flags, f.d_out, f.d_outlen, f.d_status, f.d_consumed);
+    if (fl_inflate_pool_release(h->sp_pool.cap)) {
+        (void)hipStreamSynchronize(ic.st);
+        (void)hipFree(h->sp_pool.p);
+        h->ws_bytes -= h->sp_pool.cap;
+        h->sp_pool.p = nullptr;
+        h->sp_pool.cap = 0;
+    }
+    if (done < 0) {
+        h->last_error = std::string("inflate by spans: ") + hipGetErrorString(hipGetLastError());
+        return FLATE_HIP_E_LAUNCH;
+    }
+    return done > 0 ? upload_chunks(h, ic.chunks) : FLATE_HIP_OK;
+}
+
+int choose_inflate_paths(InflateCall& ic) {
+    flate_hip_ctx* h = ic.h;
+    int rc;
+    ic.par = fl_inflate_par_plan(ic.chunks.data(), ic.n, h->knobs.inflate_par, ic.flags);
+    if (ic.par.use) {
+        if ((rc = ensure(h, h->dbg_par_handed, sizeof(uint32_t)))) return rc;
+        HIP_OK(h, hipMemsetAsync(h->dbg_par_handed.p, 0, sizeof(uint32_t), ic.st));
+        h->dbg_par_taken += ic.par.taken;
+    }
+    ic.large = fl_inflate_ring_large(h->knobs.inflate_ring, ic.n);
+    if (ic.pin_io) HIP_OK(h, hipStreamSynchronize(h->s_out));  // (nothing of an earlier call may still read st_out)
+    ic.sub = ic.pin_io ? fl_inflate_sub_batch(ic.n, h->knobs.host_pass_chunks) : ic.n;
+    return FLATE_HIP_OK;
+}
+
+// Pinned: every sub-batch's input copy is submitted BEFORE any output copy: an output copy waits for its sub-batch's kernels,
+// and an input copy submitted behind it can land in the same in-order DMA queue and wait with it -- then nothing
+// overlaps (round 5, profiles/r05_host_path.txt: what happened to the compress path's rectangle copy).
+int submit_input_copies(InflateCall& ic) {
+    flate_hip_ctx* h = ic.h;
+    int rc;
+    size_t k = 0;
+    for (uint32_t c0 = 0; ic.pin_io && c0 < ic.n; c0 += ic.sub, k++) {
+        const uint32_t nc = std::min(ic.sub, ic.n - c0);
+        hipEvent_t ev_in;
+        if ((rc = xfer_event(h, 2 * k, &ev_in))) return rc;
+        const uint64_t a = ic.hin[c0], b = ic.hin[c0 + nc];
+        if (b > a) HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (a - ic.f.in_lo), ic.in + a, b - a, hipMemcpyHostToDevice, h->s_in));
+        HIP_OK(h, hipEventRecord(ev_in, h->s_in));
+    }
+    return FLATE_HIP_OK;
+}
+
+// nc streams from c0 on: k_inflate_par where the call takes it, then k_inflate over what that left
+void launch_inflate(InflateCall& ic, uint32_t c0, uint32_t nc) {
+    flate_hip_ctx* h = ic.h;
+    const InflateFrame& f = ic.f;
+    const fl_chunk* dch = (const fl_chunk*)h->chunks.p + c0;
+    uint64_t* d_consumed = f.d_consumed ? f.d_consumed + c0 : nullptr;
+    const int32_t* redo_only = nullptr;
+    if (ic.par.use) {
+        ProfScope ps(h, K_INFLATE_PAR);
+        hipLaunchKernelGGL(k_inflate_par, dim3(nc), dim3(FP_THREADS), 0, ic.st, f.d_in, dch, ic.container, ic.flags, ic.par.min_bytes,
+                           h->crc, f.d_out, f.d_outlen + c0, f.d_status + c0, d_consumed);
+        redo_only = f.d_status + c0;
+    }
+    ProfScope ps(h, K_INFLATE);
+    const auto k = ic.large ? k_inflate<FL_INF_RING_LARGE> : k_inflate<FL_INF_RING_SMALL>;
+    hipLaunchKernelGGL(k, dim3(nc), dim3(64), 0, ic.st, f.d_in, dch, ic.container, ic.flags, h->crc, f.d_out, f.d_outlen + c0,
+                       f.d_status + c0, d_consumed, redo_only, (uint32_t*)h->dbg_par_handed.p);
+}
+
+int run_sub_batches(InflateCall& ic) {
+    flate_hip_ctx* h = ic.h;
+    int rc;
+    size_t k = 0;
+    for (uint32_t c0 = 0; c0 < ic.n; c0 += ic.sub, k++) {
+        const uint32_t nc = std::min(ic.sub, ic.n - c0);
+        if (ic.pin_io) {  // this sub-batch's input: it came in while the sub-batches before it were decoded
+            hipEvent_t ev_in;
+            if ((rc = xfer_event(h, 2 * k, &ev_in))) return rc;
+            HIP_OK(h, hipStreamWaitEvent(ic.st, ev_in, 0));
+        }
+        launch_inflate(ic, c0, nc);
+        HIP_OK(h, hipGetLastError());
+        if (ic.pin_io) {  // this sub-batch's output slots go home while the next sub-batch is decoded
+            hipEvent_t ev_out;
+            if ((rc = xfer_event(h, 2 * k + 1, &ev_out))) return rc;
+            HIP_OK(h, hipEventRecord(ev_out, ic.st));
+            HIP_OK(h, hipStreamWaitEvent(h->s_out, ev_out, 0));
+            const uint64_t a = ic.hout[c0], b = ic.hout[c0 + nc];
+            if (b > a) HIP_OK(h, hipMemcpyAsync(ic.out + a, ic.f.d_out + (a - ic.f.out_shift), b - a, hipMemcpyDeviceToHost, h->s_out));
+        }
+    }
+    return FLATE_HIP_OK;
+}
+
+// hin / hout are the n_chunks + 1 offsets on the host, everything else is as the entry point got it.
+// flate_hip_decompress_members runs it over the members it found (device memory).
 int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint64_t>& hin, uint32_t n_chunks, int container,
                     int flags, uint8_t* out, const std::vector<uint64_t>& hout, uint64_t* out_len, int32_t* status,
                     uint64_t* consumed, int memkind) {
-    hipStream_t st = h->stream;
+    InflateFrame f(h, memkind, n_chunks);
+    f.input(in, hin[0], hin[n_chunks]).output(out, hout[0], hout[n_chunks]).results(out_len, status, consumed);
+    InflateCall ic{h, h->stream, in, out, hin, hout, n_chunks, container, flags, f};
     int rc;
-    const uint64_t in_lo = hin[0], in_hi = hin[n_chunks];
-    const uint64_t out_lo = hout[0], out_hi = hout[n_chunks];
-
-    const uint8_t* d_in = in;
-    uint8_t* d_out = out;
-    uint64_t* d_outlen = out_len;
-    int32_t* d_status = status;
-    uint64_t* d_consumed = consumed;
-    uint64_t in_shift = 0, out_shift = 0;
-    bool pin_io = false;
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16))) return rc;
-        if ((rc = ensure(h, h->st_out, (out_hi - out_lo) + 16))) return rc;
-        if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_chunks))) return rc;
-        if ((rc = ensure(h, h->st_status, sizeof(int32_t) * n_chunks))) return rc;
-        if ((rc = ensure(h, h->st_consumed, sizeof(uint64_t) * n_chunks))) return rc;
-        // Pinned host buffers whose output slots are not much larger than what goes in (a caller who knows
-        // the sizes): sub-batches with the copies on their own streams, as in compress_impl.  Otherwise one
-        // staged copy in, and only the produced bytes come back (copy_out_host).
-        pin_io = is_pinned_host(in + in_lo) && is_pinned_host(out + out_lo) &&
-                 (out_hi - out_lo) <= 8 * (in_hi - in_lo) + (1ull << 20) && n_chunks > 4 * h->knobs.host_pass_chunks;
-        if (pin_io && ((!h->s_in && create_copy_stream(&h->s_in, true) != hipSuccess) ||
-                       (!h->s_out && create_copy_stream(&h->s_out, false) != hipSuccess)))
-            return FLATE_HIP_E_ALLOC;
-        if (in_hi > in_lo && !pin_io)
-            HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-        d_in = (const uint8_t*)h->st_in.p;
-        d_out = (uint8_t*)h->st_out.p;
-        d_outlen = (uint64_t*)h->st_outlen.p;
-        d_status = (int32_t*)h->st_status.p;
-        d_consumed = (uint64_t*)h->st_consumed.p;
-        in_shift = in_lo;
-        out_shift = out_lo;
-    }
-    std::vector<fl_chunk> chunks(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; i++) {
-        fl_chunk& c = chunks[i];
-        const uint64_t len = hin[i + 1] - hin[i];
-        if (len > 0xfffffff0ull) return FLATE_HIP_E_INVALID_ARG;
-        c.in_off = hin[i] - in_shift;
-        c.out_off = hout[i] - out_shift;
-        c.out_cap = hout[i + 1] - hout[i];
-        c.in_len = (uint32_t)len;
-        c.first_block = 0;
-        c.n_blocks = 0;
-        c.skip = 0;
-    }
-    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n_chunks))) return rc;
-    HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
-    HIP_OK(h, hipStreamSynchronize(st));
-    // (what goes back to the caller beyond out_len[i] is zeros, never bytes of an earlier call; the copies of the
-    // call before are done: it waited for them)
-    if (memkind == FLATE_HIP_MEM_HOST && out_hi > out_lo) HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, out_hi - out_lo, st));
-    h->dbg_span_taken = h->dbg_span_done = h->dbg_par_taken = 0;
-    // A few long streams: each by many workgroups at once (spans); what comes out whole is skipped below.
-    if (!pin_io) {
-        const int done = try_span_inflate(h, st, d_in, chunks, container, flags, d_out, d_outlen, d_status, d_consumed);
-        // (the pool holds a second copy of the decoded output: a large one does not stay with the handle)
-        if (h->sp_pool.cap > (2ull << 30)) {
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(h->sp_pool.p);
-            h->ws_bytes -= h->sp_pool.cap;
-            h->sp_pool.p = nullptr;
-            h->sp_pool.cap = 0;
-        }
-        if (done < 0) {
-            h->last_error = std::string("inflate by spans: ") + hipGetErrorString(hipGetLastError());
-            return FLATE_HIP_E_LAUNCH;
-        }
-        if (done > 0) {
-            HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
-            HIP_OK(h, hipStreamSynchronize(st));
-        }
-    }
-    // Long streams of a batch that has few of them: a workgroup per stream (kernels_inflate_par.h).  It marks
-    // what it does not finish (short streams, anything irregular) FL_PAR_REDO, and k_inflate takes those.
-    bool use_par = false;
-    uint32_t par_min_bytes = 0;
-    {
-        const uint32_t min_bytes = h->knobs.inflate_par >= 0 ? (uint32_t)h->knobs.inflate_par : 32768u;  // FLATE_HIP_INFLATE_PAR -- 0: never; else the minimum stream size in bytes
-        uint32_t n_big = 0;
-        for (uint32_t i = 0; i < n_chunks; i++)  // long input, or an output slot that says the output is long
-            n_big += (chunks[i].in_len >= min_bytes || chunks[i].out_cap >= 16ull * min_bytes) ? 1u : 0u;
-        use_par = min_bytes && n_big && n_big <= 2048u && !(flags & 1);
-        par_min_bytes = min_bytes;
-    }
-    if (use_par) {
-        if ((rc = ensure(h, h->dbg_par_handed, sizeof(uint32_t)))) return rc;
-        HIP_OK(h, hipMemsetAsync(h->dbg_par_handed.p, 0, sizeof(uint32_t), st));
-        for (uint32_t i = 0; i < n_chunks; i++) h->dbg_par_taken += chunks[i].skip ? 0u : 1u;
-    }
-    // few streams: the latency of one stream decides, give each the large LDS ring (3 per CU);
-    // many streams: the small ring keeps 20 per CU in flight
-    const bool large = h->knobs.inflate_ring >= 0 ? h->knobs.inflate_ring >= (int64_t)FL_INF_RING_LARGE : n_chunks <= 4u * 256u;  // (FLATE_HIP_INFLATE_RING; measured crossover)
-    if (pin_io) HIP_OK(h, hipStreamSynchronize(h->s_out));  // (nothing of an earlier call may still read st_out)
-    // (a wave per stream: a sub-batch must still fill the chip -- 20 streams per CU -- or the kernel's latency per
-    // stream, not the copies, decides; measured: sub-batches of 1024 streams are slower than no overlap at all)
-    // sub-batches of one size (4097 streams used to be 4096 + 1, and the launch for the one cost a stream's whole latency)
-    uint32_t sub = n_chunks;
-    if (pin_io) {
-        // (a sub-batch has to fill the chip -- 20 streams per CU -- or the latency of a stream decides: two sub-batches of
-        // 2049 streams take as long as one batch, five of 3277 are 33 GB/s against 24, tools/e2e_inflate_probe.py)
-        const uint32_t target = 3u * (uint32_t)h->knobs.host_pass_chunks;
-        const uint32_t nsub = std::max(1u, n_chunks / target);
-        sub = (n_chunks + nsub - 1) / nsub;
-    }
-    size_t pass_index = 0;
-    if (pin_io) {
-        // Every sub-batch's input copy is submitted BEFORE any output copy: an output copy waits for its sub-batch's kernels,
-        // and an input copy submitted behind it can land in the same in-order DMA queue and wait with it -- then nothing
-        // overlaps (round 5, profiles/r05_host_path.txt: what happened to the compress path's rectangle copy).
-        size_t k = 0;
-        for (uint32_t c0 = 0; c0 < n_chunks; c0 += sub, k++) {
-            const uint32_t nc = std::min(sub, n_chunks - c0);
-            hipEvent_t ev_in;
-            if ((rc = xfer_event(h, 2 * k, &ev_in))) return rc;
-            const uint64_t a = hin[c0], b = hin[c0 + nc];
-            if (b > a)
-                HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (a - in_lo), in + a, b - a, hipMemcpyHostToDevice, h->s_in));
-            HIP_OK(h, hipEventRecord(ev_in, h->s_in));
-        }
-    }
-    for (uint32_t c0 = 0; c0 < n_chunks; c0 += sub, pass_index++) {
-        const uint32_t nc = std::min(sub, n_chunks - c0);
-        if (pin_io) {  // this sub-batch's input: it came in while the sub-batches before it were decoded
-            hipEvent_t ev_in;
-            if ((rc = xfer_event(h, 2 * pass_index, &ev_in))) return rc;
-            HIP_OK(h, hipStreamWaitEvent(st, ev_in, 0));
-        }
-        const fl_chunk* dch = (const fl_chunk*)h->chunks.p + c0;
-        // Long streams of a batch that has few of them: a workgroup per stream (kernels_inflate_par.h).  It marks
-        // what it does not finish (short streams, anything irregular) FL_PAR_REDO, and k_inflate takes those.
-        const int32_t* redo_only = nullptr;
-        if (use_par) {
-            ProfScope ps(h, K_INFLATE_PAR);
-            hipLaunchKernelGGL(k_inflate_par, dim3(nc), dim3(FP_THREADS), 0, st, d_in, dch, container, flags, par_min_bytes,
-                               h->crc, d_out, d_outlen + c0, d_status + c0, d_consumed ? d_consumed + c0 : nullptr);
-            redo_only = d_status + c0;
-        }
-        {
-            ProfScope ps(h, K_INFLATE);
-            if (large)
-                hipLaunchKernelGGL(k_inflate<FL_INF_RING_LARGE>, dim3(nc), dim3(64), 0, st, d_in, dch, container, flags,
-                                   h->crc, d_out, d_outlen + c0, d_status + c0,
-                                   d_consumed ? d_consumed + c0 : nullptr, redo_only, (uint32_t*)h->dbg_par_handed.p);
-            else
-                hipLaunchKernelGGL(k_inflate<FL_INF_RING_SMALL>, dim3(nc), dim3(64), 0, st, d_in, dch, container, flags,
-                                   h->crc, d_out, d_outlen + c0, d_status + c0,
-                                   d_consumed ? d_consumed + c0 : nullptr, redo_only, (uint32_t*)h->dbg_par_handed.p);
-        }
-        HIP_OK(h, hipGetLastError());
-        if (pin_io) {  // this sub-batch's output slots go home while the next sub-batch is decoded
-            hipEvent_t ev_out;
-            if ((rc = xfer_event(h, 2 * pass_index + 1, &ev_out))) return rc;
-            HIP_OK(h, hipEventRecord(ev_out, st));
-            HIP_OK(h, hipStreamWaitEvent(h->s_out, ev_out, 0));
-            const uint64_t a = hout[c0], b = hout[c0 + nc];
-            if (b > a)
-                HIP_OK(h, hipMemcpyAsync(out + a, d_out + (a - out_shift), b - a, hipMemcpyDeviceToHost, h->s_out));
-        }
-    }
-    HIP_OK(h, hipGetLastError());
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        if (consumed)
-            HIP_OK(h, hipMemcpyAsync(consumed, d_consumed, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-        if (pin_io)
-            HIP_OK(h, hipStreamSynchronize(h->s_out));
-        else if ((rc = copy_out_host(h, d_out, d_outlen, n_chunks, hout, out_shift, out, out_len)))
-            return rc;
-    } else if (h->sync) {
-        HIP_OK(h, hipStreamSynchronize(st));
-    }
+    if ((rc = stage_inflate_call(ic))) return rc;
+    if ((rc = inflate_by_spans(ic))) return rc;
+    if ((rc = choose_inflate_paths(ic))) return rc;
+    if ((rc = submit_input_copies(ic))) return rc;
+    if ((rc = run_sub_batches(ic))) return rc;
+    if ((rc = results_home(ic.f, out_len, status, consumed)) || (rc = wait_for_results(ic.f))) return rc;
+    if (ic.pin_io) HIP_OK(h, hipStreamSynchronize(h->s_out));
+    else if (ic.f.host) return copy_out_host(h, ic.f.d_out, ic.f.d_outlen, n_chunks, hout, ic.f.out_shift, out, out_len);
     return FLATE_HIP_OK;
 }
 
@@ -2807,65 +2861,30 @@ int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const ui
     std::vector<uint64_t> hin;
     int rc = fetch_offsets(h, in_off, n_chunks, memkind, hin);
     if (rc) return rc;
-    const uint64_t in_lo = hin[0], in_hi = hin[n_chunks];
-    const uint8_t* d_in = in;
-    uint64_t* d_sizes = sizes;
-    int32_t* d_status = status;
-    uint64_t* d_consumed = consumed;
-    uint64_t in_shift = 0;
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16))) return rc;
-        if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_chunks))) return rc;
-        if ((rc = ensure(h, h->st_status, sizeof(int32_t) * n_chunks))) return rc;
-        if ((rc = ensure(h, h->st_consumed, sizeof(uint64_t) * n_chunks))) return rc;
-        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-        d_in = (const uint8_t*)h->st_in.p;
-        d_sizes = (uint64_t*)h->st_outlen.p;
-        d_status = (int32_t*)h->st_status.p;
-        d_consumed = (uint64_t*)h->st_consumed.p;
-        in_shift = in_lo;
-    }
-    std::vector<fl_chunk> chunks(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; i++) {
-        const uint64_t len = hin[i + 1] - hin[i];
-        if (len > 0xfffffff0ull) return FLATE_HIP_E_INVALID_ARG;
-        fl_chunk c{};
-        c.in_off = hin[i] - in_shift;
-        c.in_len = (uint32_t)len;
-        chunks[i] = c;
-    }
-    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n_chunks))) return rc;
-    HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
-    HIP_OK(h, hipStreamSynchronize(st));
+    InflateFrame f(h, memkind, n_chunks);
+    f.input(in, hin[0], hin[n_chunks]).results(sizes, status, consumed);  // (no output buffer)
+    if ((rc = reserve_frame(f, FRAME_CONSUMED)) || (rc = stage_frame_whole(f, FRAME_CONSUMED))) return rc;
+    std::vector<fl_chunk> chunks;
+    if (!fl_inflate_chunks(hin.data(), nullptr, n_chunks, f.in_shift, 0, chunks)) return FLATE_HIP_E_INVALID_ARG;
+    if ((rc = upload_chunks(h, chunks))) return rc;
     h->dbg_size_chain = h->dbg_size_whole = 0;
     // A few long streams: each by many waves at once; what comes out whole is skipped below.
-    const int done = size_by_spans(h, st, d_in, chunks, container, flags, d_sizes, d_status, d_consumed);
+    const int done = size_by_spans(h, st, f.d_in, chunks, container, flags, f.d_outlen, f.d_status, f.d_consumed);
     if (done < 0) {
         h->last_error = std::string("size probe by spans: ") + hipGetErrorString(hipGetLastError());
         return FLATE_HIP_E_LAUNCH;
     }
-    if (done > 0) {
-        HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n_chunks, hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-    }
+    if (done > 0 && (rc = upload_chunks(h, chunks))) return rc;
     h->dbg_size_chain = (uint64_t)done;
     h->dbg_size_whole = n_chunks - (uint64_t)done;
     if ((uint32_t)done < n_chunks) {
         ProfScope ps(h, K_INFLATE_SIZE);
-        hipLaunchKernelGGL(k_inflate_size<false>, dim3(n_chunks), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p, container,
-                           flags, d_sizes, d_status, d_consumed, (const fl_size_span*)nullptr, (fl_size_rec*)nullptr);
+        hipLaunchKernelGGL(k_inflate_size<false>, dim3(n_chunks), dim3(64), 0, st, f.d_in, (const fl_chunk*)h->chunks.p, container,
+                           flags, f.d_outlen, f.d_status, f.d_consumed, (const fl_size_span*)nullptr, (fl_size_rec*)nullptr);
     }
     HIP_OK(h, hipGetLastError());
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        HIP_OK(h, hipMemcpyAsync(sizes, d_sizes, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        if (consumed)
-            HIP_OK(h, hipMemcpyAsync(consumed, d_consumed, sizeof(uint64_t) * n_chunks, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-    } else if (h->sync) {
-        HIP_OK(h, hipStreamSynchronize(st));
-    }
-    return FLATE_HIP_OK;
+    if ((rc = results_home(f, sizes, status, consumed))) return rc;
+    return wait_for_results(f);
 }
 
 int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]) {
@@ -2874,6 +2893,229 @@ int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]) {
     counts[1] = h->dbg_size_whole;
     return FLATE_HIP_OK;
 }
+
+}  // extern "C"
+
+namespace {
+
+// ---- flate_hip_decompress_members: the call's record and its stages (the rules: member_plan.h)
+struct MemberCall {
+    flate_hip_ctx* h;
+    hipStream_t st;
+    uint32_t n;
+    int container, flags;
+    const std::vector<uint64_t>& hin;  // the caller's offsets
+    InflateFrame f;
+    const uint64_t* d_inoff;  // the input offsets on the device: the caller's, or vin staged
+    uint32_t* d_nmem;
+    std::vector<uint64_t> vin, vout;  // the offsets the kernels and decompress_core see
+    bool scan = false;                // the members are searched for (gzip), not walked
+    uint64_t n_cand = 0;
+    fl_member_tiles tiles;
+    uint64_t cap = 0;  // entries of all tables together, at most
+    uint64_t M = 0;    // ... and as they came back
+    std::vector<uint64_t> doff, msize;
+    std::vector<uint32_t> mstart;
+    std::vector<uint64_t> min_, mout;  // the members as a batch of their own
+};
+
+// host memory: the whole call runs on staged copies whose offsets start at 0
+int stage_member_call(MemberCall& mc, const std::vector<uint64_t>& hout, bool want_nmem) {
+    flate_hip_ctx* h = mc.h;
+    InflateFrame& f = mc.f;
+    const uint32_t n = mc.n, what = FRAME_OUT | FRAME_CONSUMED | FRAME_NULL_CONSUMED;
+    int rc;
+    mc.vin = mc.hin;
+    mc.vout = hout;
+    if (f.host) {
+        for (uint32_t i = 0; i <= n; i++) {
+            mc.vin[i] -= f.in_lo;
+            mc.vout[i] -= f.out_lo;
+        }
+        if ((rc = reserve_frame(f, what)) || (rc = ensure(h, h->st_inoff, sizeof(uint64_t) * ((size_t)n + 1))) ||
+            (rc = ensure(h, h->mb_nmem, sizeof(uint32_t) * n)) || (rc = stage_frame_whole(f, what)))
+            return rc;
+        HIP_OK(h, hipMemcpyAsync(h->st_inoff.p, mc.vin.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, mc.st));
+        if ((rc = clear_staged_out(f))) return rc;
+        mc.d_inoff = (const uint64_t*)h->st_inoff.p;
+        mc.d_nmem = want_nmem ? (uint32_t*)h->mb_nmem.p : nullptr;
+    }
+    h->dbg_member[0] = h->dbg_member[1] = h->dbg_member[2] = 0;
+    if ((rc = ensure(h, h->mb_taboff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if ((rc = ensure(h, h->mb_tabn, sizeof(uint64_t) * n))) return rc;
+    if ((rc = ensure(h, h->mb_non, sizeof(uint64_t) * n))) return rc;
+    return ensure(h, h->mb_denseoff, sizeof(uint64_t) * ((size_t)n + 1));
+}
+
+// scan: count the candidates; too many, and the call walks
+int count_member_candidates(MemberCall& mc) {
+    flate_hip_ctx* h = mc.h;
+    const InflateFrame& f = mc.f;
+    const uint64_t lo = mc.vin[0], hi = mc.vin[mc.n];
+    int rc;
+    mc.scan = mc.container == 1 && h->knobs.member_scan;
+    if (!mc.scan || hi <= lo) return FLATE_HIP_OK;
+    if (!fl_member_scan_tiles((uint64_t)(uintptr_t)f.d_in, lo, hi, mc.tiles)) return FLATE_HIP_E_INVALID_ARG;
+    const uint64_t n_tiles = mc.tiles.n_tiles;
+    if ((rc = ensure(h, h->mb_tiles, sizeof(uint64_t) * (n_tiles + 1)))) return rc;
+    if ((rc = ensure(h, h->mb_tileoff, sizeof(uint64_t) * (n_tiles + 1)))) return rc;
+    {
+        ProfScope ps(h, K_MEMBER_SCAN);
+        hipLaunchKernelGGL(k_member_scan<false>, dim3((uint32_t)n_tiles), dim3(64), 0, mc.st, f.d_in, mc.tiles.rel0, lo, hi, mc.d_inoff,
+                           mc.n, (uint64_t*)h->mb_tiles.p, (uint64_t*)nullptr, (fl_chunk*)nullptr, (uint64_t)0);
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, mc.st, (const uint64_t*)h->mb_tiles.p, (uint32_t)n_tiles,
+                           (uint64_t*)h->mb_tileoff.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipMemcpyAsync(&mc.n_cand, (const uint64_t*)h->mb_tileoff.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, mc.st));
+    HIP_OK(h, hipStreamSynchronize(mc.st));
+    if (mc.n_cand > h->knobs.member_candidates) mc.scan = false;
+    return FLATE_HIP_OK;
+}
+
+// the member tables: the candidates' arrays (scan) or where every stream's table starts (walk), and room for cap entries
+int size_member_tables(MemberCall& mc) {
+    flate_hip_ctx* h = mc.h;
+    const uint32_t n = mc.n;
+    int rc;
+    if (mc.scan) {
+        mc.cap = fl_member_scan_cap(mc.n_cand, n);
+        const size_t nc1 = (size_t)std::max<uint64_t>(mc.n_cand, 1);
+        if ((rc = ensure(h, h->mb_cand, sizeof(uint64_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_chunks, sizeof(fl_chunk) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_psize, sizeof(uint64_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_pstatus, sizeof(int32_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_pcons, sizeof(uint64_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_succ, sizeof(uint32_t) * nc1))) return rc;
+        if ((rc = ensure(h, h->mb_chain, sizeof(uint32_t) * nc1))) return rc;
+    } else {
+        std::vector<uint64_t> toff((size_t)n + 1);
+        mc.cap = fl_member_walk_offsets(mc.hin.data(), n, mc.container, toff.data());
+        HIP_OK(h, hipMemcpyAsync(h->mb_taboff.p, toff.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, mc.st));
+        HIP_OK(h, hipStreamSynchronize(mc.st));  // (toff leaves scope)
+    }
+    if ((rc = ensure(h, h->mb_tabstart, sizeof(uint32_t) * mc.cap))) return rc;
+    return ensure(h, h->mb_tabsize, sizeof(uint64_t) * mc.cap);
+}
+
+// every stream's table: from the chain of its candidates (scan), or member by member (walk)
+int scan_or_walk_members(MemberCall& mc) {
+    flate_hip_ctx* h = mc.h;
+    const InflateFrame& f = mc.f;
+    const uint32_t n = mc.n;
+    const uint64_t lo = mc.vin[0], hi = mc.vin[n];
+    if (mc.scan) {
+        if (mc.n_cand) {
+            {
+                ProfScope ps(h, K_MEMBER_SCAN);
+                hipLaunchKernelGGL(k_member_scan<true>, dim3((uint32_t)mc.tiles.n_tiles), dim3(64), 0, mc.st, f.d_in, mc.tiles.rel0, lo, hi,
+                                   mc.d_inoff, n, (uint64_t*)h->mb_tileoff.p, (uint64_t*)h->mb_cand.p, (fl_chunk*)h->mb_chunks.p, mc.n_cand);
+            }
+            ProfScope ps(h, K_INFLATE_SIZE);
+            hipLaunchKernelGGL(k_inflate_size<false>, dim3((uint32_t)mc.n_cand), dim3(64), 0, mc.st, f.d_in, (const fl_chunk*)h->mb_chunks.p,
+                               mc.container, mc.flags, (uint64_t*)h->mb_psize.p, (int32_t*)h->mb_pstatus.p, (uint64_t*)h->mb_pcons.p,
+                               (const fl_size_span*)nullptr, (fl_size_rec*)nullptr);
+        }
+        ProfScope ps(h, K_MEMBER_CHAIN);
+        hipLaunchKernelGGL(k_member_chain, dim3(n), dim3(64), 0, mc.st, mc.d_inoff, (const uint64_t*)h->mb_cand.p, (uint32_t)mc.n_cand,
+                           (const int32_t*)h->mb_pstatus.p, (const uint64_t*)h->mb_pcons.p, (const uint64_t*)h->mb_psize.p,
+                           (uint32_t*)h->mb_succ.p, (uint32_t*)h->mb_chain.p, (uint64_t*)h->mb_taboff.p, (uint64_t*)h->mb_tabn.p,
+                           (uint32_t*)h->mb_tabstart.p, (uint64_t*)h->mb_tabsize.p, (uint64_t*)h->mb_non.p);
+    } else {
+        ProfScope ps(h, K_MEMBER_WALK);
+        hipLaunchKernelGGL(k_member_walk, dim3(n), dim3(64), 0, mc.st, f.d_in, mc.d_inoff, mc.container, mc.flags,
+                           (const uint64_t*)h->mb_taboff.p, (uint64_t*)h->mb_tabn.p, (uint32_t*)h->mb_tabstart.p, (uint64_t*)h->mb_tabsize.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    return FLATE_HIP_OK;
+}
+
+// back to back, and home: with the candidates counted the table's size is bounded and it comes with its offsets
+int pack_and_fetch_members(MemberCall& mc) {
+    flate_hip_ctx* h = mc.h;
+    const uint32_t n = mc.n;
+    const uint64_t cap = mc.cap;
+    std::vector<uint64_t> non;
+    int rc;
+    mc.doff.resize((size_t)n + 1);
+    if ((rc = ensure(h, h->mb_dstart, sizeof(uint32_t) * cap))) return rc;
+    if ((rc = ensure(h, h->mb_dsize, sizeof(uint64_t) * cap))) return rc;
+    {
+        ProfScope ps(h, K_MEMBER_PACK);
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, mc.st, (const uint64_t*)h->mb_tabn.p, n, (uint64_t*)h->mb_denseoff.p);
+        hipLaunchKernelGGL(k_member_pack, dim3(n), dim3(64), 0, mc.st, (const uint64_t*)h->mb_taboff.p, (const uint64_t*)h->mb_tabn.p,
+                           (const uint32_t*)h->mb_tabstart.p, (const uint64_t*)h->mb_tabsize.p, (const uint64_t*)h->mb_denseoff.p,
+                           (uint32_t*)h->mb_dstart.p, (uint64_t*)h->mb_dsize.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipMemcpyAsync(mc.doff.data(), h->mb_denseoff.p, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, mc.st));
+    if (mc.scan) {
+        non.resize(n);
+        mc.mstart.resize(cap);
+        mc.msize.resize(cap);
+        HIP_OK(h, hipMemcpyAsync(non.data(), h->mb_non.p, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, mc.st));
+        HIP_OK(h, hipMemcpyAsync(mc.mstart.data(), h->mb_dstart.p, sizeof(uint32_t) * cap, hipMemcpyDeviceToHost, mc.st));
+        HIP_OK(h, hipMemcpyAsync(mc.msize.data(), h->mb_dsize.p, sizeof(uint64_t) * cap, hipMemcpyDeviceToHost, mc.st));
+    }
+    HIP_OK(h, hipStreamSynchronize(mc.st));
+    mc.M = mc.doff[n];
+    if (!fl_member_count_ok(mc.M, n, cap)) {
+        h->last_error = "member table: " + std::to_string(mc.M) + " members of " + std::to_string(n) + " streams";
+        return FLATE_HIP_E_LAUNCH;
+    }
+    if (!mc.scan) {
+        mc.mstart.resize(mc.M);
+        mc.msize.resize(mc.M);
+        HIP_OK(h, hipMemcpyAsync(mc.mstart.data(), h->mb_dstart.p, sizeof(uint32_t) * mc.M, hipMemcpyDeviceToHost, mc.st));
+        HIP_OK(h, hipMemcpyAsync(mc.msize.data(), h->mb_dsize.p, sizeof(uint64_t) * mc.M, hipMemcpyDeviceToHost, mc.st));
+        HIP_OK(h, hipStreamSynchronize(mc.st));
+        h->dbg_member[1] = n;
+        return FLATE_HIP_OK;
+    }
+    uint64_t on = 0;
+    for (uint32_t i = 0; i < n; i++) on += non[i];
+    h->dbg_member[0] = n;
+    h->dbg_member[2] = mc.n_cand - on;
+    return FLATE_HIP_OK;
+}
+
+// the members as a batch of their own: a contiguous partition of the input and of the slots
+int partition_members(MemberCall& mc) {
+    mc.min_.resize((size_t)mc.M + 1);
+    mc.mout.resize((size_t)mc.M + 1);
+    const fl_member_verdict v = fl_member_partition(mc.doff.data(), mc.mstart.data(), mc.msize.data(), mc.vin.data(), mc.vout.data(),
+                                                    mc.n, mc.min_.data(), mc.mout.data());
+    if (v.fault == FL_MEM_TAB_OK) return FLATE_HIP_OK;
+    mc.h->last_error = "member table: stream " + std::to_string(v.stream) +
+                       (v.fault == FL_MEM_TAB_NO_FIRST ? " does not start with a member" : " is out of order");
+    return FLATE_HIP_E_LAUNCH;
+}
+
+int decode_members(MemberCall& mc) {
+    flate_hip_ctx* h = mc.h;
+    int rc;
+    if ((rc = ensure(h, h->mb_outlen, sizeof(uint64_t) * mc.M))) return rc;
+    if ((rc = ensure(h, h->mb_status, sizeof(int32_t) * mc.M))) return rc;
+    if ((rc = ensure(h, h->mb_cons, sizeof(uint64_t) * mc.M))) return rc;
+    return decompress_core(h, mc.f.d_in, mc.min_, (uint32_t)mc.M, mc.container, mc.flags, mc.f.d_out, mc.mout, (uint64_t*)h->mb_outlen.p,
+                           (int32_t*)h->mb_status.p, (uint64_t*)h->mb_cons.p, FLATE_HIP_MEM_DEVICE);
+}
+
+int fold_members(MemberCall& mc) {
+    flate_hip_ctx* h = mc.h;
+    {
+        ProfScope ps(h, K_MEMBER_FOLD);
+        hipLaunchKernelGGL(k_member_fold, dim3(mc.n), dim3(64), 0, mc.st, (const uint64_t*)h->mb_denseoff.p,
+                           (const uint64_t*)h->mb_outlen.p, (const int32_t*)h->mb_status.p, (const uint64_t*)h->mb_cons.p, mc.f.d_outlen,
+                           mc.f.d_status, mc.f.d_consumed, mc.d_nmem);
+    }
+    HIP_OK(h, hipGetLastError());
+    return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 // The members of every stream, found on the device (kernels_members.h), decoded by decompress_core as streams of their own
 // and folded back.  The host waits for the offsets, for the candidate count (scan) or the member count (walk), and for
@@ -2886,220 +3128,26 @@ int flate_hip_decompress_members(flate_hip_handle h, const uint8_t* in, const ui
     if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
     if (n_streams == 0) return FLATE_HIP_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
-    hipStream_t st = h->stream;
     const uint32_t n = n_streams;
-
     std::vector<uint64_t> hin, hout;
-    int rc = fetch_offsets(h, in_off, n, memkind, hin);
-    if (rc) return rc;
-    if ((rc = fetch_offsets(h, out_off, n, memkind, hout))) return rc;
-    for (uint32_t i = 0; i < n; i++)
-        if (hin[i + 1] - hin[i] > 0xfffffff0ull) return FLATE_HIP_E_INVALID_ARG;
-    const uint64_t in_lo = hin[0], in_hi = hin[n], out_lo = hout[0], out_hi = hout[n];
-
-    // host memory: the whole call runs on staged copies whose offsets start at 0
-    const bool host = memkind == FLATE_HIP_MEM_HOST;
-    const uint8_t* d_in = in;
-    uint8_t* d_out = out;
-    const uint64_t* d_inoff = in_off;
-    uint64_t* d_outlen = out_len;
-    int32_t* d_status = status;
-    uint64_t* d_consumed = consumed;
-    uint32_t* d_nmem = n_members;
-    std::vector<uint64_t> vin(hin), vout(hout);  // the offsets the kernels and decompress_core see
-    if (host) {
-        for (uint32_t i = 0; i <= n; i++) {
-            vin[i] -= in_lo;
-            vout[i] -= out_lo;
-        }
-        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16))) return rc;
-        if ((rc = ensure(h, h->st_out, (out_hi - out_lo) + 16))) return rc;
-        if ((rc = ensure(h, h->st_inoff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-        if ((rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n))) return rc;
-        if ((rc = ensure(h, h->st_status, sizeof(int32_t) * n))) return rc;
-        if ((rc = ensure(h, h->st_consumed, sizeof(uint64_t) * n))) return rc;
-        if ((rc = ensure(h, h->mb_nmem, sizeof(uint32_t) * n))) return rc;
-        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(h->st_in.p, in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipMemcpyAsync(h->st_inoff.p, vin.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
-        // (what goes back to the caller beyond out_len[i] is zeros, never bytes of an earlier call)
-        if (out_hi > out_lo) HIP_OK(h, hipMemsetAsync(h->st_out.p, 0, out_hi - out_lo, st));
-        d_in = (const uint8_t*)h->st_in.p;
-        d_out = (uint8_t*)h->st_out.p;
-        d_inoff = (const uint64_t*)h->st_inoff.p;
-        d_outlen = (uint64_t*)h->st_outlen.p;
-        d_status = (int32_t*)h->st_status.p;
-        d_consumed = consumed ? (uint64_t*)h->st_consumed.p : nullptr;
-        d_nmem = n_members ? (uint32_t*)h->mb_nmem.p : nullptr;
-    }
-    const uint64_t lo = vin[0], hi = vin[n];
-
-    h->dbg_member[0] = h->dbg_member[1] = h->dbg_member[2] = 0;
-    if ((rc = ensure(h, h->mb_taboff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ensure(h, h->mb_tabn, sizeof(uint64_t) * n))) return rc;
-    if ((rc = ensure(h, h->mb_non, sizeof(uint64_t) * n))) return rc;
-    if ((rc = ensure(h, h->mb_denseoff, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-
-    // ---- scan: count the candidates; too many, and the call walks ----
-    bool scan = container == 1 && h->knobs.member_scan;
-    uint64_t n_cand = 0;
-    int64_t rel0 = 0;
-    uint64_t n_tiles = 0;
-    if (scan && hi > lo) {
-        const uintptr_t first = (uintptr_t)(d_in + lo);
-        rel0 = (int64_t)lo - (int64_t)(first & 15);
-        n_tiles = (uint64_t)((int64_t)hi - rel0 + FL_MEM_SCAN_TILE - 1) / FL_MEM_SCAN_TILE;
-        if (n_tiles > 0x7fffffffull) return FLATE_HIP_E_INVALID_ARG;
-        if ((rc = ensure(h, h->mb_tiles, sizeof(uint64_t) * (n_tiles + 1)))) return rc;
-        if ((rc = ensure(h, h->mb_tileoff, sizeof(uint64_t) * (n_tiles + 1)))) return rc;
-        {
-            ProfScope ps(h, K_MEMBER_SCAN);
-            hipLaunchKernelGGL(k_member_scan<false>, dim3((uint32_t)n_tiles), dim3(64), 0, st, d_in, rel0, lo, hi, d_inoff, n,
-                               (uint64_t*)h->mb_tiles.p, (uint64_t*)nullptr, (fl_chunk*)nullptr, (uint64_t)0);
-            hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, st, (const uint64_t*)h->mb_tiles.p, (uint32_t)n_tiles,
-                               (uint64_t*)h->mb_tileoff.p);
-        }
-        HIP_OK(h, hipGetLastError());
-        HIP_OK(h, hipMemcpyAsync(&n_cand, (const uint64_t*)h->mb_tileoff.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-        if (n_cand > h->knobs.member_candidates) scan = false;
-    }
-
-    // ---- the member tables ----
-    uint64_t cap = 0;  // entries of all tables together, at most
-    if (scan) {
-        cap = n_cand + n;
-        const size_t nc1 = (size_t)std::max<uint64_t>(n_cand, 1);
-        if ((rc = ensure(h, h->mb_cand, sizeof(uint64_t) * nc1))) return rc;
-        if ((rc = ensure(h, h->mb_chunks, sizeof(fl_chunk) * nc1))) return rc;
-        if ((rc = ensure(h, h->mb_psize, sizeof(uint64_t) * nc1))) return rc;
-        if ((rc = ensure(h, h->mb_pstatus, sizeof(int32_t) * nc1))) return rc;
-        if ((rc = ensure(h, h->mb_pcons, sizeof(uint64_t) * nc1))) return rc;
-        if ((rc = ensure(h, h->mb_succ, sizeof(uint32_t) * nc1))) return rc;
-        if ((rc = ensure(h, h->mb_chain, sizeof(uint32_t) * nc1))) return rc;
-    } else {
-        const uint32_t least = fl_member_least_bytes(container);
-        std::vector<uint64_t> toff((size_t)n + 1);
-        for (uint32_t i = 0; i < n; i++) {
-            toff[i] = cap;
-            cap += (hin[i + 1] - hin[i]) / least + 2;
-        }
-        toff[n] = cap;
-        HIP_OK(h, hipMemcpyAsync(h->mb_taboff.p, toff.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipStreamSynchronize(st));  // (toff leaves scope)
-    }
-    if ((rc = ensure(h, h->mb_tabstart, sizeof(uint32_t) * cap))) return rc;
-    if ((rc = ensure(h, h->mb_tabsize, sizeof(uint64_t) * cap))) return rc;
-    if (scan) {
-        if (n_cand) {
-            {
-                ProfScope ps(h, K_MEMBER_SCAN);
-                hipLaunchKernelGGL(k_member_scan<true>, dim3((uint32_t)n_tiles), dim3(64), 0, st, d_in, rel0, lo, hi, d_inoff, n,
-                                   (uint64_t*)h->mb_tileoff.p, (uint64_t*)h->mb_cand.p, (fl_chunk*)h->mb_chunks.p, n_cand);
-            }
-            ProfScope ps(h, K_INFLATE_SIZE);
-            hipLaunchKernelGGL(k_inflate_size<false>, dim3((uint32_t)n_cand), dim3(64), 0, st, d_in, (const fl_chunk*)h->mb_chunks.p,
-                               container, flags, (uint64_t*)h->mb_psize.p, (int32_t*)h->mb_pstatus.p, (uint64_t*)h->mb_pcons.p,
-                               (const fl_size_span*)nullptr, (fl_size_rec*)nullptr);
-        }
-        ProfScope ps(h, K_MEMBER_CHAIN);
-        hipLaunchKernelGGL(k_member_chain, dim3(n), dim3(64), 0, st, d_inoff, (const uint64_t*)h->mb_cand.p, (uint32_t)n_cand,
-                           (const int32_t*)h->mb_pstatus.p, (const uint64_t*)h->mb_pcons.p, (const uint64_t*)h->mb_psize.p,
-                           (uint32_t*)h->mb_succ.p, (uint32_t*)h->mb_chain.p, (uint64_t*)h->mb_taboff.p, (uint64_t*)h->mb_tabn.p,
-                           (uint32_t*)h->mb_tabstart.p, (uint64_t*)h->mb_tabsize.p, (uint64_t*)h->mb_non.p);
-    } else {
-        ProfScope ps(h, K_MEMBER_WALK);
-        hipLaunchKernelGGL(k_member_walk, dim3(n), dim3(64), 0, st, d_in, d_inoff, container, flags, (const uint64_t*)h->mb_taboff.p,
-                           (uint64_t*)h->mb_tabn.p, (uint32_t*)h->mb_tabstart.p, (uint64_t*)h->mb_tabsize.p);
-    }
-    HIP_OK(h, hipGetLastError());
-    // back to back, and home: with the candidates counted the table's size is bounded and it comes with its offsets
-    std::vector<uint64_t> doff((size_t)n + 1), non;
-    std::vector<uint32_t> mstart;
-    std::vector<uint64_t> msize;
-    if ((rc = ensure(h, h->mb_dstart, sizeof(uint32_t) * cap))) return rc;
-    if ((rc = ensure(h, h->mb_dsize, sizeof(uint64_t) * cap))) return rc;
-    {
-        ProfScope ps(h, K_MEMBER_PACK);
-        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, st, (const uint64_t*)h->mb_tabn.p, n, (uint64_t*)h->mb_denseoff.p);
-        hipLaunchKernelGGL(k_member_pack, dim3(n), dim3(64), 0, st, (const uint64_t*)h->mb_taboff.p, (const uint64_t*)h->mb_tabn.p,
-                           (const uint32_t*)h->mb_tabstart.p, (const uint64_t*)h->mb_tabsize.p, (const uint64_t*)h->mb_denseoff.p,
-                           (uint32_t*)h->mb_dstart.p, (uint64_t*)h->mb_dsize.p);
-    }
-    HIP_OK(h, hipGetLastError());
-    HIP_OK(h, hipMemcpyAsync(doff.data(), h->mb_denseoff.p, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
-    if (scan) {
-        non.resize(n);
-        mstart.resize(cap);
-        msize.resize(cap);
-        HIP_OK(h, hipMemcpyAsync(non.data(), h->mb_non.p, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(mstart.data(), h->mb_dstart.p, sizeof(uint32_t) * cap, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(msize.data(), h->mb_dsize.p, sizeof(uint64_t) * cap, hipMemcpyDeviceToHost, st));
-    }
-    HIP_OK(h, hipStreamSynchronize(st));
-    const uint64_t M = doff[n];
-    if (M < n || M > cap || M > 0xfffffff0ull) {
-        h->last_error = "member table: " + std::to_string(M) + " members of " + std::to_string(n) + " streams";
-        return FLATE_HIP_E_LAUNCH;
-    }
-    if (!scan) {
-        mstart.resize(M);
-        msize.resize(M);
-        HIP_OK(h, hipMemcpyAsync(mstart.data(), h->mb_dstart.p, sizeof(uint32_t) * M, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(msize.data(), h->mb_dsize.p, sizeof(uint64_t) * M, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-    }
-    if (scan) {
-        uint64_t on = 0;
-        for (uint32_t i = 0; i < n; i++) on += non[i];
-        h->dbg_member[0] = n;
-        h->dbg_member[2] = n_cand - on;
-    } else {
-        h->dbg_member[1] = n;
-    }
-
-    // ---- the members as a batch of their own: a contiguous partition of the input and of the slots ----
-    std::vector<uint64_t> min_((size_t)M + 1), mout((size_t)M + 1);
-    for (uint32_t i = 0; i < n; i++) {
-        const uint64_t m0 = doff[i], m = doff[i + 1] - m0;
-        if (m == 0 || mstart[m0] != 0) {
-            h->last_error = "member table: stream " + std::to_string(i) + " does not start with a member";
-            return FLATE_HIP_E_LAUNCH;
-        }
-        for (uint64_t k = 0; k < m; k++) {
-            min_[m0 + k] = vin[i] + mstart[m0 + k];
-            if (min_[m0 + k] > vin[i + 1] || (k && mstart[m0 + k] < mstart[m0 + k - 1])) {
-                h->last_error = "member table: stream " + std::to_string(i) + " is out of order";
-                return FLATE_HIP_E_LAUNCH;
-            }
-        }
-        fl_member_slots(msize.data() + m0, (uint32_t)m, vout[i], vout[i + 1], mout.data() + m0);
-    }
-    min_[M] = vin[n];
-    mout[M] = vout[n];
-    if ((rc = ensure(h, h->mb_outlen, sizeof(uint64_t) * M))) return rc;
-    if ((rc = ensure(h, h->mb_status, sizeof(int32_t) * M))) return rc;
-    if ((rc = ensure(h, h->mb_cons, sizeof(uint64_t) * M))) return rc;
-    if ((rc = decompress_core(h, d_in, min_, (uint32_t)M, container, flags, d_out, mout, (uint64_t*)h->mb_outlen.p,
-                              (int32_t*)h->mb_status.p, (uint64_t*)h->mb_cons.p, FLATE_HIP_MEM_DEVICE)))
-        return rc;
-    {
-        ProfScope ps(h, K_MEMBER_FOLD);
-        hipLaunchKernelGGL(k_member_fold, dim3(n), dim3(64), 0, st, (const uint64_t*)h->mb_denseoff.p,
-                           (const uint64_t*)h->mb_outlen.p, (const int32_t*)h->mb_status.p, (const uint64_t*)h->mb_cons.p, d_outlen,
-                           d_status, d_consumed, d_nmem);
-    }
-    HIP_OK(h, hipGetLastError());
-    if (host) {
-        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        if (consumed) HIP_OK(h, hipMemcpyAsync(consumed, d_consumed, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-        if (n_members) HIP_OK(h, hipMemcpyAsync(n_members, d_nmem, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-        if ((rc = copy_out_host(h, d_out, d_outlen, n, hout, out_lo, out, out_len))) return rc;
-    } else if (h->sync) {
-        HIP_OK(h, hipStreamSynchronize(st));
-    }
-    return FLATE_HIP_OK;
+    int rc;
+    if ((rc = fetch_offsets(h, in_off, n, memkind, hin)) || (rc = fetch_offsets(h, out_off, n, memkind, hout))) return rc;
+    if (fl_inflate_oversize(hin.data(), n) != n) return FLATE_HIP_E_INVALID_ARG;
+    InflateFrame f(h, memkind, n);
+    f.input(in, hin[0], hin[n]).output(out, hout[0], hout[n]).results(out_len, status, consumed);
+    MemberCall mc{h, h->stream, n, container, flags, hin, f, in_off, n_members};
+    if ((rc = stage_member_call(mc, hout, n_members != nullptr))) return rc;
+    if ((rc = count_member_candidates(mc))) return rc;
+    if ((rc = size_member_tables(mc))) return rc;
+    if ((rc = scan_or_walk_members(mc))) return rc;
+    if ((rc = pack_and_fetch_members(mc))) return rc;
+    if ((rc = partition_members(mc))) return rc;
+    if ((rc = decode_members(mc))) return rc;
+    if ((rc = fold_members(mc))) return rc;
+    if ((rc = results_home(mc.f, out_len, status, consumed))) return rc;
+    if (mc.f.host && n_members) HIP_OK(h, hipMemcpyAsync(n_members, mc.d_nmem, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = wait_for_results(mc.f))) return rc;
+    return mc.f.host ? copy_out_host(h, mc.f.d_out, mc.f.d_outlen, n, hout, mc.f.out_shift, out, out_len) : FLATE_HIP_OK;
 }
 
 int flate_hip_debug_member_paths(flate_hip_handle h, uint64_t counts[3]) {
@@ -4154,20 +4202,6 @@ struct flate_hip_index {
 
 namespace {
 
-// n values of a caller's array to the host (memkind says where they are)
-template <class T>
-int fetch_array(flate_hip_ctx* h, const T* p, uint64_t n, int memkind, std::vector<T>& host) {
-    host.resize(n);
-    if (!n) return FLATE_HIP_OK;
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        memcpy(host.data(), p, sizeof(T) * n);
-    } else {
-        HIP_OK(h, hipMemcpyAsync(host.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost, h->stream));
-        HIP_OK(h, hipStreamSynchronize(h->stream));
-    }
-    return FLATE_HIP_OK;
-}
-
 int index_alloc_windows(flate_hip_ctx* h, flate_hip_index* ix) {
     if (!ix->tab.win_bytes) return FLATE_HIP_OK;
     if (hipMalloc((void**)&ix->d_win, ix->tab.win_bytes) != hipSuccess) {
@@ -4189,17 +4223,10 @@ int index_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const
     fl_idx_tab& t = ix->tab;
     const uint32_t n = (uint32_t)t.streams.size();
     int rc;
-    std::vector<fl_chunk> chunks(n);
-    for (uint32_t i = 0; i < n; i++) {
-        fl_chunk c{};
-        c.in_off = hin[i] - in_shift;
-        c.in_len = (uint32_t)t.streams[i].in_len;
-        c.skip = t.streams[i].status != 0;  // (not walked, and not cut below)
-        chunks[i] = c;
-    }
-    if ((rc = ensure(h, h->chunks, sizeof(fl_chunk) * n))) return rc;
-    HIP_OK(h, hipMemcpyAsync(h->chunks.p, chunks.data(), sizeof(fl_chunk) * n, hipMemcpyHostToDevice, st));
-    HIP_OK(h, hipStreamSynchronize(st));
+    std::vector<fl_chunk> chunks;  // (the streams' lengths are hin's: flate_hip_index_build took them from it)
+    if (!fl_inflate_chunks(hin.data(), nullptr, n, in_shift, 0, chunks)) return FLATE_HIP_E_INVALID_ARG;
+    for (uint32_t i = 0; i < n; i++) chunks[i].skip = t.streams[i].status != 0;  // (not walked, and not cut below)
+    if ((rc = upload_chunks(h, chunks))) return rc;
     // ---- long streams: the size probe's spans, and where their chain closes a walk per live span
     std::vector<std::vector<fl_idx_span_walk>> cut(n);
     {
@@ -4476,15 +4503,9 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
     }
     const uint64_t scratch = fl_idx_passes(slot.data(), n_ranges, h->knobs.index_pass_bytes, pass_first, slot_off);
 
-    const uint8_t* d_in = in;
-    uint8_t* d_out = out;
-    uint64_t* d_outlen = out_len;
-    int32_t* d_status = status;
-    uint64_t in_shift = 0, out_shift = 0;
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        if ((rc = ensure(h, h->st_in, (in_hi - in_lo) + 16)) || (rc = ensure(h, h->st_out, (out_hi - out_lo) + 16)) ||
-            (rc = ensure(h, h->st_outlen, sizeof(uint64_t) * n_ranges)) || (rc = ensure(h, h->st_status, sizeof(int32_t) * n_ranges)))
-            return rc;
+    InflateFrame f(h, memkind, n_ranges);
+    f.input(in, in_lo, in_hi).output(out, out_lo, out_hi).results(out_len, status, nullptr);
+    if (f.host) {
         // Of the input only what the decodes can consume is staged, each byte at its own place: from a range's point to
         // the first point at or behind its end.  (The bit reader stages and looks ahead beyond that; what it finds there
         // is never consumed.)
@@ -4495,14 +4516,7 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
                 iv.push_back(hin[hstream[j]] + plan[j].in_hi);
             }
         fl_idx_merge_intervals(iv, 65536);
-        for (size_t k = 0; k + 1 < iv.size(); k += 2)
-            HIP_OK(h, hipMemcpyAsync((uint8_t*)h->st_in.p + (iv[k] - in_lo), in + iv[k], iv[k + 1] - iv[k], hipMemcpyHostToDevice, st));
-        d_in = (const uint8_t*)h->st_in.p;
-        d_out = (uint8_t*)h->st_out.p;
-        d_outlen = (uint64_t*)h->st_outlen.p;
-        d_status = (int32_t*)h->st_status.p;
-        in_shift = in_lo;
-        out_shift = out_lo;
+        if ((rc = reserve_frame(f, FRAME_OUT)) || (rc = stage_frame(f, FRAME_OUT, iv.data(), iv.size()))) return rc;
     }
     std::vector<fl_range_job> jobs(n_ranges);
     std::vector<uint64_t> rtab(2 * (size_t)n_ranges);  // the pack kernel's: source in the scratch | destination
@@ -4513,7 +4527,7 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
         jb.decode = p.decode;
         if (p.decode) {
             const fl_idx_point& pt = t.points[p.point];
-            jb.in_off = hin[hstream[j]] - in_shift;
+            jb.in_off = hin[hstream[j]] - f.in_shift;
             jb.in_len = (uint32_t)t.streams[hstream[j]].in_len;
             jb.in_bit = pt.in_bit;
             jb.win_off = pt.win_off;
@@ -4524,7 +4538,7 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
         }
         jobs[j] = jb;
         rtab[j] = slot_off[j] + p.skip;
-        rtab[n_ranges + j] = hout[j] - out_shift;
+        rtab[n_ranges + j] = hout[j] - f.out_shift;
     }
     if ((rc = ensure(h, h->ix_rjobs, sizeof(fl_range_job) * n_ranges)) || (rc = ensure(h, h->ix_rtab, sizeof(uint64_t) * 2 * n_ranges)) ||
         (rc = ensure(h, h->ix_scratch, scratch + 16)))
@@ -4542,50 +4556,26 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
         const uint32_t a = (uint32_t)pass_first[k], nr = (uint32_t)(pass_first[k + 1] - pass_first[k]);
         uint64_t longest = 0;
         for (uint32_t j = a; j < a + nr; j++) longest = std::max(longest, plan[j].len);
-        // few ranges: each gets the large LDS ring; many: the small one keeps 20 per CU in flight (as decompress_core)
-        const bool large = h->knobs.inflate_ring >= 0 ? h->knobs.inflate_ring >= (int64_t)FL_INF_RING_LARGE : nr <= 4u * 256u;
         {
             ProfScope ps(h, K_INFLATE_RANGE);
-            if (large)
-                hipLaunchKernelGGL(k_inflate_range<FL_INF_RING_LARGE>, dim3(nr), dim3(64), 0, st, d_in, dj + a, 0, (const uint8_t*)idx->d_win,
-                                   dscr, d_outlen + a, d_status + a);
-            else
-                hipLaunchKernelGGL(k_inflate_range<FL_INF_RING_SMALL>, dim3(nr), dim3(64), 0, st, d_in, dj + a, 0, (const uint8_t*)idx->d_win,
-                                   dscr, d_outlen + a, d_status + a);
+            const auto kern = fl_inflate_ring_large(h->knobs.inflate_ring, nr) ? k_inflate_range<FL_INF_RING_LARGE> : k_inflate_range<FL_INF_RING_SMALL>;
+            hipLaunchKernelGGL(kern, dim3(nr), dim3(64), 0, st, f.d_in, dj + a, 0, (const uint8_t*)idx->d_win, dscr, f.d_outlen + a,
+                               f.d_status + a);
         }
         if (longest) {
             ProfScope ps(h, K_RANGE_PACK);
             const uint32_t ny = (uint32_t)std::min<uint64_t>(16, (longest + FL_GATHER_SLICE - 1) / FL_GATHER_SLICE);
-            hipLaunchKernelGGL(k_range_pack, dim3(nr, ny), dim3(256), 0, st, (const uint8_t*)dscr, dsrc + a, (const uint64_t*)(d_outlen + a),
-                               d_out, ddst + a);
+            hipLaunchKernelGGL(k_range_pack, dim3(nr, ny), dim3(256), 0, st, (const uint8_t*)dscr, dsrc + a, (const uint64_t*)(f.d_outlen + a),
+                               f.d_out, ddst + a);
         }
         HIP_OK(h, hipGetLastError());
         h->dbg_index_passes++;
     }
-    if (memkind == FLATE_HIP_MEM_HOST) {
-        HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * n_ranges, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_ranges, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-        // the delivered bytes back to back, then slot by slot: nothing else of the caller's buffer is written
-        std::vector<uint64_t> packoff(n_ranges + 1ull, 0);
-        for (uint32_t j = 0; j < n_ranges; j++) packoff[j + 1] = packoff[j] + out_len[j];
-        const uint64_t total = packoff[n_ranges];
-        if (total) {
-            if ((rc = ensure(h, h->st_pack, total + 16)) || (rc = ensure(h, h->st_packoff, sizeof(uint64_t) * (n_ranges + 1ull)))) return rc;
-            HIP_OK(h, hipMemcpyAsync(h->st_packoff.p, packoff.data(), sizeof(uint64_t) * (n_ranges + 1ull), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_gather_copy, gather_grid(n_ranges), dim3(256), 0, st, (const uint8_t*)d_out, ddst, (const uint64_t*)d_outlen,
-                               (uint8_t*)h->st_pack.p, (const uint64_t*)h->st_packoff.p);
-            HIP_OK(h, hipGetLastError());
-            std::vector<uint8_t> packed(total);
-            HIP_OK(h, hipMemcpyAsync(packed.data(), h->st_pack.p, total, hipMemcpyDeviceToHost, st));
-            HIP_OK(h, hipStreamSynchronize(st));
-            for (uint32_t j = 0; j < n_ranges; j++)
-                if (out_len[j]) memcpy(out + hout[j], packed.data() + packoff[j], out_len[j]);
-        }
-    } else if (h->sync) {
-        HIP_OK(h, hipStreamSynchronize(st));
-    }
-    return FLATE_HIP_OK;
+    if ((rc = results_home(f, out_len, status, nullptr)) || (rc = wait_for_results(f)) || !f.host) return rc;
+    // the delivered bytes back to back, then slot by slot: nothing else of the caller's buffer is written
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < n_ranges; j++) total += out_len[j];
+    return total ? copy_out_packed(h, f.d_out, ddst, f.d_outlen, n_ranges, hout, f.out_shift, out, out_len, total) : FLATE_HIP_OK;
 }
 
 // Debug / test seam: the good streams of the last flate_hip_index_build call that were walked span by span / whole by one wave.

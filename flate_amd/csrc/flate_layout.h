@@ -9,6 +9,12 @@
 #define FL_CHUNK_STRIDE 65536u  // per-chunk stride of the LZ scratch arrays
 #define FL_BLOCK_BYTES 65535u   // SimpleCompressor buffer, deflate.zig:456
 
+// The inflaters (kernels_inflate.h): recent output kept in LDS (power of two); matches up to ring - 260 back are served
+// from it.  Large batches run the small ring (20 streams per CU in flight); small batches, where the
+// latency of one stream is what counts, the large one: every match is then an LDS copy (inflate_plan.h decides).
+#define FL_INF_RING_SMALL 2048u
+#define FL_INF_RING_LARGE 32768u
+
 // One independent input chunk (= one output stream).
 struct fl_chunk {
     uint64_t in_off;   // byte offset of the chunk in `in`

@@ -39,11 +39,7 @@ typedef fl_hdec_t<32> fl_hdec_small;  // distance (30) and code-length (19) alph
 #ifndef FL_INF16_DST_BITS
 #define FL_INF16_DST_BITS 9  // k_inflate's own distance table (fl_inflate_ws16): 7 KB of LDS per stream still hold 20 per CU; 8 bits 17.9 ms, 9: 17.6, 10: 19.1
 #endif
-// Recent output kept in LDS (power of two); matches up to ring - 260 back are served from it.
-// Large batches run the small ring (20 streams per CU in flight); small batches, where the
-// latency of one stream is what counts, the large one: every match is then an LDS copy.
-#define FL_INF_RING_SMALL 2048u
-#define FL_INF_RING_LARGE 32768u
+// (FL_INF_RING_SMALL / FL_INF_RING_LARGE, the recent output kept in LDS: flate_layout.h)
 
 struct fl_inflate_ws {
     enum { DST_BITS = FL_INF_DST_BITS };

@@ -118,3 +118,82 @@ FL_MP_HD void fl_member_slots(const uint64_t* size, uint32_t m, uint64_t slot_st
         at += size[k] < room ? size[k] : room;
     }
 }
+
+// ---- the host's side of flate_hip_decompress_members (flate_hip.hip)
+
+#define FL_MEM_MAX_TILES 0x7fffffffull    // tiles of a scan: a workgroup each, the grid's x
+#define FL_MEM_MAX_MEMBERS 0xfffffff0ull  // members of a call: they are decoded as one batch, whose count is 32 bits
+
+// The scan's tiles over the input bytes [lo, hi) (offsets into the buffer at address `base`): a lane reads 16 bytes at an
+// address that is a multiple of 16, so the first tile starts at rel0 <= lo (it may be negative: the bytes before lo are
+// not looked at), up to 15 bytes before it.  False: more tiles than a grid has workgroups.
+struct fl_member_tiles {
+    int64_t rel0 = 0;
+    uint64_t n_tiles = 0;
+};
+inline bool fl_member_scan_tiles(uint64_t base, uint64_t lo, uint64_t hi, fl_member_tiles& t) {
+    const uint64_t first = base + lo;
+    t.rel0 = (int64_t)lo - (int64_t)(first & 15);
+    t.n_tiles = (uint64_t)((int64_t)hi - t.rel0 + FL_MEM_SCAN_TILE - 1) / FL_MEM_SCAN_TILE;
+    return t.n_tiles <= FL_MEM_MAX_TILES;
+}
+
+// Entries of all member tables together, at most.  Scan: every candidate is on at most one chain, and a stream's table
+// has at most one entry more than its chain (the failing remainder).
+inline uint64_t fl_member_scan_cap(uint64_t n_cand, uint32_t n_streams) { return n_cand + n_streams; }
+
+// Walk: a stream of len bytes has at most len / least + 1 members, and one entry more for the remainder; toff[0..n] is
+// where every stream's table starts in the one array (k_member_walk's).  Returns toff[n], the capacity.
+inline uint64_t fl_member_walk_offsets(const uint64_t* hin, uint32_t n, int container, uint64_t* toff) {
+    const uint32_t least = fl_member_least_bytes(container);
+    uint64_t cap = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        toff[i] = cap;
+        cap += (hin[i + 1] - hin[i]) / least + 2;
+    }
+    toff[n] = cap;
+    return cap;
+}
+
+// The number of members that came back: every stream has at least one entry, and the tables hold no more than cap.
+inline bool fl_member_count_ok(uint64_t M, uint32_t n_streams, uint64_t cap) {
+    return !(M < n_streams || M > cap || M > FL_MEM_MAX_MEMBERS);
+}
+
+// What is wrong with the table of a stream
+enum fl_member_fault { FL_MEM_TAB_OK = 0, FL_MEM_TAB_NO_FIRST = 1, FL_MEM_TAB_ORDER = 2 };
+struct fl_member_verdict {
+    int fault = FL_MEM_TAB_OK;
+    uint32_t stream = 0;  // the first stream whose table is refused
+};
+
+// The members as a batch of their own: a contiguous partition of the input and of the slots.  doff[0..n]: where every
+// stream's entries are in mstart / msize (a prefix sum of the table lengths: ascending from 0, doff[n] = M entries, which
+// fl_member_count_ok has seen); vin / vout[0..n]: the streams' input offsets and slots as the kernels see them.  Writes
+// min_ / mout[0..M]: the members' input offsets and slots.  A stream's table is refused when it is empty or its first
+// member does not start at the stream's first byte (NO_FIRST), and when a start goes backwards or lies beyond the
+// stream's end (ORDER); min_ / mout are then not to be used.
+inline fl_member_verdict fl_member_partition(const uint64_t* doff, const uint32_t* mstart, const uint64_t* msize, const uint64_t* vin,
+                                             const uint64_t* vout, uint32_t n, uint64_t* min_, uint64_t* mout) {
+    fl_member_verdict v;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t m0 = doff[i], m = doff[i + 1] - m0;
+        v.stream = i;
+        if (m == 0 || mstart[m0] != 0) {
+            v.fault = FL_MEM_TAB_NO_FIRST;
+            return v;
+        }
+        for (uint64_t k = 0; k < m; k++) {
+            min_[m0 + k] = vin[i] + mstart[m0 + k];
+            if (min_[m0 + k] > vin[i + 1] || (k && mstart[m0 + k] < mstart[m0 + k - 1])) {
+                v.fault = FL_MEM_TAB_ORDER;
+                return v;
+            }
+        }
+        fl_member_slots(msize + m0, (uint32_t)m, vout[i], vout[i + 1], mout + m0);
+    }
+    v.stream = 0;
+    min_[doff[n]] = vin[n];
+    mout[doff[n]] = vout[n];
+    return v;
+}

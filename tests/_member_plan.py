@@ -26,8 +26,55 @@ def lib():
         L.shim_member_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64,
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
         L.shim_member_slots.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.shim_member_scan_tiles.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.shim_member_scan_cap.argtypes = [C.c_uint64, C.c_uint32]
+        L.shim_member_scan_cap.restype = C.c_uint64
+        L.shim_member_walk_offsets.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        L.shim_member_walk_offsets.restype = C.c_uint64
+        L.shim_member_count_ok.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
+        L.shim_member_partition.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         _lib = L
     return _lib
+
+
+OK, NO_FIRST, ORDER = 0, 1, 2   # fl_member_fault
+
+
+def scan_tiles(base, lo, hi):
+    """(rel0, n_tiles), or None where the scan would need more tiles than a grid has"""
+    rel0, n_tiles = C.c_int64(0), C.c_uint64(0)
+    ok = lib().shim_member_scan_tiles(base, lo, hi, C.byref(rel0), C.byref(n_tiles))
+    return (rel0.value, n_tiles.value) if ok else None
+
+
+def scan_cap(n_cand, n_streams):
+    return int(lib().shim_member_scan_cap(n_cand, n_streams))
+
+
+def walk_offsets(hin, container):
+    """(toff[0..n], capacity)"""
+    a = np.array(hin, np.uint64)
+    toff = np.zeros(len(hin), np.uint64)
+    cap = lib().shim_member_walk_offsets(a.ctypes.data, len(hin) - 1, container, toff.ctypes.data)
+    return [int(x) for x in toff], int(cap)
+
+
+def count_ok(M, n_streams, cap):
+    return bool(lib().shim_member_count_ok(M, n_streams, cap))
+
+
+def partition(doff, mstart, msize, vin, vout):
+    """(fault, stream, min_, mout): the members' input offsets and slots (None, None where the table is refused)"""
+    n, M = len(doff) - 1, doff[-1]
+    d, s, z = np.array(doff, np.uint64), np.array(list(mstart) + [0], np.uint32), np.array(list(msize) + [0], np.uint64)
+    vi, vo = np.array(vin, np.uint64), np.array(vout, np.uint64)
+    min_, mout = np.zeros(M + 1, np.uint64), np.zeros(M + 1, np.uint64)
+    stream = C.c_uint32(0)
+    fault = lib().shim_member_partition(d.ctypes.data, s.ctypes.data, z.ctypes.data, vi.ctypes.data, vo.ctypes.data, n,
+                                        min_.ctypes.data, mout.ctypes.data, C.byref(stream))
+    if fault:
+        return fault, stream.value, None, None
+    return fault, stream.value, [int(x) for x in min_], [int(x) for x in mout]
 
 
 def scan_tile():

@@ -42,4 +42,32 @@ void shim_member_slots(const uint64_t* size, uint32_t m, uint64_t slot_start, ui
     fl_member_slots(size, m, slot_start, slot_end, out);
 }
 
+// ---- the host's side of flate_hip_decompress_members
+
+// the scan's tiles over [lo, hi) of a buffer at address base; returns 0 where there are too many
+int shim_member_scan_tiles(uint64_t base, uint64_t lo, uint64_t hi, int64_t* rel0, uint64_t* n_tiles) {
+    fl_member_tiles t;
+    const bool ok = fl_member_scan_tiles(base, lo, hi, t);
+    *rel0 = t.rel0;
+    *n_tiles = t.n_tiles;
+    return ok ? 1 : 0;
+}
+
+uint64_t shim_member_scan_cap(uint64_t n_cand, uint32_t n_streams) { return fl_member_scan_cap(n_cand, n_streams); }
+
+// toff[0..n]; returns the capacity
+uint64_t shim_member_walk_offsets(const uint64_t* hin, uint32_t n, int container, uint64_t* toff) {
+    return fl_member_walk_offsets(hin, n, container, toff);
+}
+
+int shim_member_count_ok(uint64_t M, uint32_t n_streams, uint64_t cap) { return fl_member_count_ok(M, n_streams, cap) ? 1 : 0; }
+
+// min_ / mout[0..doff[n]]; returns the fault (0: none) and the stream it names
+int shim_member_partition(const uint64_t* doff, const uint32_t* mstart, const uint64_t* msize, const uint64_t* vin, const uint64_t* vout,
+                          uint32_t n, uint64_t* min_, uint64_t* mout, uint32_t* stream) {
+    const fl_member_verdict v = fl_member_partition(doff, mstart, msize, vin, vout, n, min_, mout);
+    *stream = v.stream;
+    return v.fault;
+}
+
 }  // extern "C"

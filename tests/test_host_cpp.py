@@ -60,6 +60,25 @@ def test_stream_plan_under_the_sanitizers():
     assert "ok" in r.stdout
 
 
+def test_inflate_plan_under_the_sanitizers():
+    """tests/host_cpp/test_inflate_plan.cpp: a program of its own, built with AddressSanitizer and UBSan, that pushes random
+    and hostile inputs (empty streams, streams at and beyond the length limit, nearly 2^32 streams, member tables with an
+    empty stream, a first start that is not 0, starts that go backwards or lie beyond their stream) through every rule of
+    flate_amd/csrc/inflate_plan.h and through the host's side of flate_amd/csrc/member_plan.h.  It checks that the sub-batches
+    partition [0, n), that the members of an accepted table are a contiguous ascending cover of the input range and of the
+    slots, that a refused table names the stream that was spoilt, and that a table's capacity is never below what it holds;
+    what the rules decide is the business of tests/test_inflate_plan_cpu.py and tests/test_members_cpu.py."""
+    src = os.path.join(ROOT, "tests", "host_cpp", "test_inflate_plan.cpp")
+    exe = os.path.join(ROOT, "tests", "host_cpp", "test_inflate_plan")
+    deps = [src] + [os.path.join(ROOT, "flate_amd", "csrc", h) for h in ("inflate_plan.h", "member_plan.h", "flate_layout.h", "flate_common.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-o", exe, src],
+                       check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ok" in r.stdout
+
+
 @pytest.mark.gpu
 def test_facade_public_interface_on_gpu():
     import torch

@@ -112,6 +112,88 @@ def test_a_stream_inside_a_batch():
     assert M.stream_of([7, 8], 7) == 0
 
 
+# ---------------------------------------------------------------- the host's side of the call (member_plan.h)
+
+TILE = 16384
+
+
+@pytest.mark.parametrize("residue", range(16))
+def test_scan_tiles_at_every_residue_of_the_address(residue):
+    """a lane reads 16 bytes at a multiple of 16: the first tile starts up to 15 bytes before the first input byte"""
+    assert M.scan_tile() == TILE
+    base = 0x7f0000001000 + residue
+    for lo in (0, 3, 100):
+        back = (base + lo) & 15
+        rel0 = lo - back                                  # negative where lo < back
+        for k in (1, 2):
+            assert M.scan_tiles(base, lo, rel0 + k * TILE - 1) == (rel0, k)
+            assert M.scan_tiles(base, lo, rel0 + k * TILE) == (rel0, k)
+            assert M.scan_tiles(base, lo, rel0 + k * TILE + 1) == (rel0, k + 1)
+        assert M.scan_tiles(base, lo, lo + 1) == (rel0, 1)
+
+
+def test_scan_tiles_bound():
+    most = 0x7fffffff
+    assert M.scan_tiles(0x1000, 0, most * TILE) == (0, most)
+    assert M.scan_tiles(0x1000, 0, most * TILE + 1) is None
+    assert M.scan_tiles(0x1001, 16, most * TILE + 1) == (15, most)     # (the tiles start at 15)
+    assert M.scan_tiles(0x1001, 16, most * TILE + 16) is None
+
+
+@pytest.mark.parametrize("container, least, toff", [
+    (0, 2, [0, 52, 54, 76]),      # 100 / 2 + 2, 0 / 2 + 2, 41 / 2 + 2
+    (1, 20, [0, 7, 9, 13]),       # 100 / 20 + 2, 2, 41 / 20 + 2
+    (2, 8, [0, 14, 16, 23]),      # 100 / 8 + 2, 2, 41 / 8 + 2
+])
+def test_table_capacities(container, least, toff):
+    assert M.least_bytes(container) == least
+    # walk: a table per stream, side by side; the offsets of the streams in the caller's buffer do not matter
+    assert M.walk_offsets([0, 100, 100, 141], container) == (toff, toff[-1])
+    assert M.walk_offsets([1000, 1100, 1100, 1141], container) == (toff, toff[-1])
+    # ... a stream of k smallest members and some bytes more holds them and the failing remainder
+    for k in (1, 7, 1000):
+        assert M.walk_offsets([0, k * least + least - 1], container)[1] == k + 2
+    # scan: every candidate on at most one chain, one entry more per stream
+    assert M.scan_cap(0, 3) == 3 and M.scan_cap(10, 3) == 13 and M.scan_cap(1 << 22, 0xffffffff) == (1 << 22) + 0xffffffff
+
+
+def test_member_count_that_came_back():
+    assert M.count_ok(2, 2, 10) and M.count_ok(10, 2, 10)
+    assert not M.count_ok(1, 2, 10)                       # a stream without an entry
+    assert not M.count_ok(11, 2, 10)                      # more than the tables hold
+    assert M.count_ok(0xfffffff0, 1, 1 << 40) and not M.count_ok(0xfffffff1, 1, 1 << 40)
+
+
+VIN, VOUT = [0, 100, 250], [1000, 2000, 2600]
+
+
+def test_partition_of_a_good_table():
+    fault, _, min_, mout = M.partition([0, 2, 3], [0, 40, 0], [300, 9999, 50], VIN, VOUT)
+    assert fault == M.OK
+    assert min_ == [0, 40, 100, 250]
+    assert mout == [1000, 1300, 2000, 2600]
+    # a member may start at its stream's end (an empty remainder), and a member's size is clamped to the stream's slot
+    fault, _, min_, mout = M.partition([0, 3, 4], [0, 40, 100, 0], [999, 999, 0, 1], VIN, VOUT)
+    assert fault == M.OK and min_ == [0, 40, 100, 100, 250] and mout == [1000, 1999, 2000, 2000, 2600]
+
+
+@pytest.mark.parametrize("doff, mstart, fault, stream", [
+    ([0, 2, 2], [0, 40], 1, 1),                 # a stream with 0 members (the last one: nothing behind the table is read)
+    ([0, 0, 2], [0, 40], 1, 0),
+    ([0, 2, 3], [0, 40, 5], 1, 1),              # a first start that is not 0
+    ([0, 2, 3], [1, 40, 0], 1, 0),
+    ([0, 3, 4], [0, 40, 39, 0], 2, 0),          # a start that goes backwards
+    ([0, 1, 4], [0, 0, 20, 19], 2, 1),
+    ([0, 2, 3], [0, 101, 0], 2, 0),             # a start beyond the stream (100 bytes)
+    ([0, 1, 3], [0, 0, 151], 2, 1),
+    ([0, 3, 3], [0, 40, 39], 2, 0),             # two bad streams: the first is named
+    ([0, 2, 4], [0, 101, 7, 8], 2, 0),
+])
+def test_partition_refuses_hostile_tables(doff, mstart, fault, stream):
+    assert (M.NO_FIRST, M.ORDER) == (1, 2)
+    assert M.partition(doff, mstart, [10] * len(mstart), VIN, VOUT)[:2] == (fault, stream)
+
+
 def test_slots():
     assert M.slots([10, 0, 5], 100, 200) == [100, 110, 110]
     assert M.slots([10, 95, 5], 100, 200) == [100, 110, 200]   # clamped to the stream's slot

@@ -131,7 +131,8 @@ def rows(d, pattern):
     return out
 
 
-def listing(d):
+def listing(d, call_names=NAMES):
+    """call_names: what the calls of the run are called, in order (tools/inflate_calls.py lists its own run with this)"""
     api = sorted(rows(d, "*hip_api_trace.csv"), key=lambda r: (int(r["Start_Timestamp"]), int(r["Correlation_Id"])))
     main_thread = max(set(r["Thread_Id"] for r in api), key=lambda t: sum(1 for r in api if r["Thread_Id"] == t))
     api = [r for r in api if r["Thread_Id"] == main_thread]
@@ -147,9 +148,9 @@ def listing(d):
     pairs = [(a, b) for a, b in zip(sync, sync[1:]) if all(n in quiet for n in names[a + 1:b])]
     spans = [(p[1] + 1, q[0]) for p, q in zip(pairs, pairs[1:])]
     spans = [(a, b) for a, b in spans if any(n not in quiet for n in names[a:b])]
-    assert len(spans) == len(NAMES) * REPEATS, (len(spans), len(sync), sorted(set(names)))
+    assert len(spans) == len(call_names) * REPEATS, (len(spans), len(sync), sorted(set(names)))
     for k, (a, b) in enumerate(spans):
-        print("==== call %d (%s), repeat %d: %d HIP calls" % (k // REPEATS, NAMES[k // REPEATS], k % REPEATS, b - a))
+        print("==== call %d (%s), repeat %d: %d HIP calls" % (k // REPEATS, call_names[k // REPEATS], k % REPEATS, b - a))
         launched = []
         for r in api[a:b]:
             print("  " + r["Function"])
