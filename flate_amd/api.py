@@ -583,13 +583,19 @@ class ContainerModule:
         self.store = _Simple(container, _capi.MODE_STORE)
         self.Options, self.Level = Options, Level
 
-    def compress(self, reader, writer, options=None, engine=None, *, piece=None, zdict=None, joined=None):
+    def compress(self, reader, writer, options=None, engine=None, *, piece=None, zdict=None, joined=None, index=None):
         """zdict=: a preset dictionary (flate and zlib only, gzip raises ValueError): the stream is what
         zlib.decompressobj(wbits, zdict=zdict) and decompress(..., zdict=zdict) inflate (flate_hip_compress_batch_dict).
         Its last min(len, 32768) bytes and the input may be 65535 bytes together, else ValueError.
         joined=True, or a piece size of 1..65535: ONE stream of independent pieces (65535 bytes for True) at the rate of
-        the chunk path, whatever the input's length (flate_hip_compress_joined); exclusive with piece= and zdict=."""
+        the chunk path, whatever the input's length (flate_hip_compress_joined); exclusive with piece= and zdict=.
+        index=True, or a spacing in bytes (with joined= only): the call returns the blob (bytes) of a seek index over the
+        stream it wrote -- its points are piece starts and carry no windows (flate_hip_compress_joined_indexed); True is
+        the default spacing, 1 MiB.  index_from_bytes(blob, stream) reads ranges from it.  Otherwise None is returned."""
         zdict = _zdict_for(self._container, zdict)  # (gzip: ValueError, before an engine is made)
+        want_index = index is not None and index is not False
+        if want_index and (joined is None or joined is False):
+            raise ValueError("index= needs joined=: only a stream of independent pieces has window-free points")
         if joined is not None and joined is not False:
             if piece is not None or zdict is not None:
                 raise ValueError("joined= takes neither piece= nor zdict=")
@@ -602,13 +608,25 @@ class ContainerModule:
             if options.repair_q1:  # (the flag is the handle's: set for this call only, as _Compressor does)
                 eng.set_flags(_capi.DEFLATE_REPAIR_Q1)
             try:
-                outs, st = eng.compress_joined([data], self._container, int(options.level), piece=size)
+                if want_index:
+                    spacing = 0 if index is True else int(index)
+                    if spacing < 0:
+                        raise ValueError("index= is True or a spacing of at least 1 byte")
+                    outs, st, ix = eng.compress_joined([data], self._container, int(options.level), piece=size, index_spacing=spacing)
+                else:
+                    outs, st = eng.compress_joined([data], self._container, int(options.level), piece=size)
             finally:
                 if options.repair_q1:
                     eng.set_flags(0)
+            blob = None
+            if want_index:
+                try:
+                    blob = eng.index_export(ix)
+                finally:
+                    eng.index_destroy(ix)
             _compress_status(st[0])
             writer.write(outs[0])
-            return
+            return blob
         if zdict is not None:
             if piece is not None:
                 raise ValueError("piece= takes no zdict=")

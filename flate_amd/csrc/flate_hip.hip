@@ -21,12 +21,14 @@
 #include "kernels_block.h"
 #include "kernels_common.h"
 #include "dict_compress_plan.h"
+#include "index_parts_plan.h"
 #include "index_plan.h"
 #include "inflate_plan.h"
 #include "join_plan.h"
 #include "kernels_deflater.h"
 #include "kernels_dict.h"
 #include "kernels_index.h"
+#include "kernels_index_parts.h"
 #include "kernels_inflate.h"
 #include "kernels_inflate_par.h"
 #include "kernels_inflate_size.h"
@@ -84,6 +86,9 @@ enum KernelId {
     K_INDEX_WINDOWS,
     K_INFLATE_RANGE,
     K_RANGE_PACK,
+    K_JOIN_POINTS,
+    K_INFLATE_PART,
+    K_RANGE_SETTLE,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
@@ -94,7 +99,8 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_member_scan", "k_member_chain", "k_member_walk", "k_member_pack", "k_member_fold",
                                            "k_gather", "k_inflater", "k_deflater", "k_inflate_dict", "k_dict_stage",
                                            "k_join_open", "k_join_scan", "k_join_pack",
-                                           "k_index_walk", "k_index_windows", "k_inflate_range", "k_range_pack"};
+                                           "k_index_walk", "k_index_windows", "k_inflate_range", "k_range_pack",
+                                           "k_join_points", "k_inflate_part", "k_range_settle"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -113,6 +119,16 @@ struct JoinCall {
     const uint32_t* d_piece_stream = nullptr;
     const fl_join_stream* d_streams = nullptr;
     uint32_t* d_piece_cks = nullptr;
+};
+
+// What flate_hip_compress_joined_indexed asks of the joined call beyond its outputs (index_parts_plan.h): the pieces that
+// are points, and where k_join_scan put them.
+struct JoinIndex {
+    uint64_t spacing = 0;
+    std::vector<fl_join_stream> streams;  // of the call (offsets less the staging shifts)
+    std::vector<uint64_t> n_which;        // per stream: how many of its pieces are points
+    std::vector<uint64_t> which;          // those pieces stream by stream, by their number within the stream
+    std::vector<uint64_t> place;          // piece_dst of each, once the stream has been waited for
 };
 
 }  // namespace
@@ -209,6 +225,7 @@ struct flate_hip_ctx {
     // length, status and checksum part, its place in its stream's slot; per stream the checksum -- join_plan.h.
     // `join`: such a call is running and its pieces are in compress_impl (enqueue_pass appends k_join_open to every pass)
     DevBuf jn_scratch, jn_streams, jn_pstream, jn_slot, jn_len, jn_status, jn_cks, jn_dst, jn_scks;
+    DevBuf jn_which, jn_place;  // flate_hip_compress_joined_indexed: the point pieces and their places
     const JoinCall* join = nullptr;
     // flate_hip_decompressed_sizes: the span table and the span records of its long streams, and for
     // flate_hip_debug_size_paths the streams of the last call whose size came from a closed chain / from one wave
@@ -225,6 +242,10 @@ struct flate_hip_ctx {
     // flate_hip_debug_index_passes the passes of the last ranges call
     DevBuf ix_jobs, ix_recs, ix_ptbit, ix_ptpos, ix_wtab, ix_rjobs, ix_rtab, ix_scratch;
     uint64_t dbg_index_passes = 0, dbg_index_spans = 0, dbg_index_whole = 0;
+    // ... on a fresh index (index_parts_plan.h): the part jobs, the parts' pack table, lengths and statuses, the ranges'
+    // records and slots; for flate_hip_debug_index_parts the direct and scratch parts of the last ranges call
+    DevBuf ix_pjobs, ix_ptab, ix_plen, ix_pstatus, ix_rrec, ix_rdst;
+    uint64_t dbg_index_direct = 0, dbg_index_scratch = 0;
     bool ws_fixed = false;   // the two-stream passes are being enqueued: ensure() may not grow a buffer (compress_impl)
     // last level 4..9 call, for the debug seam
     uint32_t dbg_pass_chunks = 0;
@@ -1568,7 +1589,8 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->st_consumed, &h->st_pack, &h->st_packoff, &h->st_slot, &h->dbg_par_handed, &h->dc_tab, &h->dc_bytes, &h->dc_of, &h->dcc_stage,
                       &h->dcc_jobs, &h->dcc_chunks, &h->jn_scratch, &h->jn_streams, &h->jn_pstream, &h->jn_slot, &h->jn_len,
                       &h->jn_status, &h->jn_cks, &h->jn_dst, &h->jn_scks, &h->ix_jobs, &h->ix_recs, &h->ix_ptbit, &h->ix_ptpos, &h->ix_wtab,
-                      &h->ix_rjobs, &h->ix_rtab, &h->ix_scratch})
+                      &h->ix_rjobs, &h->ix_rtab, &h->ix_scratch, &h->jn_which, &h->jn_place, &h->ix_pjobs, &h->ix_ptab, &h->ix_plen,
+                      &h->ix_pstatus, &h->ix_rrec, &h->ix_rdst})
         if (b->p) (void)hipFree(b->p);
     h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
@@ -2502,10 +2524,12 @@ int flate_hip_compress_batch_dict(flate_hip_handle h, const uint8_t* in, const u
 // One gzip / zlib / raw stream from independent pieces (include/flate_hip.h: what the bytes are; join_plan.h: every
 // decision).  Here: the offsets on the host, the streams' and pieces' tables on the device, the pieces through
 // compress_impl as raw chunks into scratch slots (k_join_open behind every pass: enqueue_pass), then the scan and the pack.
-// Host buffers are staged whole.
-int flate_hip_compress_joined(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
-                              uint32_t piece_bytes, int container, int mode, uint8_t* out, const uint64_t* out_off,
-                              uint64_t* out_len, int32_t* status, int memkind) {
+// Host buffers are staged whole.  ji (flate_hip_compress_joined_indexed): the pieces that are points are chosen once the
+// streams are laid out, and behind the scan their places are collected (k_join_points) and sent home; the caller waits.
+}  // extern "C"
+namespace {
+int joined_impl(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams, uint32_t piece_bytes, int container,
+                int mode, uint8_t* out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, int memkind, JoinIndex* ji) {
     if (!h || !in_off || !out_off || !out_len || !status) return FLATE_HIP_E_INVALID_ARG;
     if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
     if (!fl_join_args_ok(piece_bytes, container, mode)) return FLATE_HIP_E_INVALID_ARG;
@@ -2537,6 +2561,21 @@ int flate_hip_compress_joined(flate_hip_handle h, const uint8_t* in, const uint6
         (rc = ensure(h, h->jn_cks, sizeof(uint32_t) * (size_t)np)) || (rc = ensure(h, h->jn_dst, sizeof(uint64_t) * (size_t)np)) ||
         (rc = ensure(h, h->jn_scks, sizeof(uint32_t) * (size_t)n_streams)))
         return rc;
+    std::vector<uint64_t> which_piece;  // ji: the point pieces among the call's pieces
+    if (ji) {
+        ji->streams = streams;
+        ji->n_which.assign(n_streams, 0);
+        for (uint32_t i = 0; i < n_streams; i++) {
+            const size_t before = ji->which.size();
+            fl_idxp_point_pieces(streams[i].n, piece, ji->spacing, ji->which);
+            ji->n_which[i] = ji->which.size() - before;
+            for (size_t q = before; q < ji->which.size(); q++) which_piece.push_back(streams[i].piece0 + ji->which[q]);
+        }
+        ji->place.assign(which_piece.size(), 0);
+        if ((rc = ensure(h, h->jn_which, sizeof(uint64_t) * which_piece.size())) || (rc = ensure(h, h->jn_place, sizeof(uint64_t) * which_piece.size())))
+            return rc;
+        HIP_OK(h, hipMemcpyAsync(h->jn_which.p, which_piece.data(), sizeof(uint64_t) * which_piece.size(), hipMemcpyHostToDevice, st));
+    }
     const uint8_t* d_in = in;
     uint8_t* d_out = out;
     uint64_t* d_outlen = out_len;
@@ -2581,16 +2620,31 @@ int flate_hip_compress_joined(flate_hip_handle h, const uint8_t* in, const uint6
                            (const uint64_t*)h->jn_len.p, (const uint64_t*)h->jn_dst.p, jc.d_piece_stream, jc.d_streams, container,
                            (const uint64_t*)d_outlen, (const int32_t*)d_status, (const uint32_t*)h->jn_scks.p, d_out);
     }
+    if (ji) {
+        ProfScope ps(h, K_JOIN_POINTS);
+        const uint64_t nq = ji->place.size();
+        hipLaunchKernelGGL(k_join_points, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, st, (const uint64_t*)h->jn_dst.p,
+                           (const uint64_t*)h->jn_which.p, nq, (uint64_t*)h->jn_place.p);
+        HIP_OK(h, hipMemcpyAsync(ji->place.data(), h->jn_place.p, sizeof(uint64_t) * nq, hipMemcpyDeviceToHost, st));
+    }
     HIP_OK(h, hipGetLastError());
     if (host) {
         HIP_OK(h, hipMemcpyAsync(out_len, d_outlen, sizeof(uint64_t) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
         HIP_OK(h, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
         HIP_OK(h, hipStreamSynchronize(st));
         if ((rc = copy_out_host(h, d_out, d_outlen, n_streams, hout, out_lo, out, out_len))) return rc;
-    } else if (h->sync) {
+    } else if (h->sync || ji) {
         HIP_OK(h, hipStreamSynchronize(st));
     }
     return FLATE_HIP_OK;
+}
+}  // namespace
+extern "C" {
+
+int flate_hip_compress_joined(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                              uint32_t piece_bytes, int container, int mode, uint8_t* out, const uint64_t* out_off,
+                              uint64_t* out_len, int32_t* status, int memkind) {
+    return joined_impl(h, in, in_off, n_streams, piece_bytes, container, mode, out, out_off, out_len, status, memkind, nullptr);
 }
 
 int flate_hip_decompress_batch(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
@@ -4198,6 +4252,9 @@ int flate_hip_debug_inflate_paths(flate_hip_handle h, uint64_t counts[4]) {
 struct flate_hip_index {
     fl_idx_tab tab;
     uint8_t* d_win = nullptr;  // tab.win_bytes bytes
+    // made by flate_hip_compress_joined_indexed (or imported from a version-2 blob): every point is a piece start and has
+    // no window, ranges are cut into parts at the points (index_parts_plan.h)
+    bool fresh = false;
 };
 
 namespace {
@@ -4343,9 +4400,164 @@ int index_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const
     return FLATE_HIP_OK;
 }
 
+// flate_hip_decompress_ranges on a fresh index (index_parts_plan.h: the cut, the part table, the passes).  The offsets and
+// the range arrays are on the host already.  The host waits behind the upload of the tables; the parts of a pass are
+// decoded a wave each (k_inflate_part), its scratch parts copied to their slots (k_range_pack), and behind the last pass
+// k_range_settle gives every range its status and length; a host caller's results come home packed, slot by slot.
+int ranges_by_parts(flate_hip_ctx* h, const fl_idx_tab& t, const uint8_t* in, const std::vector<uint64_t>& hin, uint32_t n_ranges,
+                    const std::vector<uint32_t>& hstream, const std::vector<uint64_t>& hbegin, const std::vector<uint64_t>& hlen,
+                    uint8_t* out, const std::vector<uint64_t>& hout, uint64_t* out_len, int32_t* status, int memkind) {
+    hipStream_t st = h->stream;
+    int rc;
+    fl_idxp_call c;
+    if (!fl_idxp_plan_call(t, n_ranges, hstream.data(), hbegin.data(), hlen.data(), hout.data(), h->knobs.index_pass_bytes, c))
+        return FLATE_HIP_E_UNSUPPORTED;
+    const size_t np = c.parts.size();
+    h->dbg_index_direct = c.n_direct;
+    h->dbg_index_scratch = c.n_scratch;
+
+    InflateFrame f(h, memkind, n_ranges);
+    f.input(in, hin[0], hin[hin.size() - 1]).output(out, hout[0], hout[n_ranges]).results(out_len, status, nullptr);
+    if (f.host) {
+        // of the input only what the parts can consume is staged, each byte at its own place: from a part's point to the
+        // next point
+        std::vector<uint64_t> iv;
+        for (const fl_idxp_part& p : c.parts) {
+            iv.push_back(hin[hstream[p.range]] + p.in_lo);
+            iv.push_back(hin[hstream[p.range]] + p.in_hi);
+        }
+        fl_idx_merge_intervals(iv, 65536);
+        if ((rc = reserve_frame(f, FRAME_OUT)) || (rc = stage_frame(f, FRAME_OUT, iv.data(), iv.size()))) return rc;
+    }
+    std::vector<fl_part_job> jobs(np);
+    std::vector<uint64_t> ptab(2 * np);  // the pack kernel's: source in the scratch | destination
+    std::vector<fl_range_rec> recs(n_ranges);
+    std::vector<uint64_t> rdst(n_ranges);
+    for (size_t k = 0; k < np; k++) {
+        const fl_idxp_part& p = c.parts[k];
+        const fl_idx_point& pt = t.points[p.point];
+        const uint32_t si = hstream[p.range];
+        const uint64_t dst = (hout[p.range] - f.out_shift) + p.dst;
+        fl_part_job jb{};
+        jb.in_off = hin[si] - f.in_shift;
+        jb.in_len = (uint32_t)t.streams[si].in_len;
+        jb.in_bit = pt.in_bit;
+        jb.dst_off = p.direct ? dst : c.slot_off[k];
+        jb.need = p.skip + p.len;
+        jb.len = p.len;
+        jb.direct = p.direct;
+        jobs[k] = jb;
+        ptab[k] = c.slot_off[k] + p.skip;
+        ptab[np + k] = dst;
+    }
+    for (uint32_t j = 0; j < n_ranges; j++) {
+        recs[j] = fl_range_rec{c.ranges[j].part0, c.ranges[j].n_parts, c.ranges[j].len, c.ranges[j].status, 0};
+        rdst[j] = hout[j] - f.out_shift;
+    }
+    if ((rc = ensure(h, h->ix_pjobs, sizeof(fl_part_job) * np + 16)) || (rc = ensure(h, h->ix_ptab, sizeof(uint64_t) * 2 * np + 16)) ||
+        (rc = ensure(h, h->ix_plen, sizeof(uint64_t) * np + 16)) || (rc = ensure(h, h->ix_pstatus, sizeof(int32_t) * np + 16)) ||
+        (rc = ensure(h, h->ix_rrec, sizeof(fl_range_rec) * n_ranges)) || (rc = ensure(h, h->ix_rdst, sizeof(uint64_t) * n_ranges)) ||
+        (rc = ensure(h, h->ix_scratch, c.scratch + 16)))
+        return rc;
+    if (np) {
+        HIP_OK(h, hipMemcpyAsync(h->ix_pjobs.p, jobs.data(), sizeof(fl_part_job) * np, hipMemcpyHostToDevice, st));
+        HIP_OK(h, hipMemcpyAsync(h->ix_ptab.p, ptab.data(), sizeof(uint64_t) * 2 * np, hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(h, hipMemcpyAsync(h->ix_rrec.p, recs.data(), sizeof(fl_range_rec) * n_ranges, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->ix_rdst.p, rdst.data(), sizeof(uint64_t) * n_ranges, hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipStreamSynchronize(st));  // (the tables are on the host's stack)
+
+    // ---- the passes, one after the other in the stream: they share the scratch
+    const fl_part_job* dj = (const fl_part_job*)h->ix_pjobs.p;
+    const uint64_t* dsrc = (const uint64_t*)h->ix_ptab.p;
+    const uint64_t* ddst = dsrc + np;
+    uint64_t* dlen = (uint64_t*)h->ix_plen.p;
+    int32_t* dstat = (int32_t*)h->ix_pstatus.p;
+    uint8_t* dscr = (uint8_t*)h->ix_scratch.p;
+    for (size_t k = 0; k + 1 < c.pass_first.size(); k++) {
+        const size_t a = (size_t)c.pass_first[k];
+        const uint32_t n = (uint32_t)(c.pass_first[k + 1] - c.pass_first[k]);
+        uint64_t longest = 0;  // among the pass's scratch parts
+        for (size_t q = a; q < a + n; q++)
+            if (!c.parts[q].direct) longest = std::max(longest, c.parts[q].len);
+        {
+            ProfScope ps(h, K_INFLATE_PART);
+            const auto kern = fl_inflate_ring_large(h->knobs.inflate_ring, n) ? k_inflate_part<FL_INF_RING_LARGE> : k_inflate_part<FL_INF_RING_SMALL>;
+            hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, st, f.d_in, dj + a, 0, dscr, f.d_out, dlen + a, dstat + a);
+        }
+        if (longest) {
+            ProfScope ps(h, K_RANGE_PACK);
+            const uint32_t ny = (uint32_t)std::min<uint64_t>(16, (longest + FL_GATHER_SLICE - 1) / FL_GATHER_SLICE);
+            hipLaunchKernelGGL(k_range_pack, dim3(n, ny), dim3(256), 0, st, (const uint8_t*)dscr, dsrc + a, (const uint64_t*)(dlen + a), f.d_out,
+                               ddst + a);
+        }
+        HIP_OK(h, hipGetLastError());
+        h->dbg_index_passes++;
+    }
+    {
+        ProfScope ps(h, K_RANGE_SETTLE);
+        hipLaunchKernelGGL(k_range_settle, dim3(n_ranges), dim3(64), 0, st, (const fl_range_rec*)h->ix_rrec.p, (const int32_t*)dstat, f.d_outlen,
+                           f.d_status);
+    }
+    HIP_OK(h, hipGetLastError());
+    if ((rc = results_home(f, out_len, status, nullptr)) || (rc = wait_for_results(f)) || !f.host) return rc;
+    // the delivered bytes back to back, then slot by slot: nothing else of the caller's buffer is written
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < n_ranges; j++) total += out_len[j];
+    return total ? copy_out_packed(h, f.d_out, (const uint64_t*)h->ix_rdst.p, f.d_outlen, n_ranges, hout, f.out_shift, out, out_len, total)
+                 : FLATE_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+// flate_hip_compress_joined, with the places of the point pieces read back (index_parts_plan.h: which pieces, what the
+// points are).  The host waits for the stream, then, device memory, for out_len and status.
+int flate_hip_compress_joined_indexed(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                                      uint32_t piece_bytes, int container, int mode, uint8_t* out, const uint64_t* out_off,
+                                      uint64_t* out_len, int32_t* status, int memkind, uint64_t spacing, flate_hip_index_t* idx) {
+    if (!idx) return FLATE_HIP_E_INVALID_ARG;
+    *idx = nullptr;
+    JoinIndex ji;
+    ji.spacing = spacing;
+    int rc = joined_impl(h, in, in_off, n_streams, piece_bytes, container, mode, out, out_off, out_len, status, memkind, &ji);
+    if (rc) return rc;
+    std::vector<uint64_t> hlen;
+    std::vector<int32_t> hst;
+    if (n_streams && ((rc = fetch_array(h, out_len, n_streams, memkind, hlen)) || (rc = fetch_array(h, status, n_streams, memkind, hst))))
+        return rc;
+    for (uint32_t i = 0; i < n_streams; i++)
+        if (hlen[i] > FL_IDX_MAX_IN_LEN) {  // (no decompress call takes such a stream)
+            h->last_error = "joined stream " + std::to_string(i) + " is too long for a seek index";
+            return FLATE_HIP_E_UNSUPPORTED;
+        }
+    const uint32_t piece = fl_join_piece_bytes(piece_bytes);
+    flate_hip_index* ix = new flate_hip_index();
+    ix->fresh = true;
+    ix->tab.container = (uint32_t)container;
+    ix->tab.spacing = fl_idx_spacing(spacing);
+    ix->tab.streams.resize(n_streams);
+    uint64_t q0 = 0;
+    for (uint32_t i = 0; i < n_streams; i++) {
+        fl_idx_stream& s = ix->tab.streams[i];
+        const uint64_t nq = ji.n_which[i];
+        s.in_len = hlen[i];
+        s.status = hst[i];
+        s.size = 0;
+        s.point0 = ix->tab.points.size();
+        s.n_points = 0;
+        if (hst[i] == 0) {  // (a failed stream has no points: a piece of it may not inflate to `piece` bytes)
+            s.size = ji.streams[i].n;
+            for (uint64_t q = q0; q < q0 + nq; q++) ji.place[q] -= ji.streams[i].out_off;
+            fl_idxp_points(ji.which.data() + q0, ji.place.data() + q0, nq, piece, ix->tab.points);
+            s.n_points = nq;
+        }
+        q0 += nq;
+    }
+    *idx = ix;
+    return FLATE_HIP_OK;
+}
 
 // flate_hip_decompress_batch, then the walk over what it decoded.  The host waits as that call does, then for out_len and
 // status (device memory), for the walkers' records and points, and for the window copies.
@@ -4424,12 +4636,18 @@ int64_t flate_hip_index_points(flate_hip_handle h, flate_hip_index_t idx, uint32
 
 int flate_hip_index_export_size(flate_hip_handle h, flate_hip_index_t idx, uint64_t* bytes) {
     if (!h || !idx || !bytes) return FLATE_HIP_E_INVALID_ARG;
-    *bytes = fl_idx_blob_bytes(idx->tab);
+    *bytes = idx->fresh ? fl_idxp_blob_bytes(idx->tab) : fl_idx_blob_bytes(idx->tab);
     return FLATE_HIP_OK;
 }
 
 int flate_hip_index_export(flate_hip_handle h, flate_hip_index_t idx, uint8_t* blob_host, uint64_t cap) {
-    if (!h || !idx || !blob_host || cap < fl_idx_blob_bytes(idx->tab)) return FLATE_HIP_E_INVALID_ARG;
+    if (!h || !idx || !blob_host) return FLATE_HIP_E_INVALID_ARG;
+    if (idx->fresh) {  // (tables alone: nothing of it is on the device)
+        if (cap < fl_idxp_blob_bytes(idx->tab)) return FLATE_HIP_E_INVALID_ARG;
+        (void)fl_idxp_blob_write(idx->tab, blob_host);
+        return FLATE_HIP_OK;
+    }
+    if (cap < fl_idx_blob_bytes(idx->tab)) return FLATE_HIP_E_INVALID_ARG;
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
     const uint64_t at = fl_idx_blob_write(idx->tab, blob_host);
     if (idx->tab.win_bytes) {
@@ -4445,7 +4663,9 @@ int flate_hip_index_import(flate_hip_handle h, const uint8_t* blob_host, uint64_
     if (!h || !blob_host) return FLATE_HIP_E_INVALID_ARG;
     flate_hip_index* ix = new flate_hip_index();
     uint64_t at = 0;
-    if (!fl_idx_blob_parse(blob_host, bytes, ix->tab, &at)) {
+    // (the version field picks the parser; each refuses every version but its own)
+    ix->fresh = fl_idxp_blob_version(blob_host, bytes) == FL_IDXP_VERSION;
+    if (!(ix->fresh ? fl_idxp_blob_parse(blob_host, bytes, ix->tab) : fl_idx_blob_parse(blob_host, bytes, ix->tab, &at))) {
         delete ix;
         return FLATE_HIP_E_INVALID_ARG;
     }
@@ -4484,7 +4704,7 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
     if (n_streams && (rc = fetch_offsets(h, in_off, n_streams, memkind, hin))) return rc;
     for (uint32_t i = 0; i < n_streams; i++)
         if (hin[i + 1] - hin[i] != t.streams[i].in_len) return FLATE_HIP_E_INVALID_ARG;
-    h->dbg_index_passes = 0;
+    h->dbg_index_passes = h->dbg_index_direct = h->dbg_index_scratch = 0;
     if (n_ranges == 0) return FLATE_HIP_OK;
     if ((rc = fetch_offsets(h, out_off, n_ranges, memkind, hout)) || (rc = fetch_array(h, range_stream, n_ranges, memkind, hstream)) ||
         (rc = fetch_array(h, range_begin, n_ranges, memkind, hbegin)) || (rc = fetch_array(h, range_len, n_ranges, memkind, hlen)))
@@ -4493,6 +4713,7 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
         if (hstream[j] >= n_streams) return FLATE_HIP_E_INVALID_ARG;
     const uint64_t in_lo = hin[0], in_hi = hin[n_streams], out_lo = hout[0], out_hi = hout[n_ranges];
     if ((in_hi > in_lo && !in) || (out_hi > out_lo && !out)) return FLATE_HIP_E_INVALID_ARG;
+    if (idx->fresh) return ranges_by_parts(h, t, in, hin, n_ranges, hstream, hbegin, hlen, out, hout, out_len, status, memkind);
 
     // ---- every range: its point, what it skips and delivers, its scratch; the passes
     std::vector<fl_idx_range> plan(n_ranges);
@@ -4583,6 +4804,15 @@ int flate_hip_debug_index_paths(flate_hip_handle h, uint64_t counts[2]) {
     if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
     counts[0] = h->dbg_index_spans;
     counts[1] = h->dbg_index_whole;
+    return FLATE_HIP_OK;
+}
+
+// Debug / test seam: the parts of the last flate_hip_decompress_ranges call (a fresh index; else 0 | 0) that were decoded
+// straight into a caller's slot | through scratch.
+int flate_hip_debug_index_parts(flate_hip_handle h, uint64_t counts[2]) {
+    if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
+    counts[0] = h->dbg_index_direct;
+    counts[1] = h->dbg_index_scratch;
     return FLATE_HIP_OK;
 }
 

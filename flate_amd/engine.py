@@ -294,6 +294,13 @@ class Engine:
         self._check(self._L.flate_hip_debug_index_passes(self._h, C.addressof(v)), "flate_hip_debug_index_passes")
         return int(v.value)
 
+    def index_parts(self):
+        """(parts decoded straight into a slot, parts decoded through scratch) of the last decompress_ranges call on a
+        fresh index (flate_hip_debug_index_parts)"""
+        v = np.zeros(2, dtype=np.uint64)
+        self._check(self._L.flate_hip_debug_index_parts(self._h, v.ctypes.data), "flate_hip_debug_index_parts")
+        return int(v[0]), int(v[1])
+
     def member_paths(self):
         """How the last decompress_members call found its members: (streams by the scan for candidates, streams walked,
         candidates probed that lie on no chain) (flate_hip_debug_member_paths)."""
@@ -436,16 +443,18 @@ class Engine:
     def joined_bound(self, n, piece=65535, container=0, mode=6):
         return int(self._L.flate_hip_joined_bound(int(n), int(piece), container, mode))
 
-    def compress_joined(self, streams, container, mode, piece=65535, caps=None):
+    def compress_joined(self, streams, container, mode, piece=65535, caps=None, index_spacing=None):
         """Every input as ONE gzip / zlib / raw stream of independent pieces of `piece` bytes (flate_hip_compress_joined;
         levels 4..9, piece 1..65535): the pieces are compressed with no history at the rate of the chunk path and joined
         with sync-flush markers, one header and one footer around them -- any inflater reads the result.  caps: slot
-        size per stream (default: joined_bound).  Returns (list of bytes, list of status codes)."""
+        size per stream (default: joined_bound).  Returns (list of bytes, list of status codes).  index_spacing (a
+        number of bytes; 0: 1 MiB): flate_hip_compress_joined_indexed runs, and the handle of the fresh seek index over
+        the streams is returned as a third value, to be given to index_destroy (or to an Index)."""
         self._sync_env()
         if not 1 <= int(piece) <= _capi.JOIN_MAX_PIECE:
             raise ValueError("piece must be 1..%d" % _capi.JOIN_MAX_PIECE)
         n = len(streams)
-        if n == 0:
+        if n == 0 and index_spacing is None:
             return [], []
         blob, in_off = self._host_input(streams)
         if caps is None:
@@ -456,12 +465,21 @@ class Engine:
         out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
         out_len = np.zeros(n, dtype=np.uint64)
         status = np.zeros(n, dtype=np.int32)
-        rc = self._L.flate_hip_compress_joined(self._h, blob.ctypes.data, in_off.ctypes.data, n, int(piece), container, mode,
-                                               out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
-                                               status.ctypes.data, MEM_HOST)
-        self._check(rc, "flate_hip_compress_joined")
+        ix = C.c_void_p()
+        if index_spacing is None:
+            rc = self._L.flate_hip_compress_joined(self._h, blob.ctypes.data, in_off.ctypes.data, n, int(piece), container, mode,
+                                                   out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                                   status.ctypes.data, MEM_HOST)
+            self._check(rc, "flate_hip_compress_joined")
+        else:
+            rc = self._L.flate_hip_compress_joined_indexed(self._h, blob.ctypes.data, in_off.ctypes.data, n, int(piece), container,
+                                                           mode, out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                                           status.ctypes.data, MEM_HOST, int(index_spacing), C.byref(ix))
+            self._check(rc, "flate_hip_compress_joined_indexed")
         res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
-        return res, [int(s) for s in status]
+        if index_spacing is None:
+            return res, [int(s) for s in status]
+        return res, [int(s) for s in status], ix
 
     # ---- device buffers (raw pointers; everything already in HBM) ----
     def compress_joined_device(self, in_ptr, in_off_ptr, n_streams, piece, container, mode, out_ptr, out_off_ptr,
@@ -470,6 +488,18 @@ class Engine:
         rc = self._L.flate_hip_compress_joined(self._h, in_ptr, in_off_ptr, n_streams, int(piece), container, mode, out_ptr,
                                                out_off_ptr, out_len_ptr, status_ptr, MEM_DEVICE)
         self._check(rc, "flate_hip_compress_joined")
+
+    def compress_joined_indexed_device(self, in_ptr, in_off_ptr, n_streams, piece, container, mode, out_ptr, out_off_ptr,
+                                       out_len_ptr, status_ptr, spacing=0, memkind=MEM_DEVICE):
+        """flate_hip_compress_joined_indexed on raw pointers; returns the handle of the fresh index, to be given to
+        index_destroy.  The host waits for the stream."""
+        self._sync_env()
+        ix = C.c_void_p()
+        rc = self._L.flate_hip_compress_joined_indexed(self._h, in_ptr, in_off_ptr, n_streams, int(piece), container, mode,
+                                                       out_ptr, out_off_ptr, out_len_ptr, status_ptr, memkind, int(spacing),
+                                                       C.byref(ix))
+        self._check(rc, "flate_hip_compress_joined_indexed")
+        return ix
 
     def compress_device(self, in_ptr, in_off_ptr, n_chunks, container, mode, out_ptr, out_off_ptr, out_len_ptr,
                         status_ptr):

@@ -162,6 +162,28 @@ class Engine {
             return members;
         }
     }
+    // `in` as ONE stream of independent pieces (level 4..9; piece 1..65535, 0 = 65535) into `out`, with a fresh seek index
+    // over it (flate_hip_compress_joined_indexed; spacing 0 = 1 MiB): its points are piece starts and carry no windows.
+    // The caller hands the index to read_range with out's bytes and to index_destroy when done.
+    flate_hip_index_t compress_joined_indexed(const uint8_t* in, size_t n, int container, int level, uint32_t piece, uint64_t spacing,
+                                              std::vector<uint8_t>& out) {
+        const size_t cap = flate_hip_joined_bound(n, piece, container, level);
+        const uint64_t in_off[2] = {0, n}, out_off[2] = {0, cap};
+        out.resize(cap + 8);
+        uint64_t out_len = 0;
+        int32_t status = 0;
+        flate_hip_index_t ix = nullptr;
+        const uint8_t dummy = 0;
+        const int rc = flate_hip_compress_joined_indexed(h_, n ? in : &dummy, in_off, 1, piece, container, level, out.data(), out_off,
+                                                         &out_len, &status, FLATE_HIP_MEM_HOST, spacing, &ix);
+        if (rc != FLATE_HIP_OK) throw Error(rc, std::string("flate_hip_compress_joined_indexed: ") + flate_hip_last_error(h_));
+        if (status) {
+            flate_hip_index_destroy(h_, ix);
+            throw Error(status);
+        }
+        out.resize(out_len);
+        return ix;
+    }
     // decode `in` into `out` and keep a seek index over it (flate_hip_index_build; spacing 0 = 1 MiB); the caller hands
     // the index to read_range with the same bytes and to index_destroy when done
     flate_hip_index_t build_index(const uint8_t* in, size_t n, int container, uint64_t spacing, std::vector<uint8_t>& out) {

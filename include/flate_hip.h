@@ -446,6 +446,45 @@ int flate_hip_decompress_members(flate_hip_handle h, const uint8_t* in, const ui
  * first point at or behind its end; a stream without a range costs nothing), and the results come home packed.
  * range_stream[j] >= n_streams gives FLATE_HIP_E_INVALID_ARG; n_ranges == 0 returns FLATE_HIP_OK.
  *
+ * flate_hip_compress_joined_indexed: the first twelve arguments, the bytes written, out_len, status and the error
+ * returns are exactly those of flate_hip_compress_joined -- it is that code which runs -- and *idx gets a FRESH index of
+ * the streams just written.  A fresh point is the start of a piece: a byte boundary, with no history in front of it, so
+ * a fresh point has an empty window, win_bytes is 0 and the index holds NO device memory: 24 bytes a point on the host.
+ * Stream i with status 0 (N bytes in pieces of `piece`): piece k is a candidate with out_pos = k * piece and in_bit =
+ * 8 * (the piece's first byte - the stream's first byte), the BFINAL bit of the piece's first block; which candidates
+ * are points is the rule above over the piece starts (piece 0; piece k >= 1 iff a grid line lies in ((k-1) * piece,
+ * k * piece]; spacing 1: every piece; 0: 1 MiB).  Its record holds in_len = out_len[i], size = N, status 0.  A stream
+ * whose status is not 0 (FLATE_HIP_ST_OUTPUT_TOO_SMALL, and 102 without FLATE_HIP_DEFLATE_REPAIR_Q1: a piece of it may
+ * not inflate to `piece` bytes) has no points and size 0, as a stream that failed in flate_hip_index_build.  An empty
+ * stream has point 0 and size 0.  The call WAITS ON THE HOST for the stream, whatever flate_hip_set_sync says: the
+ * places of the point pieces are collected on the device and read back (8 bytes a point, not a piece), and, device
+ * memory, out_len and status.  n_streams == 0 gives an empty index; idx == NULL is FLATE_HIP_E_INVALID_ARG; *idx is NULL
+ * whenever the return value is not FLATE_HIP_OK.  An error behind the compress -- a failed HIP call of the read-back, or
+ * FLATE_HIP_E_UNSUPPORTED for a stream longer than any decompress call takes (0xfffffff0 bytes) -- leaves out, out_len
+ * and status as flate_hip_compress_joined wrote them, valid, and no index.
+ * destroy, stream_info, points, export_size, export and import mean on a fresh index what they mean on a windowed one;
+ * its blob is version 2 (version 1's header and records, no windows), and import picks the parser by the
+ * version field.
+ *
+ * flate_hip_decompress_ranges ON A FRESH INDEX: the clipped range is cut into PARTS at the points: for every point k
+ * from the last with out_pos <= begin to the last with out_pos <= begin + L' - 1 the part is [max(begin, pos_k),
+ * min(begin + L', pos_k+1 or size)).  Every part is decoded by a wave of its own, with no history.  A part that starts
+ * at its point and ends at the next point or at the stream's size is DIRECT: it is decoded straight into the slot, at
+ * pos_k - begin, with room for exactly its length; no wave stores outside its own part.  Any other part -- per range
+ * at most the first and the last -- goes through scratch (skip + len + 258 bytes) and is copied to the slot.  Passes are
+ * cut over the parts' scratch (a direct part costs none); flate_hip_debug_index_parts counts the direct and the scratch
+ * parts of the last call.  status[j] is the first non-zero status among the range's parts in stream order, else 0;
+ * out_len[j] is L' when the status is 0, else 0.  THE CONTRACT DIFFERS FROM THE ONE ABOVE in one point: no byte outside
+ * the first L' bytes of a slot is written, but when status[j] is not 0 those L' bytes are unspecified -- other parts of
+ * the range may have landed.  (FLATE_HIP_ST_OUTPUT_TOO_SMALL and a failed stream still write nothing.)  The warning
+ * about the missing checksum stands.  The host waits as above; of a host caller's input the bytes from every part's
+ * point to the next point are staged.  More than 2^31 - 1 parts in a call give FLATE_HIP_E_UNSUPPORTED.
+ * On a windowed index the call runs exactly the code described further up.
+ *
+ * Not covered by the fresh index: indexes for joined streams written elsewhere (pigz -i, Z_FULL_FLUSH: finding
+ * window-free points while decoding is a later step); cutting ranges at the points of a windowed index; planned,
+ * sharded and dictionary calls; the resumable deflater; pieces that keep history.
+ *
  * Not covered: members behind the first of a concatenated stream (split it with flate_hip_decompress_members first);
  * building an index without decoding into caller memory; compressed windows; an index for the resumable inflater or for
  * streams with preset dictionaries; the sharded entry points and planned calls; the span path reading an index it is
@@ -467,6 +506,10 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
                                 uint32_t n_streams, uint32_t n_ranges, const uint32_t* range_stream,
                                 const uint64_t* range_begin, const uint64_t* range_len, uint8_t* out, const uint64_t* out_off,
                                 uint64_t* out_len, int32_t* status, int memkind);
+int flate_hip_compress_joined_indexed(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
+                                      uint32_t piece_bytes, int container, int mode, uint8_t* out, const uint64_t* out_off,
+                                      uint64_t* out_len, int32_t* status, int memkind, uint64_t spacing, flate_hip_index_t* idx);
+int flate_hip_debug_index_parts(flate_hip_handle h, uint64_t counts[2]); /* last ranges call: parts decoded straight into a slot | through scratch */
 int flate_hip_debug_index_passes(flate_hip_handle h, uint64_t* passes);
 int flate_hip_debug_index_paths(flate_hip_handle h, uint64_t counts[2]);
 
