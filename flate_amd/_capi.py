@@ -52,6 +52,7 @@ SYMBOLS = [
     "flate_hip_index_export_size", "flate_hip_index_export", "flate_hip_index_import", "flate_hip_decompress_ranges",
     "flate_hip_debug_index_passes", "flate_hip_debug_index_paths",
     "flate_hip_compress_joined_indexed", "flate_hip_debug_index_parts",
+    "flate_hip_index_scan",
 ]
 
 
@@ -215,6 +216,9 @@ def lib():
     L.flate_hip_compress_joined_indexed.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, u64p, u64p, i32p,
                                                     C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
     L.flate_hip_compress_joined_indexed.restype = C.c_int
+    L.flate_hip_index_scan.argtypes = [vp, vp, u64p, C.c_uint32, C.c_int, C.c_int, u64p, i32p, u64p, C.c_int, C.c_uint64,
+                                       C.POINTER(C.c_void_p)]
+    L.flate_hip_index_scan.restype = C.c_int
     L.flate_hip_debug_index_parts.argtypes = [vp, u64p]
     L.flate_hip_debug_index_parts.restype = C.c_int
     L.flate_hip_debug_tokens.argtypes = [vp, C.c_uint32, vp, C.c_uint64]

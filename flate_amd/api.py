@@ -701,6 +701,18 @@ class ContainerModule:
         raise_for_status(st[0])
         return StreamIndex(ix)
 
+    def scan_index(self, data, spacing=None, engine=None):
+        """A window-free seek index over the first member of `data` (bytes-like, or a reader that is read to its end),
+        made without decoding it (flate_hip_index_scan): a stream written with full flushes (pigz -i, Z_FULL_FLUSH) has a
+        point at every flush the spacing rule keeps (default 1 MiB) behind which no match reaches in front of it; any
+        other stream has point 0 alone.  The footer is not compared.  Raises the stream's error if the size probe
+        reports one."""
+        eng = engine or default_engine()
+        data = _read_all(data)
+        ix, _, st, _ = eng.scan_index([data], self._container, 0, spacing)
+        raise_for_status(st[0])
+        return StreamIndex(ix)
+
     def index_from_bytes(self, blob, data, engine=None):
         """the StreamIndex of StreamIndex.to_bytes() and the stream it was built from"""
         return StreamIndex.from_bytes(blob, data, engine)

@@ -23,12 +23,14 @@
 #include "dict_compress_plan.h"
 #include "index_parts_plan.h"
 #include "index_plan.h"
+#include "index_scan_plan.h"
 #include "inflate_plan.h"
 #include "join_plan.h"
 #include "kernels_deflater.h"
 #include "kernels_dict.h"
 #include "kernels_index.h"
 #include "kernels_index_parts.h"
+#include "kernels_index_scan.h"
 #include "kernels_inflate.h"
 #include "kernels_inflate_par.h"
 #include "kernels_inflate_size.h"
@@ -89,6 +91,7 @@ enum KernelId {
     K_JOIN_POINTS,
     K_INFLATE_PART,
     K_RANGE_SETTLE,
+    K_INDEX_SCAN,
     K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_checksum", "k_lz_sort", "k_lz_match",
@@ -100,7 +103,7 @@ const char* const kKernelNames[K_COUNT] = {"memset_out", "k_byte_hist", "k_check
                                            "k_gather", "k_inflater", "k_deflater", "k_inflate_dict", "k_dict_stage",
                                            "k_join_open", "k_join_scan", "k_join_pack",
                                            "k_index_walk", "k_index_windows", "k_inflate_range", "k_range_pack",
-                                           "k_join_points", "k_inflate_part", "k_range_settle"};
+                                           "k_join_points", "k_inflate_part", "k_range_settle", "k_index_scan"};
 
 struct DevBuf {
     void* p = nullptr;
@@ -245,6 +248,7 @@ struct flate_hip_ctx {
     // ... on a fresh index (index_parts_plan.h): the part jobs, the parts' pack table, lengths and statuses, the ranges'
     // records and slots; for flate_hip_debug_index_parts the direct and scratch parts of the last ranges call
     DevBuf ix_pjobs, ix_ptab, ix_plen, ix_pstatus, ix_rrec, ix_rdst;
+    DevBuf ix_entries, ix_epack;  // flate_hip_index_scan: the walkers' lists as written and packed (jobs, records and the pack table lie in ix_jobs, ix_recs and ix_wtab)
     uint64_t dbg_index_direct = 0, dbg_index_scratch = 0;
     bool ws_fixed = false;   // the two-stream passes are being enqueued: ensure() may not grow a buffer (compress_impl)
     // last level 4..9 call, for the debug seam
@@ -968,6 +972,9 @@ int copy_out_host(flate_hip_ctx* h, const uint8_t* d_out, const uint64_t* d_outl
 int decompress_core(flate_hip_ctx* h, const uint8_t* in, const std::vector<uint64_t>& hin, uint32_t n_chunks, int container,
                     int flags, uint8_t* out, const std::vector<uint64_t>& hout, uint64_t* out_len, int32_t* status,
                     uint64_t* consumed, int memkind);
+struct SpanRecords;
+int sizes_impl(flate_hip_ctx* h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container, int flags,
+               uint64_t* sizes, int32_t* status, uint64_t* consumed, int memkind, SpanRecords* keep);
 
 // workspace of a chunk-path pass of nc chunks (levels 4..9)
 // (pass_plan.h: the bytes per chunk of every buffer)
@@ -1477,12 +1484,23 @@ int size_span_records(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, con
     return (int)nsp;
 }
 
-int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::vector<fl_chunk>& chunks, int container, int flags,
-                  uint64_t* d_sizes, int32_t* d_status, uint64_t* d_consumed) {
+// what size_span_records found, kept by a caller that walks the same streams behind the probe (flate_hip_index_scan)
+struct SpanRecords {
     std::vector<uint32_t> elig, sp_first;
     std::vector<fl_size_span> spans;
     std::vector<fl_size_rec> recs;
-    if (const int nsp = size_span_records(h, st, d_in, chunks, container, flags, elig, spans, sp_first, recs); nsp <= 0) return nsp;
+    int nsp = 0;
+};
+
+int size_by_spans(flate_hip_ctx* h, hipStream_t st, const uint8_t* d_in, std::vector<fl_chunk>& chunks, int container, int flags,
+                  uint64_t* d_sizes, int32_t* d_status, uint64_t* d_consumed, SpanRecords* keep = nullptr) {
+    SpanRecords own;
+    SpanRecords& sr = keep ? *keep : own;
+    std::vector<uint32_t>&elig = sr.elig, &sp_first = sr.sp_first;
+    std::vector<fl_size_span>& spans = sr.spans;
+    std::vector<fl_size_rec>& recs = sr.recs;
+    sr.nsp = size_span_records(h, st, d_in, chunks, container, flags, elig, spans, sp_first, recs);
+    if (sr.nsp <= 0) return sr.nsp;
     // ---- the chains
     std::vector<fl_span_fin> fin;
     for (size_t k = 0; k < elig.size(); k++) {
@@ -1590,7 +1608,7 @@ int flate_hip_destroy(flate_hip_handle h) {
                       &h->dcc_jobs, &h->dcc_chunks, &h->jn_scratch, &h->jn_streams, &h->jn_pstream, &h->jn_slot, &h->jn_len,
                       &h->jn_status, &h->jn_cks, &h->jn_dst, &h->jn_scks, &h->ix_jobs, &h->ix_recs, &h->ix_ptbit, &h->ix_ptpos, &h->ix_wtab,
                       &h->ix_rjobs, &h->ix_rtab, &h->ix_scratch, &h->jn_which, &h->jn_place, &h->ix_pjobs, &h->ix_ptab, &h->ix_plen,
-                      &h->ix_pstatus, &h->ix_rrec, &h->ix_rdst})
+                      &h->ix_pstatus, &h->ix_rrec, &h->ix_rdst, &h->ix_entries, &h->ix_epack})
         if (b->p) (void)hipFree(b->p);
     h->ws_bytes = 0;  // (every buffer ensure() grew is one of the above)
     for (hipEvent_t e : h->free_events) (void)hipEventDestroy(e);
@@ -2905,6 +2923,23 @@ extern "C" {
 int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks,
                                  int container, int flags, uint64_t* sizes, int32_t* status, uint64_t* consumed,
                                  int memkind) {
+    return sizes_impl(h, in, in_off, n_chunks, container, flags, sizes, status, consumed, memkind, nullptr);
+}
+
+int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]) {
+    if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
+    counts[0] = h->dbg_size_chain;
+    counts[1] = h->dbg_size_whole;
+    return FLATE_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// flate_hip_decompressed_sizes; keep: the span records of its long streams stay with the caller
+int sizes_impl(flate_hip_ctx* h, const uint8_t* in, const uint64_t* in_off, uint32_t n_chunks, int container, int flags,
+               uint64_t* sizes, int32_t* status, uint64_t* consumed, int memkind, SpanRecords* keep) {
     if (!h || !in_off || !sizes || !status) return FLATE_HIP_E_INVALID_ARG;
     if (container < 0 || container > 2) return FLATE_HIP_E_INVALID_ARG;
     if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
@@ -2923,7 +2958,7 @@ int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const ui
     if ((rc = upload_chunks(h, chunks))) return rc;
     h->dbg_size_chain = h->dbg_size_whole = 0;
     // A few long streams: each by many waves at once; what comes out whole is skipped below.
-    const int done = size_by_spans(h, st, f.d_in, chunks, container, flags, f.d_outlen, f.d_status, f.d_consumed);
+    const int done = size_by_spans(h, st, f.d_in, chunks, container, flags, f.d_outlen, f.d_status, f.d_consumed, keep);
     if (done < 0) {
         h->last_error = std::string("size probe by spans: ") + hipGetErrorString(hipGetLastError());
         return FLATE_HIP_E_LAUNCH;
@@ -2940,17 +2975,6 @@ int flate_hip_decompressed_sizes(flate_hip_handle h, const uint8_t* in, const ui
     if ((rc = results_home(f, sizes, status, consumed))) return rc;
     return wait_for_results(f);
 }
-
-int flate_hip_debug_size_paths(flate_hip_handle h, uint64_t counts[2]) {
-    if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
-    counts[0] = h->dbg_size_chain;
-    counts[1] = h->dbg_size_whole;
-    return FLATE_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
 
 // ---- flate_hip_decompress_members: the call's record and its stages (the rules: member_plan.h)
 struct MemberCall {
@@ -4270,39 +4294,42 @@ int index_alloc_windows(flate_hip_ctx* h, flate_hip_index* ix) {
     return FLATE_HIP_OK;
 }
 
-// The block starts of the streams the build found good, walked a wave per stream -- a long stream a wave per span of
-// the size probe's, where the spans' chain closes; else whole by one wave: always correct, only slow -- and the windows
-// copied out of the decoded bytes.  d_in / d_out:
-// the batch on the device, in_shift / out_shift what their offsets are less than the caller's.
-int index_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const uint8_t* d_out, const std::vector<uint64_t>& hin,
-               const std::vector<uint64_t>& hout, uint64_t in_shift, uint64_t out_shift, int container, int flags) {
+// The walk jobs of the good streams of a table (flate_hip_index_build, flate_hip_index_scan): a wave per stream -- a long
+// stream a wave per span of the size probe's, where the spans' chain closes; else whole by one wave: always correct, only
+// slow.  have: the span records of a size probe that has just run over the same batch (else the spans are counted here).  d_in: the batch on the device, in_shift what its offsets are less than the caller's.  A job has room for the
+// points fl_idx_max_points allows its bytes; jobs [job0[i], job0[i + 1]) are stream i's.
+int index_walk_jobs(flate_hip_ctx* h, const fl_idx_tab& t, const uint8_t* d_in, const std::vector<uint64_t>& hin, uint64_t in_shift,
+                    int container, int flags, std::vector<fl_idx_walk_job>& jobs, std::vector<uint32_t>& job0, uint64_t& cap_total,
+                    const SpanRecords* have = nullptr) {
     hipStream_t st = h->stream;
-    fl_idx_tab& t = ix->tab;
     const uint32_t n = (uint32_t)t.streams.size();
     int rc;
-    std::vector<fl_chunk> chunks;  // (the streams' lengths are hin's: flate_hip_index_build took them from it)
+    std::vector<fl_chunk> chunks;  // (the streams' lengths are hin's: the callers took them from it)
     if (!fl_inflate_chunks(hin.data(), nullptr, n, in_shift, 0, chunks)) return FLATE_HIP_E_INVALID_ARG;
     for (uint32_t i = 0; i < n; i++) chunks[i].skip = t.streams[i].status != 0;  // (not walked, and not cut below)
     if ((rc = upload_chunks(h, chunks))) return rc;
     // ---- long streams: the size probe's spans, and where their chain closes a walk per live span
     std::vector<std::vector<fl_idx_span_walk>> cut(n);
     {
-        std::vector<uint32_t> elig, sp_first;
-        std::vector<fl_size_span> spans;
-        std::vector<fl_size_rec> recs;
-        const int nsp = size_span_records(h, st, d_in, chunks, container, flags, elig, spans, sp_first, recs);
-        if (nsp < 0) {
-            h->last_error = std::string("index walk by spans: ") + hipGetErrorString(hipGetLastError());
-            return FLATE_HIP_E_LAUNCH;
+        SpanRecords own;
+        if (!have) {
+            own.nsp = size_span_records(h, st, d_in, chunks, container, flags, own.elig, own.spans, own.sp_first, own.recs);
+            if (own.nsp < 0) {
+                h->last_error = std::string("index walk by spans: ") + hipGetErrorString(hipGetLastError());
+                return FLATE_HIP_E_LAUNCH;
+            }
+            have = &own;
         }
-        for (size_t k = 0; nsp > 0 && k < elig.size(); k++) {
-            const uint32_t a = sp_first[k], b = sp_first[k + 1];
-            if (b - a >= 2) fl_idx_span_walks(spans.data() + a, recs.data() + a, b - a, t.streams[elig[k]].size, t.spacing, cut[elig[k]]);
+        // (records of a probe that looked at every stream: those of a stream that failed are passed over)
+        for (size_t k = 0; have->nsp > 0 && k < have->elig.size(); k++) {
+            const uint32_t a = have->sp_first[k], b = have->sp_first[k + 1], i = have->elig[k];
+            if (b - a >= 2 && t.streams[i].status == 0)
+                fl_idx_span_walks(have->spans.data() + a, have->recs.data() + a, b - a, t.streams[i].size, t.spacing, cut[i]);
         }
     }
-    std::vector<fl_idx_walk_job> jobs;
-    std::vector<uint32_t> job0(n + 1, 0);  // the jobs of stream i: [job0[i], job0[i + 1])
-    uint64_t cap_total = 0;
+    jobs.clear();
+    job0.assign(n + 1, 0);
+    cap_total = 0;
     h->dbg_index_spans = h->dbg_index_whole = 0;
     for (uint32_t i = 0; i < n; i++) {
         job0[i] = (uint32_t)jobs.size();
@@ -4323,6 +4350,22 @@ int index_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const
         }
     }
     job0[n] = (uint32_t)jobs.size();
+    return FLATE_HIP_OK;
+}
+
+// The block starts of the streams the build found good, walked by the jobs above, and the windows copied out of the
+// decoded bytes.  d_in / d_out:
+// the batch on the device, in_shift / out_shift what their offsets are less than the caller's.
+int index_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const uint8_t* d_out, const std::vector<uint64_t>& hin,
+               const std::vector<uint64_t>& hout, uint64_t in_shift, uint64_t out_shift, int container, int flags) {
+    hipStream_t st = h->stream;
+    fl_idx_tab& t = ix->tab;
+    const uint32_t n = (uint32_t)t.streams.size();
+    int rc;
+    std::vector<fl_idx_walk_job> jobs;
+    std::vector<uint32_t> job0;  // the jobs of stream i: [job0[i], job0[i + 1])
+    uint64_t cap_total = 0;
+    if ((rc = index_walk_jobs(h, t, d_in, hin, in_shift, container, flags, jobs, job0, cap_total))) return rc;
     const uint32_t nj = (uint32_t)jobs.size();
     if (!nj) return FLATE_HIP_OK;
     if ((rc = ensure(h, h->ix_jobs, sizeof(fl_idx_walk_job) * nj)) || (rc = ensure(h, h->ix_recs, sizeof(fl_idx_walk_rec) * nj)) ||
@@ -4397,6 +4440,99 @@ int index_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const
     }
     HIP_OK(h, hipGetLastError());
     HIP_OK(h, hipStreamSynchronize(st));  // (the tables are on this stack; the caller may reuse `out` at once)
+    return FLATE_HIP_OK;
+}
+
+// flate_hip_index_scan behind its probe (index_scan_plan.h, kernels_index_scan.h): the good streams are walked by the
+// jobs of index_walk, cut by the span records the probe has just read back (sr), and every stream's lists become its
+// points.  Nothing but the handle's workspace is written.  The lists come home as they are where there is little room
+// for them, else only what the walkers wrote, packed on the device behind a look at their records.
+int index_scan_walk(flate_hip_ctx* h, flate_hip_index* ix, const uint8_t* d_in, const std::vector<uint64_t>& hin, uint64_t in_shift,
+                    int container, int flags, const SpanRecords& sr) {
+    hipStream_t st = h->stream;
+    fl_idx_tab& t = ix->tab;
+    const uint32_t n = (uint32_t)t.streams.size();
+    int rc;
+    std::vector<fl_idx_walk_job> jobs;
+    std::vector<uint32_t> job0;
+    uint64_t cap_total = 0;
+    if ((rc = index_walk_jobs(h, t, d_in, hin, in_shift, container, flags, jobs, job0, cap_total, &sr))) return rc;
+    cap_total = 0;
+    for (fl_idx_walk_job& jb : jobs) {  // room for a walk's list, not for its points: by its cells and by its bits
+        const uint64_t from = jb.first ? 0 : jb.start_bit, to = jb.stop_bit == ~0ull ? t.streams[jb.stream].in_len * 8 : jb.stop_bit;
+        jb.cap = fl_ixs_walk_entries(jb.cap, to - from);
+        jb.point0 = cap_total;
+        cap_total += jb.cap;
+    }
+    const uint32_t nj = (uint32_t)jobs.size();
+    std::vector<fl_ixs_walk_rec> recs(nj);
+    std::vector<fl_ixs_entry> ent;
+    std::vector<uint64_t> at(nj, 0);  // where walk k's list begins in `ent`
+    if (nj) {
+        if ((rc = ensure(h, h->ix_jobs, sizeof(fl_idx_walk_job) * nj)) || (rc = ensure(h, h->ix_recs, sizeof(fl_ixs_walk_rec) * nj)) ||
+            (rc = ensure(h, h->ix_entries, sizeof(fl_ixs_entry) * cap_total)))
+            return rc;
+        HIP_OK(h, hipMemcpyAsync(h->ix_jobs.p, jobs.data(), sizeof(fl_idx_walk_job) * nj, hipMemcpyHostToDevice, st));
+        {
+            ProfScope ps(h, K_INDEX_SCAN);
+            hipLaunchKernelGGL(k_index_scan, dim3(nj), dim3(64), 0, st, d_in, (const fl_chunk*)h->chunks.p, container, flags, t.spacing,
+                               (const fl_idx_walk_job*)h->ix_jobs.p, (fl_ixs_walk_rec*)h->ix_recs.p, (fl_ixs_entry*)h->ix_entries.p);
+        }
+        HIP_OK(h, hipGetLastError());
+        HIP_OK(h, hipMemcpyAsync(recs.data(), h->ix_recs.p, sizeof(fl_ixs_walk_rec) * nj, hipMemcpyDeviceToHost, st));
+        const bool whole = cap_total <= FL_IXS_COPY_WHOLE;
+        if (whole) {
+            ent.resize(cap_total);
+            HIP_OK(h, hipMemcpyAsync(ent.data(), h->ix_entries.p, sizeof(fl_ixs_entry) * cap_total, hipMemcpyDeviceToHost, st));
+            for (uint32_t k = 0; k < nj; k++) at[k] = jobs[k].point0;
+        }
+        HIP_OK(h, hipStreamSynchronize(st));
+        if (!whole) {
+            std::vector<uint64_t> tab(3 * (size_t)nj);  // k_gather_copy's: source | length | destination, in bytes
+            uint64_t total = 0;
+            for (uint32_t k = 0; k < nj; k++) {
+                at[k] = total;
+                tab[k] = sizeof(fl_ixs_entry) * jobs[k].point0;
+                tab[nj + k] = sizeof(fl_ixs_entry) * std::min(recs[k].n_entries, jobs[k].cap);
+                tab[2 * (size_t)nj + k] = sizeof(fl_ixs_entry) * total;
+                total += std::min(recs[k].n_entries, jobs[k].cap);
+            }
+            ent.resize(total);
+            if (total) {
+                if ((rc = ensure(h, h->ix_wtab, sizeof(uint64_t) * 3 * nj)) || (rc = ensure(h, h->ix_epack, sizeof(fl_ixs_entry) * total))) return rc;
+                HIP_OK(h, hipMemcpyAsync(h->ix_wtab.p, tab.data(), sizeof(uint64_t) * 3 * nj, hipMemcpyHostToDevice, st));
+                const uint64_t* w = (const uint64_t*)h->ix_wtab.p;
+                {
+                    ProfScope ps(h, K_GATHER);
+                    hipLaunchKernelGGL(k_gather_copy, gather_grid(nj), dim3(256), 0, st, (const uint8_t*)h->ix_entries.p, w, w + nj,
+                                       (uint8_t*)h->ix_epack.p, w + 2 * (size_t)nj);
+                }
+                HIP_OK(h, hipGetLastError());
+                HIP_OK(h, hipMemcpyAsync(ent.data(), h->ix_epack.p, sizeof(fl_ixs_entry) * total, hipMemcpyDeviceToHost, st));
+                HIP_OK(h, hipStreamSynchronize(st));  // (the table is on this stack)
+            }
+        }
+    }
+    std::vector<fl_ixs_walk> walks;
+    for (uint32_t i = 0; i < n; i++) {
+        fl_idx_stream& s = t.streams[i];
+        s.point0 = t.points.size();
+        s.n_points = 0;
+        if (job0[i] == job0[i + 1]) continue;
+        walks.clear();
+        bool good = true;
+        for (uint32_t k = job0[i]; k < job0[i + 1] && good; k++) {
+            const fl_idx_walk_job& jb = jobs[k];
+            const fl_ixs_walk_rec& r = recs[k];
+            good = r.status == 0 && r.n_entries <= jb.cap && (r.final_seen != 0) == (k + 1 == job0[i + 1]);
+            walks.push_back(fl_ixs_walk{ent.data() + at[k], r.n_entries, r.out_len, r.last_mark, r.has_mark, jb.first});
+        }
+        if (!good || !fl_ixs_points(walks.data(), walks.size(), s.size, t.spacing, t.points)) {
+            h->last_error = "index scan of stream " + std::to_string(i) + " disagrees with its probe";
+            return FLATE_HIP_E_LAUNCH;
+        }
+        s.n_points = t.points.size() - s.point0;
+    }
     return FLATE_HIP_OK;
 }
 
@@ -4604,6 +4740,54 @@ int flate_hip_index_build(flate_hip_handle h, const uint8_t* in, const uint64_t*
     return FLATE_HIP_OK;
 }
 
+// flate_hip_decompressed_sizes, then the scan walk over the streams it found good.  The host waits as that call does, then
+// for the offsets, sizes and status (device memory), for the walkers' records, and for their lists.
+int flate_hip_index_scan(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams, int container, int flags,
+                         uint64_t* sizes, int32_t* status, uint64_t* consumed, int memkind, uint64_t spacing, flate_hip_index_t* idx) {
+    if (!idx) return FLATE_HIP_E_INVALID_ARG;
+    *idx = nullptr;
+    if (!h || !in_off || !sizes || !status) return FLATE_HIP_E_INVALID_ARG;
+    if (!fl_idx_args_ok(container, memkind)) return FLATE_HIP_E_INVALID_ARG;
+    int rc;
+    std::vector<uint64_t> hin(1, 0), hsize;
+    std::vector<int32_t> hst;
+    SpanRecords sr;
+    if (n_streams) {
+        if ((rc = sizes_impl(h, in, in_off, n_streams, container, flags, sizes, status, consumed, memkind, &sr))) return rc;
+        if ((rc = fetch_offsets(h, in_off, n_streams, memkind, hin)) || (rc = fetch_array(h, sizes, n_streams, memkind, hsize)) ||
+            (rc = fetch_array(h, status, n_streams, memkind, hst)))
+            return rc;
+        for (uint32_t i = 0; i < n_streams; i++)
+            if (hin[i + 1] - hin[i] > FL_IDX_MAX_IN_LEN) {  // (no decompress call takes such a stream)
+                h->last_error = "stream " + std::to_string(i) + " is too long for a seek index";
+                return FLATE_HIP_E_UNSUPPORTED;
+            }
+    }
+    flate_hip_index* ix = new flate_hip_index();
+    ix->fresh = true;
+    ix->tab.container = (uint32_t)container;
+    ix->tab.spacing = fl_idx_spacing(spacing);
+    ix->tab.streams.resize(n_streams);
+    for (uint32_t i = 0; i < n_streams; i++) {
+        fl_idx_stream& s = ix->tab.streams[i];
+        s.in_len = hin[i + 1] - hin[i];
+        s.status = hst[i];
+        s.size = hst[i] == 0 ? hsize[i] : 0;
+        s.point0 = s.n_points = 0;
+    }
+    if (n_streams) {
+        // a host caller's batch is still where flate_hip_decompressed_sizes staged it
+        const bool host = memkind == FLATE_HIP_MEM_HOST;
+        rc = index_scan_walk(h, ix, host ? (const uint8_t*)h->st_in.p : in, hin, host ? hin[0] : 0, container, flags, sr);
+        if (rc) {
+            delete ix;
+            return rc;
+        }
+    }
+    *idx = ix;
+    return FLATE_HIP_OK;
+}
+
 int flate_hip_index_destroy(flate_hip_handle h, flate_hip_index_t idx) {
     if (!h || !idx) return FLATE_HIP_E_INVALID_ARG;
     (void)hipSetDevice(h->device);
@@ -4799,7 +4983,7 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
     return total ? copy_out_packed(h, f.d_out, ddst, f.d_outlen, n_ranges, hout, f.out_shift, out, out_len, total) : FLATE_HIP_OK;
 }
 
-// Debug / test seam: the good streams of the last flate_hip_index_build call that were walked span by span / whole by one wave.
+// Debug / test seam: the good streams of the last flate_hip_index_build or flate_hip_index_scan call that were walked span by span / whole by one wave.
 int flate_hip_debug_index_paths(flate_hip_handle h, uint64_t counts[2]) {
     if (!h || !counts) return FLATE_HIP_E_INVALID_ARG;
     counts[0] = h->dbg_index_spans;

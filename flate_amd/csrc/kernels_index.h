@@ -54,6 +54,7 @@ struct fl_idx_emit {
             n++;
         }
     }
+    __device__ __forceinline__ void stored_block(uint64_t, uint32_t) {}
 };
 
 // One wave per walk job.  The loop is the span instance of the size probe's (a whole stream is the span from its first

@@ -120,10 +120,12 @@ __device__ __forceinline__ int fl_sz_dynamic(fl_bitr& r, FL_LDS fl_inflate_ws16*
 // status; cnt has the bytes, end_bit / final_seen what a span's record wants.  k_inflate_size counts one member with it,
 // k_member_walk (kernels_members.h) one after the other.  HOOK is told every block start and the bytes counted in front
 // of it (a span's stop included): the index walker's point emitter (kernels_index.h); the two kernels above tell nobody
-// and compile as they did without it.
+// and compile as they did without it.  It is also told every stored block that ended well, with its LEN and BFINAL: the
+// index scanner (kernels_index_scan.h) knows a flush marker by them.
 struct fl_sz_no_hook {
     enum { ON = 0 };
     __device__ __forceinline__ void block_start(uint64_t, uint64_t) {}
+    __device__ __forceinline__ void stored_block(uint64_t, uint32_t) {}
 };
 template <bool SPAN, class HOOK = fl_sz_no_hook>
 __device__ __forceinline__ int fl_sz_member(fl_bitr& r, FL_LDS fl_inflate_ws16* ws, int container, int flags, uint32_t lane,
@@ -145,7 +147,9 @@ __device__ __forceinline__ int fl_sz_member(fl_bitr& r, FL_LDS fl_inflate_ws16* 
             if ((rc = (int)fl_uni((uint32_t)fl_inf_dynamic_header(r, ws, flags, lane)))) break;
             rc = (int)fl_uni((uint32_t)fl_sz_dynamic<SPAN>(r, ws, cnt, lane));
         } else if (btype == 0) {
+            const uint64_t n0 = HOOK::ON ? cnt.n : 0;
             rc = (int)fl_uni((uint32_t)fl_sz_stored<SPAN>(r, cnt));
+            if (HOOK::ON && rc == 0) hook->stored_block(cnt.n - n0, bfinal);
         } else if (btype == 1) {
             rc = (int)fl_uni((uint32_t)fl_inf_fixed(r, cnt, lane));
         } else {

@@ -219,6 +219,25 @@ class Engine:
         res = [out[int(out_off[i]): int(out_off[i]) + int(out_len[i])].tobytes() for i in range(n)]
         return Index(self, ix, blob, in_off, n), res, [int(s) for s in status[:n]], [int(c) for c in consumed[:n]]
 
+    def scan_index(self, streams, container=0, flags=0, spacing=None):
+        """A fresh seek index over streams written elsewhere, found without decoding them (flate_hip_index_scan): the size
+        probe runs, then every good stream is walked for its flush markers -- a point is block 0 or a marker-following
+        block start that the spacing rule keeps (default 1 MiB) and behind which no match reaches in front of it.
+        Returns (Index, list of sizes, list of status codes, list of consumed input bytes), the last three as
+        decompressed_sizes gives them; a stream whose status is not 0 has no points."""
+        self._sync_env()
+        n = len(streams)
+        blob, in_off = self._host_input(streams)
+        sizes = np.zeros(max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        consumed = np.zeros(max(n, 1), dtype=np.uint64)
+        ix = C.c_void_p()
+        rc = self._L.flate_hip_index_scan(self._h, blob.ctypes.data, in_off.ctypes.data, n, container, flags, sizes.ctypes.data,
+                                          status.ctypes.data, consumed.ctypes.data, MEM_HOST, int(spacing or 0), C.byref(ix))
+        self._check(rc, "flate_hip_index_scan")
+        return (Index(self, ix, blob, in_off, n), [int(x) for x in sizes[:n]], [int(s) for s in status[:n]],
+                [int(c) for c in consumed[:n]])
+
     def index_from_bytes(self, blob, streams):
         """An Index from what Index.to_bytes() returned and the streams it was built from (flate_hip_index_import): the blob
         is validated, the streams only by their lengths -- nothing tells bytes that have changed but still decode."""
@@ -238,6 +257,17 @@ class Engine:
         rc = self._L.flate_hip_index_build(self._h, in_ptr, in_off_ptr, n_streams, container, flags, out_ptr, out_off_ptr,
                                            out_len_ptr, status_ptr, consumed_ptr, memkind, int(spacing), C.byref(ix))
         self._check(rc, "flate_hip_index_build")
+        return ix
+
+    def scan_index_device(self, in_ptr, in_off_ptr, n_streams, container, flags, sizes_ptr, status_ptr, consumed_ptr=None,
+                          spacing=0, memkind=MEM_DEVICE):
+        """flate_hip_index_scan on raw pointers (device memory unless memkind says otherwise); returns the handle of the
+        fresh index for index_* / decompress_ranges_device, to be given to index_destroy.  The host waits for the stream."""
+        self._sync_env()
+        ix = C.c_void_p()
+        rc = self._L.flate_hip_index_scan(self._h, in_ptr, in_off_ptr, n_streams, container, flags, sizes_ptr, status_ptr,
+                                          consumed_ptr, memkind, int(spacing), C.byref(ix))
+        self._check(rc, "flate_hip_index_scan")
         return ix
 
     def index_destroy(self, ix):
@@ -283,7 +313,8 @@ class Engine:
                                                    memkind)
 
     def index_paths(self):
-        """(good streams of the last index build walked span by span, walked whole by one wave) (flate_hip_debug_index_paths)"""
+        """(good streams of the last index build or scan walked span by span, walked whole by one wave)
+        (flate_hip_debug_index_paths)"""
         v = np.zeros(2, dtype=np.uint64)
         self._check(self._L.flate_hip_debug_index_paths(self._h, v.ctypes.data), "flate_hip_debug_index_paths")
         return int(v[0]), int(v[1])

@@ -209,6 +209,25 @@ class Engine {
             return ix;
         }
     }
+    // a fresh seek index over `in`, a stream written elsewhere with full flushes, made without decoding it
+    // (flate_hip_index_scan; spacing 0 = 1 MiB): its points are block 0 and the flush points behind which no match reaches
+    // in front of them; the footer is not compared.  The caller hands the index to read_range with the same bytes and to
+    // index_destroy when done
+    flate_hip_index_t scan_index(const uint8_t* in, size_t n, int container, uint64_t spacing) {
+        const uint64_t in_off[2] = {0, n};
+        uint64_t size = 0;
+        int32_t status = 0;
+        const uint8_t dummy = 0;
+        flate_hip_index_t ix = nullptr;
+        const int rc = flate_hip_index_scan(h_, n ? in : &dummy, in_off, 1, container, 0, &size, &status, nullptr, FLATE_HIP_MEM_HOST,
+                                            spacing, &ix);
+        if (rc != FLATE_HIP_OK) throw Error(rc, std::string("flate_hip_index_scan: ") + flate_hip_last_error(h_));
+        if (status) {
+            flate_hip_index_destroy(h_, ix);
+            throw Error(status);
+        }
+        return ix;
+    }
     // bytes [begin, begin + len) of what `in` inflates to, clipped to its size (flate_hip_decompress_ranges)
     std::vector<uint8_t> read_range(flate_hip_index_t ix, const uint8_t* in, size_t n, uint64_t begin, uint64_t len) {
         uint64_t size = 0;

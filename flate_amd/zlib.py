@@ -11,6 +11,7 @@ decompressor = _m.decompressor
 Decompressor = _m.Decompressor
 decompress_members = _m.decompress_members
 build_index = _m.build_index
+scan_index = _m.scan_index
 index_from_bytes = _m.index_from_bytes
 huffman = _m.huffman
 store = _m.store

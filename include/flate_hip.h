@@ -481,14 +481,44 @@ int flate_hip_decompress_members(flate_hip_handle h, const uint8_t* in, const ui
  * point to the next point are staged.  More than 2^31 - 1 parts in a call give FLATE_HIP_E_UNSUPPORTED.
  * On a windowed index the call runs exactly the code described further up.
  *
- * Not covered by the fresh index: indexes for joined streams written elsewhere (pigz -i, Z_FULL_FLUSH: finding
- * window-free points while decoding is a later step); cutting ranges at the points of a windowed index; planned,
- * sharded and dictionary calls; the resumable deflater; pieces that keep history.
+ * flate_hip_index_scan: a FRESH index over streams written elsewhere (pigz -i, zlib with Z_FULL_FLUSH), found by walking
+ * the streams: nothing is decoded into memory and there is no output buffer.  The first ten arguments are those of
+ * flate_hip_decompressed_sizes, and sizes, status and consumed get exactly what that call writes for them -- it is that
+ * call which runs first, spans and all: the footer is read but not compared (the statuses decompress gives a wrong
+ * CRC-32, Adler-32 or ISIZE read 0 here, and such a stream is indexed), FLATE_HIP_ST_INVALID_MATCH is exact, and nothing
+ * is written anywhere else.  Then every stream whose status is 0 is walked once more for its points:
+ *   A MARK is a block start whose preceding block is a stored block with LEN 0 and BFINAL 0, the trailer of a sync or
+ *   full flush; it lies on a byte boundary.  With pos[0] = 0 for block 0 and the positions of the marks behind it in
+ *   stream order, the rule above (S = spacing; 0 means 1 MiB) says which marks are KEPT -- as it does for the piece
+ *   starts of flate_hip_compress_joined_indexed.  A kept mark at output position c is FRESH iff no match at a position
+ *   p >= c has p - distance < c.  The points are block 0 and the fresh kept marks.  A kept mark that is not fresh is
+ *   DROPPED, NOT REPLACED: where the kept mark of a cell is a sync flush, the cell's later full flush is not looked for
+ *   (spacing 1 keeps every mark that moves forward).  A stream without fresh marks has point 0 alone; a stream whose
+ *   status is not 0 has no points and size 0.
+ * *idx is of the kind flate_hip_compress_joined_indexed returns: no windows, no device memory, 24 bytes a point on the
+ * host, a version-2 blob; destroy, stream_info, points, export_size, export, import and flate_hip_decompress_ranges (the
+ * parts path) take it as they take that one.  Short streams are walked by a wave each, long streams a wave per live span
+ * where the probe's chain closes (the span records the probe has just read are used: the spans are not counted a second
+ * time; flate_hip_debug_index_paths counts the streams of the last scan that went either way), else whole by one wave.
+ * The call WAITS ON THE HOST as flate_hip_decompressed_sizes does, whatever flate_hip_set_sync says, then for the
+ * offsets, sizes and status (device memory), for the walkers' records, and -- where the lists have room for more than
+ * 4096 entries, behind a kernel that packs what was written -- for the walkers' lists; a host caller's batch is read
+ * where the probe staged it.  The workspace holds, besides the probe's, 24 bytes per possible mark: per walk its
+ * start, its first mark and 1 + out_len / S marks in cells of their own, but no more marks than its input has room for
+ * markers (one per 32 bits); and the packed copy of what was written.
+ * n_streams == 0 gives an empty index; idx == NULL is FLATE_HIP_E_INVALID_ARG; other argument errors as for the probe;
+ * *idx is NULL whenever the return value is not FLATE_HIP_OK.  An error behind the probe -- no memory for the walk, a
+ * failed HIP call, FLATE_HIP_E_UNSUPPORTED for a stream longer than 0xfffffff0 bytes, or FLATE_HIP_E_LAUNCH with
+ * "disagrees with its probe" in flate_hip_last_error when a walk contradicts the size the probe counted (not seen; it
+ * would be a fault of the library) -- leaves sizes, status and consumed as the probe wrote them, valid, and no index.
+ *
+ * Not covered by the fresh index: replacing a dropped kept mark by a later fresh one in its cell; fresh points at block
+ * starts that follow no marker; an index with some points windowed and some fresh; cutting ranges at the points of a
+ * windowed index; planned, sharded and dictionary calls; the resumable deflater; pieces that keep history.
  *
  * Not covered: members behind the first of a concatenated stream (split it with flate_hip_decompress_members first);
- * building an index without decoding into caller memory; compressed windows; an index for the resumable inflater or for
- * streams with preset dictionaries; the sharded entry points and planned calls; the span path reading an index it is
- * handed.
+ * compressed windows; an index for the resumable inflater or for streams with preset dictionaries; the sharded entry
+ * points and planned calls; the span path reading an index it is handed.
  */
 typedef struct flate_hip_index* flate_hip_index_t;
 int flate_hip_index_build(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams, int container,
@@ -509,6 +539,9 @@ int flate_hip_decompress_ranges(flate_hip_handle h, flate_hip_index_t idx, const
 int flate_hip_compress_joined_indexed(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams,
                                       uint32_t piece_bytes, int container, int mode, uint8_t* out, const uint64_t* out_off,
                                       uint64_t* out_len, int32_t* status, int memkind, uint64_t spacing, flate_hip_index_t* idx);
+int flate_hip_index_scan(flate_hip_handle h, const uint8_t* in, const uint64_t* in_off, uint32_t n_streams, int container,
+                         int flags, uint64_t* sizes, int32_t* status, uint64_t* consumed, int memkind, uint64_t spacing,
+                         flate_hip_index_t* idx);
 int flate_hip_debug_index_parts(flate_hip_handle h, uint64_t counts[2]); /* last ranges call: parts decoded straight into a slot | through scratch */
 int flate_hip_debug_index_passes(flate_hip_handle h, uint64_t* passes);
 int flate_hip_debug_index_paths(flate_hip_handle h, uint64_t counts[2]);

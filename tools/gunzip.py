@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""gunzip [--piece N | --members | --index FILE [--range BEGIN:LEN]] <file>.gz: writes <file> with the MI355X engine -- the reference's bin/gunzip.zig:25-27
+"""gunzip [--piece N | --members | --index FILE [--range BEGIN:LEN] | --scan-index FILE [--spacing N]] <file>.gz: writes <file> with the MI355X engine -- the reference's bin/gunzip.zig:25-27
 (`gzip.decompress(br.reader(), output_file.writer())`; refuses names without the .gz suffix, :15-19).
 Concatenated members are decoded one after the other (Inflate.reset, inflate.zig:301-309).  With --piece N the file is
 read N bytes at a time and decoded by the resumable inflater: memory stays bounded whatever the file's size.  With
 --members the file is read whole and all its members are found and decoded in one GPU call (gzip.decompress_members).
 With --index FILE the first member is decoded and a seek index over it is written to FILE beside the normal output
 (gzip.build_index), or read from FILE when it exists; with --range BEGIN:LEN only those bytes of the output are decoded,
-from the index, and written to stdout."""
+from the index, and written to stdout.  With --scan-index FILE nothing is decoded and no output file is written: the first
+member is walked for its full-flush points (gzip.scan_index; pigz -i and Z_FULL_FLUSH leave such points, one is kept every
+N output bytes or so, default 1 MiB) and the window-free index is written to FILE, which --index FILE --range reads as it
+reads its own."""
 import os
 os.environ.setdefault("FLATE_HIP_PRELOAD_TORCH_HIP", "1")  # one HIP runtime per process: torch, imported later, brings its own (flate_amd/_capi.py)
 import sys
@@ -31,14 +34,25 @@ def main(argv=None):
                 argv = []
             else:
                 rng, argv = (int(b), int(n)), argv[2:]
+    scan = spacing = None
+    if len(argv) >= 3 and argv[0] == "--scan-index" and piece is None and not members and index is None:
+        scan, argv = argv[1], argv[2:]
+        if len(argv) == 3 and argv[0] == "--spacing":
+            if argv[1].isdigit() and int(argv[1]) > 0:
+                spacing, argv = int(argv[1]), argv[2:]
+            else:
+                argv = []
     if len(argv) != 1:
-        print("usage: gunzip.py [--piece N | --members | --index FILE [--range BEGIN:LEN]] <file>.gz", file=sys.stderr)
+        print("usage: gunzip.py [--piece N | --members | --index FILE [--range BEGIN:LEN] | --scan-index FILE [--spacing N]] <file>.gz",
+              file=sys.stderr)
         return 2
     name = argv[0]
     if not name.endswith(".gz"):
         print("not a .gz file", file=sys.stderr)
         return 1
     from flate_amd import gzip
+    if scan is not None:
+        return scan_index(gzip, name, scan, spacing)
     if index is not None and (rng is not None or not os.path.exists(index)):
         return with_index(gzip, name, index, rng)
     # (an index that is there already has nothing to give a full decode: the normal path below)
@@ -60,6 +74,17 @@ def main(argv=None):
         if os.path.exists(tmp_name):
             os.unlink(tmp_name)
         raise
+    return 0
+
+
+def scan_index(gzip, name, index, spacing):
+    """--scan-index: the index of the file's full-flush points, written to `index`; the file is not decoded"""
+    with open(name, "rb") as src:
+        ix = gzip.scan_index(src.read(), spacing)
+    with open(index + ".gunzip-tmp", "wb") as f:
+        f.write(ix.to_bytes())
+    os.replace(index + ".gunzip-tmp", index)
+    print("%d points over %d bytes" % (len(ix.points()), ix.size), file=sys.stderr)
     return 0
 
 

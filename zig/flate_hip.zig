@@ -21,6 +21,9 @@ pub extern "c" fn flate_hip_decompress_batch(h: Handle, in: [*]const u8, in_off:
 pub const Index = ?*anyopaque;
 /// flate_hip_compress_joined with a fresh seek index over the streams it wrote (piece starts, no windows)
 pub extern "c" fn flate_hip_compress_joined_indexed(h: Handle, in: [*]const u8, in_off: [*]const u64, n_streams: u32, piece_bytes: u32, container: c_int, mode: c_int, out: [*]u8, out_off: [*]const u64, out_len: [*]u64, status: [*]i32, memkind: c_int, spacing: u64, idx: *Index) c_int;
+/// a fresh seek index over streams written elsewhere, found by walking them: the first ten arguments are those of
+/// flate_hip_decompressed_sizes; points are block 0 and the fresh marker-following block starts the spacing rule keeps
+pub extern "c" fn flate_hip_index_scan(h: Handle, in: [*]const u8, in_off: [*]const u64, n_streams: u32, container: c_int, flags: c_int, sizes: [*]u64, status: [*]i32, consumed: ?[*]u64, memkind: c_int, spacing: u64, idx: *Index) c_int;
 
 /// inflate.zig:72-78, huffman_decoder.zig:35-40, container.zig:45-51, bit_reader.zig:29
 pub const Error = error{
