@@ -1134,7 +1134,49 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
 #else
 #define PZ_EARLY_EXIT
 #endif
-#define PZ_RSTEP(QC, QN, QNN, WC0, WC1, WN0, WN1, XC, XN, H)                  \
+// A vector compare writes ZERO for the lanes that are not active (tools/ubench/vopc_inactive.hip: also with an empty exec), so
+// vcc is a subset of exec behind either compare: the hits are OR-ed into H as they come, and the lanes that walk on are
+// vcc & ~borrow.  3 scalar instructions a step, not 5.
+// The test for "no lane walks any more" stands behind every PZ_EXIT_EVERY-th step (1, 2, 3 or 6): a step that no lane makes
+// changes nothing -- exec is empty, its compare writes vcc = 0 -- and its wait returns at once.  A burst that leaves through the
+// branch leaves with exec empty, so no walking lane ever sees an odd number of role swaps.  (Measured,
+// profiles/parse_burst_step.txt: 1 / 2 / 3 / 6 -> 23.2 / 22.9 / 23.0 / 23.1 ms a step; the parent's step 23.9.)
+#ifndef PZ_EXIT_EVERY
+#define PZ_EXIT_EVERY 2
+#endif
+#if PZ_EXIT_EVERY != 1 && PZ_EXIT_EVERY != 2 && PZ_EXIT_EVERY != 3 && PZ_EXIT_EVERY != 6
+#error PZ_EXIT_EVERY: 1, 2, 3 or 6
+#endif
+#define PZ_EXIT "s_cbranch_execz .Lpz_done_%=\n\t"
+#define PZ_STAY
+// (behind step 1 .. 6 of the six that are written out)
+#if PZ_EXIT_EVERY == 1
+#define PZ_X1 PZ_EXIT
+#define PZ_X2 PZ_EXIT
+#define PZ_X3 PZ_EXIT
+#define PZ_X4 PZ_EXIT
+#define PZ_X5 PZ_EXIT
+#elif PZ_EXIT_EVERY == 2
+#define PZ_X1 PZ_STAY
+#define PZ_X2 PZ_EXIT
+#define PZ_X3 PZ_STAY
+#define PZ_X4 PZ_EXIT
+#define PZ_X5 PZ_STAY
+#elif PZ_EXIT_EVERY == 3
+#define PZ_X1 PZ_STAY
+#define PZ_X2 PZ_STAY
+#define PZ_X3 PZ_EXIT
+#define PZ_X4 PZ_STAY
+#define PZ_X5 PZ_STAY
+#else
+#define PZ_X1 PZ_STAY
+#define PZ_X2 PZ_STAY
+#define PZ_X3 PZ_STAY
+#define PZ_X4 PZ_STAY
+#define PZ_X5 PZ_STAY
+#endif
+#define PZ_X6 PZ_EXIT
+#define PZ_RSTEP(QC, QN, QNN, WC0, WC1, WN0, WN1, XC, XN, H, EXIT)            \
     PZ_W1                                                                      \
     "v_lshl_add_u32 %[a1], %[" QN "], 1, %[prvb]\n\t"                          \
     "ds_read_u16 %[" QNN "], %[a1]\n\t"                                        \
@@ -1145,15 +1187,13 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
     PZ_W2                                                                      \
     "v_alignbyte_b32 %[t], %[" WC1 "], %[" WC0 "], %[" XC "]\n\t"              \
     "v_cmp_eq_u32 vcc, %[t], %[pref]\n\t"                                      \
-    "s_and_b64 %[st], exec, vcc\n\t"                                           \
-    "s_or_b64 %[" H "], %[" H "], %[st]\n\t"                                   \
+    "s_or_b64 %[" H "], %[" H "], vcc\n\t"                                     \
     "s_andn2_b64 exec, exec, vcc\n\t"                                          \
     "v_cmp_ge_u32 vcc, %[" QN "], %[lo]\n\t"                                   \
     "v_sub_co_u32_e64 %[cb], %[st], %[cb], 1\n\t"                              \
-    "s_andn2_b64 vcc, vcc, %[st]\n\t"                                          \
-    "s_and_b64 exec, exec, vcc\n\t"                                            \
+    "s_andn2_b64 exec, vcc, %[st]\n\t"                                         \
     PZ_W3                                                                      \
-    "s_cbranch_execz .Lpz_done_%=\n\t"
+    EXIT
                         uint32_t q2r, xb, cb;
                         uint64_t s_h0, s_h1, s_h2;
                         asm volatile(
@@ -1163,12 +1203,12 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
                             "s_mov_b64 %[h2], 0\n\t"
                             "v_add_u32 %[cb], -1, %[cnt]\n\t"
                             ".rept " PZ_STR(PZ_ROT) "\n\t"
-                            PZ_RSTEP("q0", "q1", "q2", "wa0", "wa1", "wb0", "wb1", "xa", "xb", "h0")
-                            PZ_RSTEP("q1", "q2", "q0", "wb0", "wb1", "wa0", "wa1", "xb", "xa", "h1")
-                            PZ_RSTEP("q2", "q0", "q1", "wa0", "wa1", "wb0", "wb1", "xa", "xb", "h2")
-                            PZ_RSTEP("q0", "q1", "q2", "wb0", "wb1", "wa0", "wa1", "xb", "xa", "h0")
-                            PZ_RSTEP("q1", "q2", "q0", "wa0", "wa1", "wb0", "wb1", "xa", "xb", "h1")
-                            PZ_RSTEP("q2", "q0", "q1", "wb0", "wb1", "wa0", "wa1", "xb", "xa", "h2")
+                            PZ_RSTEP("q0", "q1", "q2", "wa0", "wa1", "wb0", "wb1", "xa", "xb", "h0", PZ_X1)
+                            PZ_RSTEP("q1", "q2", "q0", "wb0", "wb1", "wa0", "wa1", "xb", "xa", "h1", PZ_X2)
+                            PZ_RSTEP("q2", "q0", "q1", "wa0", "wa1", "wb0", "wb1", "xa", "xb", "h2", PZ_X3)
+                            PZ_RSTEP("q0", "q1", "q2", "wb0", "wb1", "wa0", "wa1", "xb", "xa", "h0", PZ_X4)
+                            PZ_RSTEP("q1", "q2", "q0", "wa0", "wa1", "wb0", "wb1", "xa", "xb", "h1", PZ_X5)
+                            PZ_RSTEP("q2", "q0", "q1", "wb0", "wb1", "wa0", "wa1", "xb", "xa", "h2", PZ_X6)
                             PZ_EARLY_EXIT  // (behind the six steps: a burst always makes some)
                             ".endr\n\t"
                             ".Lpz_done_%=:\n\t"
@@ -1193,6 +1233,14 @@ __global__ __launch_bounds__(PZ_THREADS, PZ_THREADS / 256) void k_lz_parse(const
                         (void)nqB;
                         (void)xn;
 #undef PZ_RSTEP
+#undef PZ_EXIT
+#undef PZ_STAY
+#undef PZ_X1
+#undef PZ_X2
+#undef PZ_X3
+#undef PZ_X4
+#undef PZ_X5
+#undef PZ_X6
 #undef PZ_W1
 #undef PZ_W2
 #undef PZ_W3
