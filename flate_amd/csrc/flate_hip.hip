@@ -3719,6 +3719,32 @@ struct flate_hip_inflater {
 };
 
 namespace {
+// ---- the device buffers of the resumable sessions (inflaters, deflaters): they only grow, with room to spare, and
+// belong to the session, not to the handle's workspace.  `who` owns the buffer ("an inflater": the error text); `held`,
+// where given, counts the bytes (the deflaters': flate_hip_debug_device_bytes).
+void session_free(DevBuf& b, uint64_t* held = nullptr) {
+    if (b.p) {
+        (void)hipFree(b.p);
+        if (held) *held -= b.cap;
+    }
+    b = DevBuf();
+}
+int session_grow(flate_hip_ctx* h, DevBuf& b, size_t bytes, const char* who, uint64_t* held = nullptr) {
+    if (bytes <= b.cap) return FLATE_HIP_OK;
+    (void)hipStreamSynchronize(h->stream);
+    session_free(b, held);
+    const size_t want = bytes + bytes / 8 + 256;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        h->last_error = "hipMalloc(" + std::to_string(want) + ") for " + who + " feed failed";
+        return FLATE_HIP_E_ALLOC;
+    }
+    b.cap = want;
+    if (held) *held += want;
+    return FLATE_HIP_OK;
+}
+
 int inflater_reset_all(flate_hip_ctx* h, flate_hip_inflater* s, const uint32_t* d_which, uint32_t n) {
     if (n == 0) return FLATE_HIP_OK;
     hipLaunchKernelGGL(k_inflater_reset, dim3((n + 255) / 256), dim3(256), 0, h->stream, (uint8_t*)s->sess, d_which, n, s->n,
@@ -3726,19 +3752,55 @@ int inflater_reset_all(flate_hip_ctx* h, flate_hip_inflater* s, const uint32_t* 
     HIP_OK(h, hipGetLastError());
     return FLATE_HIP_OK;
 }
-int inflater_buf(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
-    if (bytes <= b.cap) return FLATE_HIP_OK;
-    (void)hipStreamSynchronize(h->stream);
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        b.p = nullptr;
-        h->last_error = "hipMalloc(" + std::to_string(want) + ") for an inflater feed failed";
-        return FLATE_HIP_E_ALLOC;
+
+// one launch for both memory kinds: the kernel reads the offsets, flags and slots where they lie
+int launch_inflater(flate_hip_ctx* h, flate_hip_inflater* s, const uint8_t* in, const uint64_t* in_off, const uint8_t* final_,
+                    uint8_t* out, const uint64_t* out_off, uint64_t* out_len, uint64_t* consumed, int32_t* status) {
+    ProfScope ps(h, K_INFLATER);
+    hipLaunchKernelGGL(s->dict_aware ? k_inflater_dict : k_inflater, dim3(s->n), dim3(64), 0, h->stream, in, in_off, final_, out,
+                       out_off, out_len, consumed, status, (uint8_t*)s->sess, s->container, s->flags, h->crc);
+    HIP_OK(h, hipGetLastError());
+    return FLATE_HIP_OK;
+}
+
+// ---- a host-memory feed runs on copies (the rules: inflate_plan.h).  The pieces, the offsets from 0 and the flags go to the
+// device ...
+int stage_inflater_feed(flate_hip_ctx* h, flate_hip_inflater* s, const uint8_t* in, uint64_t in_lo, const uint8_t* final_,
+                        const std::vector<uint64_t>& hin, const std::vector<uint64_t>& hout) {
+    const size_t n = s->n;
+    const auto grow = [&](DevBuf& b, size_t bytes) { return session_grow(h, b, bytes, "an inflater"); };
+    int rc;
+    if ((rc = grow(s->in, hin[n] + 16)) || (rc = grow(s->out, hout[n] + 16)) || (rc = grow(s->in_off, 8 * (n + 1))) ||
+        (rc = grow(s->out_off, 8 * (n + 1))) || (rc = grow(s->fin, n)) || (rc = grow(s->out_len, 8 * n)) ||
+        (rc = grow(s->consumed, 8 * n)) || (rc = grow(s->status, 4 * n)))
+        return rc;
+    if (hin[n]) HIP_OK(h, hipMemcpyAsync(s->in.p, in + in_lo, hin[n], hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipMemcpyAsync(s->in_off.p, hin.data(), 8 * (n + 1), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipMemcpyAsync(s->out_off.p, hout.data(), 8 * (n + 1), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipMemcpyAsync(s->fin.p, final_, n, hipMemcpyHostToDevice, h->stream));
+    return FLATE_HIP_OK;
+}
+
+// ... and the results come home, then the produced bytes into the caller's slots (fl_inflater_copy_each)
+int inflater_feed_home(flate_hip_ctx* h, flate_hip_inflater* s, const std::vector<uint64_t>& hout, uint8_t* out,
+                       const uint64_t* out_off, uint64_t* out_len, uint64_t* consumed, int32_t* status) {
+    const uint32_t n = s->n;
+    hipStream_t st = h->stream;
+    HIP_OK(h, hipMemcpyAsync(out_len, s->out_len.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(consumed, s->consumed.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipMemcpyAsync(status, s->status.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_OK(h, hipStreamSynchronize(st));
+    if (fl_inflater_copy_each(n)) {
+        for (uint32_t i = 0; i < n; i++)
+            if (out_len[i]) HIP_OK(h, hipMemcpyAsync(out + out_off[i], (uint8_t*)s->out.p + hout[i], out_len[i], hipMemcpyDeviceToHost, st));
+    } else if (hout[n]) {
+        s->host_out.resize(hout[n]);
+        HIP_OK(h, hipMemcpyAsync(s->host_out.data(), s->out.p, hout[n], hipMemcpyDeviceToHost, st));
+        HIP_OK(h, hipStreamSynchronize(st));
+        for (uint32_t i = 0; i < n; i++)
+            if (out_len[i]) std::memcpy(out + out_off[i], s->host_out.data() + hout[i], out_len[i]);
     }
-    b.cap = want;
+    HIP_OK(h, hipStreamSynchronize(st));
     return FLATE_HIP_OK;
 }
 }  // namespace
@@ -3776,7 +3838,7 @@ int flate_hip_inflater_destroy(flate_hip_handle h, flate_hip_inflater_t s) {
     (void)hipStreamSynchronize(h->stream);
     for (DevBuf* b : {&s->in, &s->in_off, &s->fin, &s->out, &s->out_off, &s->out_len, &s->consumed, &s->status, &s->which,
                       &s->dict, &s->dict_tab, &s->applied})
-        if (b->p) (void)hipFree(b->p);
+        session_free(*b);
     (void)hipFree(s->sess);
     delete s;
     return FLATE_HIP_OK;
@@ -3788,7 +3850,7 @@ int flate_hip_inflater_reset(flate_hip_handle h, flate_hip_inflater_t s, const u
         if (which[k] >= s->n) return FLATE_HIP_E_INVALID_ARG;
     if (n_which == 0) return FLATE_HIP_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
-    int rc = inflater_buf(h, s->which, sizeof(uint32_t) * n_which);
+    int rc = session_grow(h, s->which, sizeof(uint32_t) * n_which, "an inflater");
     if (rc) return rc;
     // (a pageable source: the copy has been taken when hipMemcpyAsync returns, the kernel is ordered behind it)
     HIP_OK(h, hipMemcpyAsync(s->which.p, which, sizeof(uint32_t) * n_which, hipMemcpyHostToDevice, h->stream));
@@ -3807,13 +3869,13 @@ int flate_hip_inflater_set_dictionary(flate_hip_handle h, flate_hip_inflater_t s
     if (n_which == 0) return FLATE_HIP_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
     hipStream_t st = h->stream;
+    const auto grow = [&](DevBuf& b, size_t bytes) { return session_grow(h, b, bytes, "an inflater"); };
     int rc;
-    if ((rc = inflater_buf(h, s->which, sizeof(uint32_t) * n_which)) || (rc = inflater_buf(h, s->applied, n_which)) ||
-        (rc = inflater_buf(h, s->dict_tab, sizeof(fl_dict_ent))))
+    if ((rc = grow(s->which, sizeof(uint32_t) * n_which)) || (rc = grow(s->applied, n_which)) || (rc = grow(s->dict_tab, sizeof(fl_dict_ent))))
         return rc;
     const uint8_t* d_dict = dict;
     if (memkind == FLATE_HIP_MEM_HOST) {
-        if ((rc = inflater_buf(h, s->dict, dict_len + 16))) return rc;
+        if ((rc = grow(s->dict, dict_len + 16))) return rc;
         if (dict_len) HIP_OK(h, hipMemcpyAsync(s->dict.p, dict, dict_len, hipMemcpyHostToDevice, st));
         d_dict = (const uint8_t*)s->dict.p;
     }
@@ -3842,68 +3904,20 @@ int flate_hip_inflater_feed(flate_hip_handle h, flate_hip_inflater_t s, const ui
     if (!h || !s || !in_off || !final_ || !out_off || !out_len || !consumed || !status) return FLATE_HIP_E_INVALID_ARG;
     if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
-    hipStream_t st = h->stream;
-    const uint32_t n = s->n;
-    if (memkind == FLATE_HIP_MEM_DEVICE) {  // enqueue only: the kernel reads the offsets itself
-        ProfScope ps(h, K_INFLATER);
-        hipLaunchKernelGGL(s->dict_aware ? k_inflater_dict : k_inflater, dim3(n), dim3(64), 0, st, in, in_off, final_, out, out_off,
-                           out_len, consumed, status, (uint8_t*)s->sess, s->container, s->flags, h->crc);
-        HIP_OK(h, hipGetLastError());
-        if (h->sync) HIP_OK(h, hipStreamSynchronize(st));
+    int rc;
+    if (memkind == FLATE_HIP_MEM_DEVICE) {  // enqueue only: the kernel reads the caller's offsets itself
+        if ((rc = launch_inflater(h, s, in, in_off, final_, out, out_off, out_len, consumed, status))) return rc;
+        if (h->sync) HIP_OK(h, hipStreamSynchronize(h->stream));
         return FLATE_HIP_OK;
     }
-    // host memory: check the slots, stage pieces and offsets, run, bring the produced bytes home
-    for (uint32_t i = 0; i < n; i++) {
-        if (in_off[i + 1] < in_off[i] || out_off[i + 1] < out_off[i]) return FLATE_HIP_E_INVALID_ARG;
-        const uint64_t slot = out_off[i + 1] - out_off[i];
-        const bool skipped = in_off[i + 1] == in_off[i] && !final_[i] && slot == 0;
-        if (!skipped && slot > 0 && slot < 258) return FLATE_HIP_E_INVALID_ARG;
-    }
-    const uint64_t in_lo = in_off[0], in_n = in_off[n] - in_lo, out_lo = out_off[0], out_n = out_off[n] - out_lo;
-    std::vector<uint64_t> hin(n + 1), hout(n + 1);
-    for (uint32_t i = 0; i <= n; i++) {
-        hin[i] = in_off[i] - in_lo;
-        hout[i] = out_off[i] - out_lo;
-    }
-    int rc;
-    if ((rc = inflater_buf(h, s->in, in_n + 16)) || (rc = inflater_buf(h, s->out, out_n + 16)) ||
-        (rc = inflater_buf(h, s->in_off, 8 * (n + 1))) || (rc = inflater_buf(h, s->out_off, 8 * (n + 1))) ||
-        (rc = inflater_buf(h, s->fin, n)) || (rc = inflater_buf(h, s->out_len, 8 * n)) ||
-        (rc = inflater_buf(h, s->consumed, 8 * n)) || (rc = inflater_buf(h, s->status, 4 * n)))
+    if (!fl_inflater_slots_ok(in_off, out_off, final_, s->n)) return FLATE_HIP_E_INVALID_ARG;
+    std::vector<uint64_t> hin, hout;
+    fl_inflater_rebase(in_off, out_off, s->n, hin, hout);
+    if ((rc = stage_inflater_feed(h, s, in, in_off[0], final_, hin, hout))) return rc;
+    if ((rc = launch_inflater(h, s, (const uint8_t*)s->in.p, (const uint64_t*)s->in_off.p, (const uint8_t*)s->fin.p, (uint8_t*)s->out.p,
+                              (const uint64_t*)s->out_off.p, (uint64_t*)s->out_len.p, (uint64_t*)s->consumed.p, (int32_t*)s->status.p)))
         return rc;
-    if (in_n) HIP_OK(h, hipMemcpyAsync(s->in.p, in + in_lo, in_n, hipMemcpyHostToDevice, st));
-    HIP_OK(h, hipMemcpyAsync(s->in_off.p, hin.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
-    HIP_OK(h, hipMemcpyAsync(s->out_off.p, hout.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
-    HIP_OK(h, hipMemcpyAsync(s->fin.p, final_, n, hipMemcpyHostToDevice, st));
-    {
-        ProfScope ps(h, K_INFLATER);
-        hipLaunchKernelGGL(s->dict_aware ? k_inflater_dict : k_inflater, dim3(n), dim3(64), 0, st, (const uint8_t*)s->in.p, (const uint64_t*)s->in_off.p,
-                           (const uint8_t*)s->fin.p, (uint8_t*)s->out.p, (const uint64_t*)s->out_off.p,
-                           (uint64_t*)s->out_len.p, (uint64_t*)s->consumed.p, (int32_t*)s->status.p, (uint8_t*)s->sess,
-                           s->container, s->flags, h->crc);
-        HIP_OK(h, hipGetLastError());
-    }
-    HIP_OK(h, hipMemcpyAsync(out_len, s->out_len.p, 8 * n, hipMemcpyDeviceToHost, st));
-    HIP_OK(h, hipMemcpyAsync(consumed, s->consumed.p, 8 * n, hipMemcpyDeviceToHost, st));
-    HIP_OK(h, hipMemcpyAsync(status, s->status.p, 4 * n, hipMemcpyDeviceToHost, st));
-    HIP_OK(h, hipStreamSynchronize(st));
-    // only the produced bytes reach the caller's slots (what lies beyond out_len[i] stays as it was): a few streams
-    // by a copy each, many by one copy of the slots to the host and a copy of each stream's bytes from there
-    if (n > 16) {
-        if (out_n) {
-            s->host_out.resize(out_n);
-            HIP_OK(h, hipMemcpyAsync(s->host_out.data(), s->out.p, out_n, hipMemcpyDeviceToHost, st));
-            HIP_OK(h, hipStreamSynchronize(st));
-            for (uint32_t i = 0; i < n; i++)
-                if (out_len[i]) std::memcpy(out + out_off[i], s->host_out.data() + hout[i], out_len[i]);
-        }
-    } else {
-        for (uint32_t i = 0; i < n; i++)
-            if (out_len[i])
-                HIP_OK(h, hipMemcpyAsync(out + out_off[i], (uint8_t*)s->out.p + hout[i], out_len[i], hipMemcpyDeviceToHost, st));
-    }
-    HIP_OK(h, hipStreamSynchronize(st));
-    return FLATE_HIP_OK;
+    return inflater_feed_home(h, s, hout, out, out_off, out_len, consumed, status);
 }
 
 }  // extern "C"
@@ -3913,47 +3927,227 @@ struct flate_hip_deflater {
     uint32_t n = 0;
     int container = 0, mode = 0;
     DevBuf state, bufs;  // fl_dfl_state and FL_DFL_BUF bytes of SimpleCompressor buffer per stream
-    // output a feed made beyond its slot: handed out by the next feeds, before the stream takes more input
-    std::vector<DevBuf> pend;
-    std::vector<uint64_t> pend_len, pend_pos;
-    // host mirror of the per-stream counters the feeds plan with
-    std::vector<uint32_t> bl;
-    std::vector<uint8_t> hdr_done, finished;
+    std::vector<fl_dfl_mirror> mirror;  // per stream: the counters the feeds plan with (deflater_plan.h) ...
+    std::vector<DevBuf> pend;           // ... and the bytes of its pending output
     // feed workspace: the pieces (host feeds), the staged input, the produced blocks, the tables
     DevBuf src, win, wout, chunks, blk, sb, ckblk, cksb, jobs, produced, plans, hist, cks;
 };
 
+static_assert((int)FL_FEED_MORE == (int)FLATE_HIP_FEED_MORE && (int)FL_FEED_FLUSH == (int)FLATE_HIP_FEED_FLUSH &&
+                  (int)FL_FEED_FINISH == (int)FLATE_HIP_FEED_FINISH && (int)FL_DFL_ST_OK == (int)FLATE_HIP_ST_OK &&
+                  (int)FL_DFL_ST_NEED_INPUT == (int)FLATE_HIP_ST_NEED_INPUT && (int)FL_DFL_ST_NEED_OUTPUT == (int)FLATE_HIP_ST_NEED_OUTPUT,
+              "deflater_plan.h speaks of the ops and statuses of include/flate_hip.h");
+
 namespace {
-int deflater_buf(flate_hip_ctx* h, DevBuf& b, size_t bytes) {
-    if (bytes <= b.cap) return FLATE_HIP_OK;
-    (void)hipStreamSynchronize(h->stream);
-    if (b.p) {
-        (void)hipFree(b.p);
-        h->dfl_bytes -= b.cap;
+
+// ---- flate_hip_deflater_feed: what a feed decides is deflater_plan.h's, the stages below carry it out over one record
+// per call.  (A feed that fails halfway -- an allocation for pending output, a HIP call -- leaves the mirror moved on for
+// the streams it had settled or drained by then.)
+struct DeflaterFeed {
+    flate_hip_ctx* h;
+    flate_hip_deflater* d;
+    hipStream_t st;
+    const uint8_t* in;  // the caller's buffers
+    uint8_t* out;
+    bool dev;                         // device memory
+    std::vector<uint64_t> hin, hout;  // the caller's tables on the host
+    std::vector<uint8_t> hop;
+    std::vector<uint64_t> r_len, r_cons;  // what the feed answers
+    std::vector<int32_t> r_st;
+    std::vector<uint32_t> act;  // the streams that take their piece: job j is stream act[j]
+    fl_dfl_layout lay;
+    fl_params prm{};
+    const uint8_t* src = nullptr;  // where the jobs' src_off count from: the caller's buffer, or the staged pieces
+
+    hipMemcpyKind to_out() const { return dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; }
+    int grow(DevBuf& b, size_t bytes) { return session_grow(h, b, bytes, "a deflater", &h->dfl_bytes); }
+};
+
+// offsets and ops on the host: the block tables are built here (device feeds wait for them)
+int fetch_feed_tables(DeflaterFeed& df, const uint64_t* in_off, const uint64_t* out_off, const uint8_t* op) {
+    flate_hip_ctx* h = df.h;
+    const size_t n = df.d->n;
+    df.hin.resize(n + 1);
+    df.hout.resize(n + 1);
+    df.hop.resize(n);
+    if (df.dev) {
+        HIP_OK(h, hipMemcpyAsync(df.hin.data(), in_off, 8 * (n + 1), hipMemcpyDeviceToHost, df.st));
+        HIP_OK(h, hipMemcpyAsync(df.hout.data(), out_off, 8 * (n + 1), hipMemcpyDeviceToHost, df.st));
+        HIP_OK(h, hipMemcpyAsync(df.hop.data(), op, n, hipMemcpyDeviceToHost, df.st));
+        HIP_OK(h, hipStreamSynchronize(df.st));
+    } else {
+        std::memcpy(df.hin.data(), in_off, 8 * (n + 1));
+        std::memcpy(df.hout.data(), out_off, 8 * (n + 1));
+        std::memcpy(df.hop.data(), op, n);
     }
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        h->last_error = "hipMalloc(" + std::to_string(want) + ") for a deflater feed failed";
-        return FLATE_HIP_E_ALLOC;
-    }
-    b.cap = want;
-    h->dfl_bytes += want;
     return FLATE_HIP_OK;
 }
-void deflater_free(flate_hip_ctx* h, DevBuf& b) {
-    if (b.p) {
-        (void)hipFree(b.p);
-        h->dfl_bytes -= b.cap;
+
+// every stream's route (fl_dfl_route_stream); pending output goes into the slots here
+int drain_and_route(DeflaterFeed& df) {
+    flate_hip_ctx* h = df.h;
+    flate_hip_deflater* d = df.d;
+    df.r_len.assign(d->n, 0);
+    df.r_cons.assign(d->n, 0);
+    df.r_st.assign(d->n, FLATE_HIP_ST_NEED_INPUT);
+    for (uint32_t i = 0; i < d->n; i++) {
+        const fl_dfl_route r = fl_dfl_route_stream(d->mirror[i], df.hin[i + 1] - df.hin[i], df.hop[i], df.hout[i + 1] - df.hout[i]);
+        if (r.give) HIP_OK(h, hipMemcpyAsync(df.out + df.hout[i], (const uint8_t*)d->pend[i].p + r.from, r.give, df.to_out(), df.st));
+        df.r_len[i] = r.give;
+        df.r_st[i] = r.status;
+        if (r.kind == FL_DFL_ACTIVE) df.act.push_back(i);
     }
-    b.p = nullptr;
-    b.cap = 0;
+    return FLATE_HIP_OK;
 }
-// the largest piece one feed takes for a stream: its buffer and the piece are staged together, positions are 32-bit
-constexpr uint64_t kDeflaterMaxPiece = 0xfff00000ull - FL_DFL_BUF;
+
+void lay_out_feed(DeflaterFeed& df) {
+    const flate_hip_deflater* d = df.d;
+    fl_dfl_lay_out(d->mirror.data(), df.act, df.hin.data(), df.hop.data(), df.dev, df.lay);
+    (void)level_args(d->mode, df.prm);
+    df.prm.container = d->container;
+    df.prm.mode = d->mode;
+    df.prm.n_chunks = (uint32_t)df.act.size();
+    df.prm.n_blocks = (uint32_t)df.lay.blocks.size();
+}
+
+int reserve_feed_buffers(DeflaterFeed& df) {
+    flate_hip_deflater* d = df.d;
+    const fl_dfl_layout& lay = df.lay;
+    const size_t nj = lay.jobs.size(), nb = std::max<size_t>(lay.blocks.size(), 1), nck = std::max<size_t>(lay.units.size(), 1);
+    int rc;
+    if ((!df.dev && (rc = df.grow(d->src, df.hin[d->n] - df.hin[0] + 16))) || (rc = df.grow(d->win, lay.win_n + 16)) || (rc = df.grow(d->wout, lay.out_n + 16)) ||
+        (rc = df.grow(d->jobs, sizeof(fl_dfl_job) * nj)) || (rc = df.grow(d->chunks, sizeof(fl_chunk) * nj)) ||
+        (rc = df.grow(d->produced, 8 * nj)) || (rc = df.grow(d->blk, 4 * nb)) || (rc = df.grow(d->sb, sizeof(fl_sblock) * nb)) ||
+        (rc = df.grow(d->ckblk, 4 * nck)) || (rc = df.grow(d->cksb, sizeof(fl_sblock) * nck)) ||
+        (rc = df.grow(d->plans, sizeof(fl_block_plan) * nb)) || (rc = df.grow(d->hist, 4 * 320 * nb)) || (rc = df.grow(d->cks, 8 * nck)))
+        return rc;
+    return FLATE_HIP_OK;
+}
+
+// a host feed's pieces, the tables, and a cleared output (the bit packer ORs into it)
+int upload_feed_tables(DeflaterFeed& df) {
+    flate_hip_ctx* h = df.h;
+    flate_hip_deflater* d = df.d;
+    const fl_dfl_layout& lay = df.lay;
+    const size_t nj = lay.jobs.size(), nb = lay.blocks.size(), nck = lay.units.size();
+    const uint64_t in_lo = df.hin[0], in_hi = df.hin[d->n];
+    df.src = df.in;
+    if (!df.dev) {
+        if (in_hi > in_lo) HIP_OK(h, hipMemcpyAsync(d->src.p, df.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, df.st));
+        df.src = (const uint8_t*)d->src.p;
+    }
+    HIP_OK(h, hipMemcpyAsync(d->jobs.p, lay.jobs.data(), sizeof(fl_dfl_job) * nj, hipMemcpyHostToDevice, df.st));
+    HIP_OK(h, hipMemcpyAsync(d->chunks.p, lay.chunks.data(), sizeof(fl_chunk) * nj, hipMemcpyHostToDevice, df.st));
+    if (nb) {
+        HIP_OK(h, hipMemcpyAsync(d->blk.p, lay.block_job.data(), 4 * nb, hipMemcpyHostToDevice, df.st));
+        HIP_OK(h, hipMemcpyAsync(d->sb.p, lay.blocks.data(), sizeof(fl_sblock) * nb, hipMemcpyHostToDevice, df.st));
+    }
+    if (nck) {
+        HIP_OK(h, hipMemcpyAsync(d->ckblk.p, lay.unit_job.data(), 4 * nck, hipMemcpyHostToDevice, df.st));
+        HIP_OK(h, hipMemcpyAsync(d->cksb.p, lay.units.data(), sizeof(fl_sblock) * nck, hipMemcpyHostToDevice, df.st));
+    }
+    HIP_OK(h, hipMemsetAsync(d->wout.p, 0, lay.out_n, df.st));
+    return FLATE_HIP_OK;
+}
+
+// stage, checksum, plan, place (k_deflater_offsets), pack, keep (k_deflater_commit)
+int enqueue_feed_kernels(DeflaterFeed& df) {
+    flate_hip_ctx* h = df.h;
+    flate_hip_deflater* d = df.d;
+    hipStream_t st = df.st;
+    const uint32_t nj = (uint32_t)df.lay.jobs.size(), nb = (uint32_t)df.lay.blocks.size(), nck = (uint32_t)df.lay.units.size();
+    const fl_dfl_job* djobs = (const fl_dfl_job*)d->jobs.p;
+    const fl_chunk* dch = (const fl_chunk*)d->chunks.p;
+    const uint32_t* dblk = (const uint32_t*)d->blk.p;
+    const fl_sblock* dsb = (const fl_sblock*)d->sb.p;
+    fl_block_plan* dpl = (fl_block_plan*)d->plans.p;
+    const uint8_t* dwin = (const uint8_t*)d->win.p;
+    {
+        ProfScope ps(h, K_DEFLATER);
+        hipLaunchKernelGGL(k_deflater_stage, dim3(nj, df.lay.slices), dim3(256), 0, st, df.src, djobs, dch, (const uint8_t*)d->bufs.p,
+                           (uint8_t*)d->win.p);
+    }
+    if (d->container != 0 && nck) {
+        ProfScope ps(h, K_CHECKSUM);
+        hipLaunchKernelGGL(k_checksum, dim3(nck), dim3(64), 0, st, dwin, dch, (const uint32_t*)d->ckblk.p,
+                           (const fl_sblock*)d->cksb.p, df.prm, h->crc, (uint32_t*)d->cks.p);
+    }
+    if (nb) {
+        ProfScope ps(h, K_PLAN);
+        if (d->mode == 0) {
+            hipLaunchKernelGGL(k_plan_store, dim3((nb + 255) / 256), dim3(256), 0, st, dch, dblk, dsb, nb, dpl);
+        } else {
+            hipLaunchKernelGGL(k_byte_hist, dim3(nb), dim3(256), 0, st, dwin, dch, dblk, dsb, (uint32_t*)d->hist.p);
+            hipLaunchKernelGGL(k_plan, dim3((nb + FL_PLAN_WAVES - 1) / FL_PLAN_WAVES), dim3(64 * FL_PLAN_WAVES), 0, st,
+                               dch, dblk, dsb, df.prm, (const uint32_t*)d->hist.p, dpl);
+        }
+    }
+    {
+        ProfScope ps(h, K_DEFLATER);
+        hipLaunchKernelGGL(k_deflater_offsets, dim3(nj), dim3(64), 0, st, djobs, dch, df.prm, h->crc, dpl, (const uint32_t*)d->cks.p,
+                           (fl_dfl_state*)d->state.p, (uint8_t*)d->wout.p, (uint64_t*)d->produced.p);
+    }
+    if (nb) {
+        ProfScope ps(h, K_ENCODE);
+        hipLaunchKernelGGL(k_encode<false>, dim3(nb), dim3(64 * FL_ENC_WAVES), 0, st, dwin, dch, dblk,
+                           (const fl_block_plan*)dpl, (const uint32_t*)nullptr, (uint32_t*)d->wout.p);
+    }
+    {
+        ProfScope ps(h, K_DEFLATER);
+        hipLaunchKernelGGL(k_deflater_commit, dim3(nj), dim3(256), 0, st, djobs, dch, (const uint64_t*)d->produced.p, dwin,
+                           (const uint8_t*)d->wout.p, (fl_dfl_state*)d->state.p, (uint8_t*)d->bufs.p);
+    }
+    HIP_OK(h, hipGetLastError());
+    return FLATE_HIP_OK;
+}
+
+// every job's produced bytes: into the slot, the rest kept as pending output (fl_dfl_settle)
+int settle_and_deliver(DeflaterFeed& df) {
+    flate_hip_ctx* h = df.h;
+    flate_hip_deflater* d = df.d;
+    const uint32_t nj = (uint32_t)df.lay.jobs.size();
+    std::vector<uint64_t> prod(nj);
+    HIP_OK(h, hipMemcpyAsync(prod.data(), d->produced.p, 8 * (size_t)nj, hipMemcpyDeviceToHost, df.st));
+    HIP_OK(h, hipStreamSynchronize(df.st));
+    for (uint32_t j = 0; j < nj; j++) {
+        const uint32_t i = df.act[j];
+        const fl_chunk& ck = df.lay.chunks[j];
+        fl_dfl_mirror m = d->mirror[i];
+        const fl_dfl_settled s = fl_dfl_settle(m, df.lay.jobs[j], ck, prod[j], df.hout[i + 1] - df.hout[i]);
+        if (!s.ok) {
+            h->last_error = "deflater feed: a stream produced more than its bound";
+            return FLATE_HIP_E_LAUNCH;
+        }
+        const uint8_t* from = (const uint8_t*)d->wout.p + ck.out_off;
+        if (s.give) HIP_OK(h, hipMemcpyAsync(df.out + df.hout[i], from, s.give, df.to_out(), df.st));
+        if (s.pend) {
+            if (int rc = df.grow(d->pend[i], s.pend)) return rc;
+            HIP_OK(h, hipMemcpyAsync(d->pend[i].p, from + s.give, s.pend, hipMemcpyDeviceToDevice, df.st));
+        }
+        d->mirror[i] = m;
+        df.r_len[i] = s.give;
+        df.r_cons[i] = s.consumed;
+        df.r_st[i] = s.status;
+    }
+    return FLATE_HIP_OK;
+}
+
+int feed_results_home(DeflaterFeed& df, uint64_t* out_len, uint64_t* consumed, int32_t* status) {
+    flate_hip_ctx* h = df.h;
+    const size_t n = df.d->n;
+    if (df.dev) {
+        HIP_OK(h, hipMemcpyAsync(out_len, df.r_len.data(), 8 * n, hipMemcpyHostToDevice, df.st));
+        HIP_OK(h, hipMemcpyAsync(consumed, df.r_cons.data(), 8 * n, hipMemcpyHostToDevice, df.st));
+        HIP_OK(h, hipMemcpyAsync(status, df.r_st.data(), 4 * n, hipMemcpyHostToDevice, df.st));
+    } else {
+        std::memcpy(out_len, df.r_len.data(), 8 * n);
+        std::memcpy(consumed, df.r_cons.data(), 8 * n);
+        std::memcpy(status, df.r_st.data(), 4 * n);
+    }
+    HIP_OK(h, hipStreamSynchronize(df.st));
+    return FLATE_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3977,19 +4171,15 @@ int flate_hip_deflater_create(flate_hip_handle h, uint32_t n_streams, int contai
     d->container = container;
     d->mode = mode;
     d->pend.resize(n_streams);
-    d->pend_len.assign(n_streams, 0);
-    d->pend_pos.assign(n_streams, 0);
-    d->bl.assign(n_streams, 0);
-    d->hdr_done.assign(n_streams, 0);
-    d->finished.assign(n_streams, 0);
-    int rc = deflater_buf(h, d->state, sizeof(fl_dfl_state) * (size_t)n_streams);
-    if (!rc) rc = deflater_buf(h, d->bufs, (size_t)FL_DFL_BUF * n_streams);
+    d->mirror.assign(n_streams, fl_dfl_mirror());
+    int rc = session_grow(h, d->state, sizeof(fl_dfl_state) * (size_t)n_streams, "a deflater", &h->dfl_bytes);
+    if (!rc) rc = session_grow(h, d->bufs, (size_t)FL_DFL_BUF * n_streams, "a deflater", &h->dfl_bytes);
     if (!rc && (hipMemsetAsync(d->state.p, 0, sizeof(fl_dfl_state) * (size_t)n_streams, h->stream) != hipSuccess ||
                 hipStreamSynchronize(h->stream) != hipSuccess))
         rc = FLATE_HIP_E_LAUNCH;
     if (rc) {
-        deflater_free(h, d->state);
-        deflater_free(h, d->bufs);
+        session_free(d->state, &h->dfl_bytes);
+        session_free(d->bufs, &h->dfl_bytes);
         delete d;
         return rc;
     }
@@ -4003,8 +4193,8 @@ int flate_hip_deflater_destroy(flate_hip_handle h, flate_hip_deflater_t d) {
     (void)hipStreamSynchronize(h->stream);
     for (DevBuf* b : {&d->state, &d->bufs, &d->src, &d->win, &d->wout, &d->chunks, &d->blk, &d->sb, &d->ckblk, &d->cksb,
                       &d->jobs, &d->produced, &d->plans, &d->hist, &d->cks})
-        deflater_free(h, *b);
-    for (DevBuf& b : d->pend) deflater_free(h, b);
+        session_free(*b, &h->dfl_bytes);
+    for (DevBuf& b : d->pend) session_free(b, &h->dfl_bytes);
     delete d;
     return FLATE_HIP_OK;
 }
@@ -4017,10 +4207,7 @@ int flate_hip_deflater_reset(flate_hip_handle h, flate_hip_deflater_t d, const u
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
     for (uint32_t k = 0; k < n_which; k++) {
         const uint32_t i = which[k];
-        d->bl[i] = 0;
-        d->hdr_done[i] = 0;
-        d->finished[i] = 0;
-        d->pend_len[i] = d->pend_pos[i] = 0;
+        d->mirror[i] = fl_dfl_mirror();
         HIP_OK(h, hipMemsetAsync((fl_dfl_state*)d->state.p + i, 0, sizeof(fl_dfl_state), h->stream));
     }
     HIP_OK(h, hipStreamSynchronize(h->stream));
@@ -4033,207 +4220,19 @@ int flate_hip_deflater_feed(flate_hip_handle h, flate_hip_deflater_t d, const ui
     if (!h || !d || !in_off || !op || !out_off || !out_len || !consumed || !status) return FLATE_HIP_E_INVALID_ARG;
     if (memkind != FLATE_HIP_MEM_HOST && memkind != FLATE_HIP_MEM_DEVICE) return FLATE_HIP_E_INVALID_ARG;
     if (hipSetDevice(h->device) != hipSuccess) return FLATE_HIP_E_NO_DEVICE;
-    hipStream_t st = h->stream;
-    const uint32_t n = d->n;
-    const bool dev = memkind == FLATE_HIP_MEM_DEVICE;
-    const hipMemcpyKind to_out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    // offsets and ops on the host: the block tables are built here (device feeds wait for them)
-    std::vector<uint64_t> hin(n + 1), hout(n + 1);
-    std::vector<uint8_t> hop(n);
-    if (dev) {
-        HIP_OK(h, hipMemcpyAsync(hin.data(), in_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(hout.data(), out_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipMemcpyAsync(hop.data(), op, n, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-    } else {
-        std::memcpy(hin.data(), in_off, 8 * ((size_t)n + 1));
-        std::memcpy(hout.data(), out_off, 8 * ((size_t)n + 1));
-        std::memcpy(hop.data(), op, n);
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (hin[i + 1] < hin[i] || hout[i + 1] < hout[i] || hop[i] > FLATE_HIP_FEED_FINISH) return FLATE_HIP_E_INVALID_ARG;
-        if (hin[i + 1] - hin[i] > kDeflaterMaxPiece) return FLATE_HIP_E_INVALID_ARG;
-    }
-    if (hin[n] > hin[0] && !in) return FLATE_HIP_E_INVALID_ARG;
-    std::vector<uint64_t> r_len(n, 0), r_cons(n, 0);
-    std::vector<int32_t> r_st(n, FLATE_HIP_ST_NEED_INPUT);
+    DeflaterFeed df{h, d, h->stream, in, out, memkind == FLATE_HIP_MEM_DEVICE};
     int rc;
-
-    // streams with output left over: drain it, take nothing; finished ones take nothing; the rest take their piece
-    std::vector<uint32_t> act;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint64_t pn = hin[i + 1] - hin[i], slot = hout[i + 1] - hout[i];
-        if (d->pend_len[i] > d->pend_pos[i]) {
-            const uint64_t give = std::min(slot, d->pend_len[i] - d->pend_pos[i]);
-            if (give)
-                HIP_OK(h, hipMemcpyAsync(out + hout[i], (const uint8_t*)d->pend[i].p + d->pend_pos[i], give, to_out, st));
-            d->pend_pos[i] += give;
-            r_len[i] = give;
-            const bool left = d->pend_pos[i] < d->pend_len[i];
-            // (everything delivered: NEED_INPUT, or the final status of a finished stream; consumed 0 says the piece was
-            // not taken and goes again)
-            r_st[i] = left ? FLATE_HIP_ST_NEED_OUTPUT : (d->finished[i] ? FLATE_HIP_ST_OK : FLATE_HIP_ST_NEED_INPUT);
-            if (!left) d->pend_len[i] = d->pend_pos[i] = 0;
-        } else if (d->finished[i]) {
-            r_st[i] = FLATE_HIP_ST_OK;
-        } else if (!(pn == 0 && hop[i] == FLATE_HIP_FEED_MORE && slot == 0)) {
-            act.push_back(i);
-        }
+    if ((rc = fetch_feed_tables(df, in_off, out_off, op))) return rc;
+    if (!fl_dfl_feed_ok(df.hin.data(), df.hout.data(), df.hop.data(), d->n, in != nullptr)) return FLATE_HIP_E_INVALID_ARG;
+    if ((rc = drain_and_route(df))) return rc;
+    if (!df.act.empty()) {
+        lay_out_feed(df);
+        if ((rc = reserve_feed_buffers(df))) return rc;
+        if ((rc = upload_feed_tables(df))) return rc;
+        if ((rc = enqueue_feed_kernels(df))) return rc;
+        if ((rc = settle_and_deliver(df))) return rc;
     }
-
-    if (!act.empty()) {
-        const uint32_t nj = (uint32_t)act.size();
-        fl_params prm{};
-        (void)level_args(d->mode, prm);
-        prm.container = d->container;
-        prm.mode = d->mode;
-        prm.n_chunks = nj;
-        prm.stream = 0;
-        std::vector<fl_dfl_job> jobs(nj);
-        std::vector<fl_chunk> chunks(nj);
-        std::vector<fl_sblock> sbl, cku;
-        std::vector<uint32_t> blk, ckblk;
-        uint64_t win_n = 0, out_n = 0, max_units = 1;
-        const uint64_t in_lo = hin[0];
-        for (uint32_t j = 0; j < nj; j++) {
-            const uint32_t i = act[j];
-            fl_dfl_job& jb = jobs[j];
-            fl_chunk& c = chunks[j];
-            std::memset(&c, 0, sizeof c);
-            jb.stream = i;
-            jb.bl = d->bl[i];
-            jb.n = (uint32_t)(hin[i + 1] - hin[i]);
-            jb.src_off = dev ? hin[i] : hin[i] - in_lo;
-            jb.hdr = d->hdr_done[i] ? 0u : 1u;
-            jb.finish = hop[i] == FLATE_HIP_FEED_FINISH ? 1u : 0u;
-            c.first_block = (uint32_t)sbl.size();
-            jb.keep = fl_dfl_blocks(jb.bl, jb.n, hop[i], sbl);
-            c.n_blocks = (uint32_t)sbl.size() - c.first_block;
-            for (uint32_t k = 0; k < c.n_blocks; k++) blk.push_back(j);
-            jb.ck_first = (uint32_t)cku.size();
-            jb.ck_n = fl_dfl_checksum_units(jb.bl, jb.n, cku);
-            for (uint32_t k = 0; k < jb.ck_n; k++) ckblk.push_back(j);
-            const uint32_t L = jb.bl + jb.n;
-            c.in_off = win_n;
-            c.in_len = L;
-            win_n += (((uint64_t)L + 15) & ~15ull) + 16;
-            c.out_off = out_n;
-            c.out_cap = fl_dfl_out_bound(jb.bl, jb.n);
-            out_n += (c.out_cap + 15) & ~15ull;
-            c.unfinished = jb.finish ? 0u : 1u;
-            max_units = std::max<uint64_t>(max_units, ((uint64_t)L + 15) / 16);
-        }
-        const uint32_t nb = (uint32_t)sbl.size(), nck = (uint32_t)cku.size();
-        prm.n_blocks = nb;
-        const uint8_t* src = in;
-        if (!dev) {
-            if ((rc = deflater_buf(h, d->src, hin[n] - in_lo + 16))) return rc;
-            if (hin[n] > in_lo) HIP_OK(h, hipMemcpyAsync(d->src.p, in + in_lo, hin[n] - in_lo, hipMemcpyHostToDevice, st));
-            src = (const uint8_t*)d->src.p;
-        }
-        if ((rc = deflater_buf(h, d->win, win_n + 16)) || (rc = deflater_buf(h, d->wout, out_n + 16)) ||
-            (rc = deflater_buf(h, d->jobs, sizeof(fl_dfl_job) * nj)) || (rc = deflater_buf(h, d->chunks, sizeof(fl_chunk) * nj)) ||
-            (rc = deflater_buf(h, d->produced, 8 * (size_t)nj)) ||
-            (rc = deflater_buf(h, d->blk, 4 * (size_t)std::max(nb, 1u))) || (rc = deflater_buf(h, d->sb, sizeof(fl_sblock) * std::max(nb, 1u))) ||
-            (rc = deflater_buf(h, d->ckblk, 4 * (size_t)std::max(nck, 1u))) ||
-            (rc = deflater_buf(h, d->cksb, sizeof(fl_sblock) * std::max(nck, 1u))) ||
-            (rc = deflater_buf(h, d->plans, sizeof(fl_block_plan) * std::max(nb, 1u))) ||
-            (rc = deflater_buf(h, d->hist, 4 * 320 * (size_t)std::max(nb, 1u))) ||
-            (rc = deflater_buf(h, d->cks, 8 * (size_t)std::max(nck, 1u))))
-            return rc;
-        HIP_OK(h, hipMemcpyAsync(d->jobs.p, jobs.data(), sizeof(fl_dfl_job) * nj, hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipMemcpyAsync(d->chunks.p, chunks.data(), sizeof(fl_chunk) * nj, hipMemcpyHostToDevice, st));
-        if (nb) {
-            HIP_OK(h, hipMemcpyAsync(d->blk.p, blk.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, st));
-            HIP_OK(h, hipMemcpyAsync(d->sb.p, sbl.data(), sizeof(fl_sblock) * nb, hipMemcpyHostToDevice, st));
-        }
-        if (nck) {
-            HIP_OK(h, hipMemcpyAsync(d->ckblk.p, ckblk.data(), 4 * (size_t)nck, hipMemcpyHostToDevice, st));
-            HIP_OK(h, hipMemcpyAsync(d->cksb.p, cku.data(), sizeof(fl_sblock) * nck, hipMemcpyHostToDevice, st));
-        }
-        HIP_OK(h, hipMemsetAsync(d->wout.p, 0, out_n, st));  // (the bit packer ORs into the output)
-        const fl_dfl_job* djobs = (const fl_dfl_job*)d->jobs.p;
-        const fl_chunk* dch = (const fl_chunk*)d->chunks.p;
-        const uint32_t* dblk = (const uint32_t*)d->blk.p;
-        const fl_sblock* dsb = (const fl_sblock*)d->sb.p;
-        fl_block_plan* dpl = (fl_block_plan*)d->plans.p;
-        {
-            ProfScope ps(h, K_DEFLATER);
-            const uint32_t slices = (uint32_t)std::min<uint64_t>(1024, (max_units + 255) / 256);
-            hipLaunchKernelGGL(k_deflater_stage, dim3(nj, slices), dim3(256), 0, st, src, djobs, dch, (const uint8_t*)d->bufs.p,
-                               (uint8_t*)d->win.p);
-        }
-        const uint8_t* dwin = (const uint8_t*)d->win.p;
-        if (d->container != 0 && nck) {
-            ProfScope ps(h, K_CHECKSUM);
-            hipLaunchKernelGGL(k_checksum, dim3(nck), dim3(64), 0, st, dwin, dch, (const uint32_t*)d->ckblk.p,
-                               (const fl_sblock*)d->cksb.p, prm, h->crc, (uint32_t*)d->cks.p);
-        }
-        if (nb) {
-            ProfScope ps(h, K_PLAN);
-            if (d->mode == 0) {
-                hipLaunchKernelGGL(k_plan_store, dim3((nb + 255) / 256), dim3(256), 0, st, dch, dblk, dsb, nb, dpl);
-            } else {
-                hipLaunchKernelGGL(k_byte_hist, dim3(nb), dim3(256), 0, st, dwin, dch, dblk, dsb, (uint32_t*)d->hist.p);
-                hipLaunchKernelGGL(k_plan, dim3((nb + FL_PLAN_WAVES - 1) / FL_PLAN_WAVES), dim3(64 * FL_PLAN_WAVES), 0, st,
-                                   dch, dblk, dsb, prm, (const uint32_t*)d->hist.p, dpl);
-            }
-        }
-        {
-            ProfScope ps(h, K_DEFLATER);
-            hipLaunchKernelGGL(k_deflater_offsets, dim3(nj), dim3(64), 0, st, djobs, dch, prm, h->crc, dpl,
-                               (const uint32_t*)d->cks.p, (fl_dfl_state*)d->state.p, (uint8_t*)d->wout.p,
-                               (uint64_t*)d->produced.p);
-        }
-        if (nb) {
-            ProfScope ps(h, K_ENCODE);
-            hipLaunchKernelGGL(k_encode<false>, dim3(nb), dim3(64 * FL_ENC_WAVES), 0, st, dwin, dch, dblk,
-                               (const fl_block_plan*)dpl, (const uint32_t*)nullptr, (uint32_t*)d->wout.p);
-        }
-        {
-            ProfScope ps(h, K_DEFLATER);
-            hipLaunchKernelGGL(k_deflater_commit, dim3(nj), dim3(256), 0, st, djobs, dch, (const uint64_t*)d->produced.p, dwin,
-                               (const uint8_t*)d->wout.p, (fl_dfl_state*)d->state.p, (uint8_t*)d->bufs.p);
-        }
-        HIP_OK(h, hipGetLastError());
-        std::vector<uint64_t> prod(nj);
-        HIP_OK(h, hipMemcpyAsync(prod.data(), d->produced.p, 8 * (size_t)nj, hipMemcpyDeviceToHost, st));
-        HIP_OK(h, hipStreamSynchronize(st));
-        for (uint32_t j = 0; j < nj; j++) {
-            const uint32_t i = act[j];
-            const uint64_t p = prod[j], slot = hout[i + 1] - hout[i];
-            if (p > chunks[j].out_cap) {
-                h->last_error = "deflater feed: a stream produced more than its bound";
-                return FLATE_HIP_E_LAUNCH;
-            }
-            const uint64_t give = std::min(p, slot);
-            const uint8_t* from = (const uint8_t*)d->wout.p + chunks[j].out_off;
-            if (give) HIP_OK(h, hipMemcpyAsync(out + hout[i], from, give, to_out, st));
-            if (p > give) {
-                if ((rc = deflater_buf(h, d->pend[i], p - give))) return rc;
-                HIP_OK(h, hipMemcpyAsync(d->pend[i].p, from + give, p - give, hipMemcpyDeviceToDevice, st));
-                d->pend_len[i] = p - give;
-                d->pend_pos[i] = 0;
-            }
-            d->bl[i] = jobs[j].keep;
-            d->hdr_done[i] = 1;
-            if (jobs[j].finish) d->finished[i] = 1;
-            r_len[i] = give;
-            r_cons[i] = jobs[j].n;
-            r_st[i] = p > give ? FLATE_HIP_ST_NEED_OUTPUT : (jobs[j].finish ? FLATE_HIP_ST_OK : FLATE_HIP_ST_NEED_INPUT);
-        }
-    }
-    if (dev) {
-        HIP_OK(h, hipMemcpyAsync(out_len, r_len.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipMemcpyAsync(consumed, r_cons.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        HIP_OK(h, hipMemcpyAsync(status, r_st.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    } else {
-        std::memcpy(out_len, r_len.data(), 8 * (size_t)n);
-        std::memcpy(consumed, r_cons.data(), 8 * (size_t)n);
-        std::memcpy(status, r_st.data(), 4 * (size_t)n);
-    }
-    HIP_OK(h, hipStreamSynchronize(st));
-    return FLATE_HIP_OK;
+    return feed_results_home(df, out_len, consumed, status);
 }
 
 int flate_hip_debug_device_bytes(flate_hip_handle h, uint64_t* bytes) {

@@ -2,7 +2,9 @@
 // flate_hip_decompressed_sizes, flate_hip_decompress_members, flate_hip_decompress_ranges, index_walk): the chunk table
 // they hand the kernels, which LDS ring a launch gets, when a host call with pinned buffers runs in sub-batches and how
 // large those are, when k_inflate_par runs before k_inflate, when the span pool is given back, and how a host caller's
-// output comes home.  Plain C++ (no HIP types): flate_hip.hip uses it, tests/cpu_shim compiles it for the CPU tests.
+// output comes home -- and of the resumable inflater's host feeds (flate_hip_inflater_feed): which slots it takes, the
+// offsets it stages, how the produced bytes come home.  Plain C++ (no HIP types): flate_hip.hip uses it, tests/cpu_shim
+// compiles it for the CPU tests.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -146,3 +148,35 @@ inline fl_copy_out fl_copy_out_plan(const uint64_t* hout, const uint64_t* out_le
         if (out_len[i]) p.end = std::max(p.end, hout[i] + out_len[i]);
     return p;
 }
+
+// ---- the resumable inflater's host feeds (flate_hip_inflater_feed with FLATE_HIP_MEM_HOST)
+
+#define FL_INFLATER_MIN_SLOT 258u      // a slot is empty or at least the longest match: such a feed always makes progress
+#define FL_INFLATER_COPY_EACH_MAX 16u  // up to this many streams, each stream's bytes come home by a copy of their own
+
+// The caller's tables (n + 1 offsets each, n final flags): the offsets ascend, and the slot of a stream that is not
+// skipped -- an empty piece, final 0 and an empty slot -- is empty or at least FL_INFLATER_MIN_SLOT bytes.
+inline bool fl_inflater_slots_ok(const uint64_t* in_off, const uint64_t* out_off, const uint8_t* final_, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        if (in_off[i + 1] < in_off[i] || out_off[i + 1] < out_off[i]) return false;
+        const uint64_t slot = out_off[i + 1] - out_off[i];
+        const bool skipped = in_off[i + 1] == in_off[i] && !final_[i] && slot == 0;
+        if (!skipped && slot > 0 && slot < FL_INFLATER_MIN_SLOT) return false;
+    }
+    return true;
+}
+
+// The pieces and the slots are staged from their first byte: the offsets the kernel sees start at 0
+inline void fl_inflater_rebase(const uint64_t* in_off, const uint64_t* out_off, uint32_t n, std::vector<uint64_t>& hin,
+                               std::vector<uint64_t>& hout) {
+    hin.resize((size_t)n + 1);
+    hout.resize((size_t)n + 1);
+    for (uint32_t i = 0; i <= n; i++) {
+        hin[i] = in_off[i] - in_off[0];
+        hout[i] = out_off[i] - out_off[0];
+    }
+}
+
+// Only the produced bytes reach the caller's slots (what lies beyond out_len[i] stays as it was): a few streams by a
+// copy each from the device, many by one copy of all slots to the host and a memcpy of each stream's bytes from there.
+inline bool fl_inflater_copy_each(uint32_t n) { return n <= FL_INFLATER_COPY_EACH_MAX; }

@@ -17,18 +17,7 @@ struct fl_dfl_state {
     uint32_t carry_nbits;  // ... and how many of its bits are written (0..7)
 };
 
-// per stream fed in this call (host-built)
-struct fl_dfl_job {
-    uint64_t src_off;   // the piece in the feed's source buffer
-    uint32_t stream;    // index of the stream in the deflater
-    uint32_t bl;        // buffered bytes carried from the last feed (< 65535), staged before the piece
-    uint32_t n;         // bytes of the piece
-    uint32_t keep;      // bytes at the end of the staged input that stay buffered
-    uint32_t ck_first;  // the piece's checksum units in the checksum tables ...
-    uint32_t ck_n;      // ... and how many
-    uint32_t hdr;       // 1: the container header goes out first
-    uint32_t finish;    // 1: final block and footer
-};
+// (fl_dfl_job, what the host builds per stream fed in this call: deflater_plan.h)
 
 // buffered bytes + piece -> in[chunk.in_off ..): a grid of (jobs, slices), every thread one aligned 16-byte unit
 __global__ __launch_bounds__(256) void k_deflater_stage(const uint8_t* __restrict__ src, const fl_dfl_job* __restrict__ jobs,

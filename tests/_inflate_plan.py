@@ -1,6 +1,7 @@
 """ctypes binding of tests/cpu_shim/inflate_plan_shim.cpp: the host decisions of the inflate entry points
 (flate_amd/csrc/inflate_plan.h) as the library computes them -- the chunk table, the LDS ring, the pinned sub-batches, the
-k_inflate_par rule, the span pool's bound, the copy-out plan.  TEST INFRASTRUCTURE ONLY."""
+k_inflate_par rule, the span pool's bound, the copy-out plan, the rules of the resumable inflater's host feeds.  TEST
+INFRASTRUCTURE ONLY."""
 import ctypes as C
 import os
 import subprocess
@@ -41,6 +42,9 @@ def lib():
         L.shim_inflate_chunks.argtypes = [p, p, u32, u64, u64, p]
         L.shim_inflate_pool_release.argtypes = [u64]
         L.shim_copy_out_plan.argtypes = [p, p, u32, p]
+        L.shim_inflater_slots_ok.argtypes = [p, p, p, u32]
+        L.shim_inflater_rebase.argtypes = [p, p, u32, p, p]
+        L.shim_inflater_copy_each.argtypes = [u32]
         _lib = L
     return _lib
 
@@ -114,3 +118,21 @@ def copy_out(hout, out_len):
     out = np.zeros(2, np.uint64)
     kind = lib().shim_copy_out_plan(a.ctypes.data, b.ctypes.data, len(hout) - 1, out.ctypes.data)
     return kind, int(out[0]), int(out[1])
+
+
+def inflater_slots_ok(in_off, out_off, final):
+    a, b, c = _u64(in_off), _u64(out_off), np.ascontiguousarray(np.array(list(final), np.uint8))
+    assert len(in_off) == len(out_off) == len(final) + 1
+    return bool(lib().shim_inflater_slots_ok(a.ctypes.data, b.ctypes.data, c.ctypes.data, len(final)))
+
+
+def inflater_rebase(in_off, out_off):
+    """(hin, hout): the offsets the staged copies are read with"""
+    a, b = _u64(in_off), _u64(out_off)
+    hin, hout = np.zeros(len(in_off), np.uint64), np.zeros(len(out_off), np.uint64)
+    assert lib().shim_inflater_rebase(a.ctypes.data, b.ctypes.data, len(in_off) - 1, hin.ctypes.data, hout.ctypes.data) == 1
+    return [int(x) for x in hin], [int(x) for x in hout]
+
+
+def inflater_copy_each(n_streams):
+    return bool(lib().shim_inflater_copy_each(n_streams))

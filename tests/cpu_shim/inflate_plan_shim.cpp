@@ -1,6 +1,7 @@
 // CPU build of the inflate entry points' host decisions (flate_amd/csrc/inflate_plan.h).
 // TEST INFRASTRUCTURE ONLY: lets the chunk table, the ring rule, the pinned sub-batches, the k_inflate_par rule, the span
-// pool's bound and the copy-out plan be checked without a GPU.  Not linked into libflate_hip.so.
+// pool's bound, the copy-out plan and the rules of the resumable inflater's host feeds be checked without a GPU.  Not linked
+// into libflate_hip.so.
 #include "../../flate_amd/csrc/inflate_plan.h"
 
 #include <cstring>
@@ -69,5 +70,22 @@ int shim_copy_out_plan(const uint64_t* hout, const uint64_t* out_len, uint32_t n
     out[1] = p.end;
     return p.kind;
 }
+
+// ---- the resumable inflater's host feeds
+int shim_inflater_slots_ok(const uint64_t* in_off, const uint64_t* out_off, const uint8_t* final_, uint32_t n) {
+    return fl_inflater_slots_ok(in_off, out_off, final_, n) ? 1 : 0;
+}
+
+// hin, hout: n + 1 entries each; returns 0 where the tables do not come back with that length
+int shim_inflater_rebase(const uint64_t* in_off, const uint64_t* out_off, uint32_t n, uint64_t* hin, uint64_t* hout) {
+    std::vector<uint64_t> a(3, 77), b;  // (what they held must go)
+    fl_inflater_rebase(in_off, out_off, n, a, b);
+    if (a.size() != (size_t)n + 1 || b.size() != (size_t)n + 1) return 0;
+    memcpy(hin, a.data(), 8 * a.size());
+    memcpy(hout, b.data(), 8 * b.size());
+    return 1;
+}
+
+int shim_inflater_copy_each(uint32_t n) { return fl_inflater_copy_each(n) ? 1 : 0; }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 // their stream.  Built with -fsanitize=address,undefined by tests/test_host_cpp.py; needs no GPU.  It checks invariants --
 // the sub-batches partition [0, n), the members a table is accepted with are a contiguous ascending cover of the input
 // range and of the slots, a table's capacity is never below what it holds, every index handed out is inside its array --
-// not what the rules decide (tests/test_inflate_plan_cpu.py and tests/test_members_cpu.py do).
+// not what the rules decide (tests/test_inflate_plan_cpu.py and tests/test_members_cpu.py do).  The resumable inflater's host
+// feeds are walked too: tables that go back, slots around the least one, and the rebased tables of those that are accepted.
 #include <cstdio>
 #include <cstdlib>
 
@@ -185,11 +186,38 @@ static int walk_members(int set_no) {
     return 0;
 }
 
+// ---- a host feed of the resumable inflater: tables that ascend or go back, slots around the least one
+static int walk_inflater_feed(int set_no) {
+    const uint32_t n = (uint32_t)below(40);
+    std::vector<uint64_t> in_off(n + 1ull), out_off(n + 1ull), hin, hout;
+    std::vector<uint8_t> fin(n + 1ull);
+    in_off[0] = below(2) ? below(1ull << 40) : ~0ull - (1ull << 30);
+    out_off[0] = below(2) ? below(1ull << 40) : ~0ull - (1ull << 30);
+    bool good = true;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t piece = below(3) ? below(100000) : 0, slot = below(3) ? FL_INFLATER_MIN_SLOT + below(100000) : below(8) ? 0 : 1 + below(257);
+        in_off[i + 1] = below(50) ? in_off[i] + piece : in_off[i] - 1 - below(1000);
+        out_off[i + 1] = below(50) ? out_off[i] + slot : out_off[i] - 1 - below(1000);
+        fin[i] = (uint8_t)below(2);
+        const uint64_t s = out_off[i + 1] - out_off[i];
+        good = good && in_off[i + 1] >= in_off[i] && out_off[i + 1] >= out_off[i] && (s == 0 || s >= FL_INFLATER_MIN_SLOT);
+    }
+    CHECK(fl_inflater_slots_ok(in_off.data(), out_off.data(), fin.data(), n) == good);
+    CHECK(fl_inflater_copy_each(n) == (n <= 16));
+    if (!good) return 0;
+    fl_inflater_rebase(in_off.data(), out_off.data(), n, hin, hout);
+    CHECK(hin.size() == n + 1ull && hout.size() == n + 1ull && hin[0] == 0 && hout[0] == 0);
+    for (uint32_t i = 0; i < n; i++)  // the same pieces and slots, inside the staged copies
+        CHECK(hin[i + 1] - hin[i] == in_off[i + 1] - in_off[i] && hout[i + 1] - hout[i] == out_off[i + 1] - out_off[i] &&
+              hin[i + 1] <= in_off[n] - in_off[0] && hout[i + 1] <= out_off[n] - out_off[0]);
+    return 0;
+}
+
 int main() {
     for (int set_no = 0; set_no < 40; set_no++)
         if (walk_counts(set_no)) return 1;
     for (int set_no = 0; set_no < 3000; set_no++)
-        if (walk_batch(set_no) || walk_members(set_no)) return 1;
+        if (walk_batch(set_no) || walk_members(set_no) || walk_inflater_feed(set_no)) return 1;
     if (tables_refused == 0 || tables_refused == tables_seen) {
         printf("no mix of good and hostile tables: %llu of %llu refused\n", (unsigned long long)tables_refused, (unsigned long long)tables_seen);
         return 1;

@@ -352,6 +352,52 @@ def test_device_memory_feeds(mode):
         assert pyzlib.decompress(bytes(outs[i])) == datas[i]
 
 
+def _raw_feed(eng, d, device, blob, in_off, ops, out_off):
+    """flate_hip_deflater_feed as it is, on host or device memory -> (return code, outputs, statuses, consumed)"""
+    from flate_amd._capi import MEM_DEVICE, MEM_HOST
+    n = len(ops)
+    arrs = [np.frombuffer(blob, dtype=np.uint8).copy(), np.array(in_off, dtype=np.uint64), np.array(ops, dtype=np.uint8),
+            np.zeros(max(out_off), dtype=np.uint8), np.array(out_off, dtype=np.uint64), np.zeros(n, dtype=np.uint64),
+            np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32)]
+    if device:
+        import torch
+        ts = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to("cuda:0") for a in arrs]
+        rc = eng._L.flate_hip_deflater_feed(eng._h, d._d, *[t.data_ptr() for t in ts], MEM_DEVICE)
+        torch.cuda.synchronize()
+        out, _, ln, cons, st = [t.cpu().numpy() for t in ts[3:]]
+    else:
+        rc = eng._L.flate_hip_deflater_feed(eng._h, d._d, *[a.ctypes.data for a in arrs], MEM_HOST)
+        out, _, ln, cons, st = arrs[3:]
+    return rc, [out[int(out_off[i]): int(out_off[i]) + int(ln[i])].tobytes() for i in range(n)], st.tolist(), cons.tolist()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_a_refused_feed_touches_nothing(mode, device):
+    """three streams that each cross a block; between two valid feeds, a feed with an op above FINISH and a feed whose
+    offsets go back are refused as a whole, and the streams still come out as the one-shot call's"""
+    from flate_amd._capi import E_INVALID_ARG
+    eng = engine()
+    datas = [_text(70000, seed=60 + i) for i in range(3)]
+    want, _ = eng.compress_many(datas, O.GZIP, mode)
+    cut = 30000
+    first, rest = b"".join(x[:cut] for x in datas), b"".join(x[cut:] for x in datas)
+    off1, off2 = [0, cut, 2 * cut, 3 * cut], [0, 40000, 80000, 120000]
+    slots = [0, 80000, 160000, 240000]
+    d = eng.deflater(3, O.GZIP, mode)
+    try:
+        rc, outs, st, cons = _raw_feed(eng, d, device, first, off1, [MORE] * 3, slots)
+        assert rc == 0 and st == [NEED_INPUT] * 3 and cons == [cut] * 3
+        assert _raw_feed(eng, d, device, rest, off2, [FINISH, 3, FINISH], slots)[0] == E_INVALID_ARG
+        assert _raw_feed(eng, d, device, rest, [0, 80000, 40000, 120000], [FINISH] * 3, slots)[0] == E_INVALID_ARG
+        rc, outs2, st, cons = _raw_feed(eng, d, device, rest, off2, [FINISH] * 3, slots)
+        assert rc == 0 and st == [0] * 3 and cons == [40000] * 3
+    finally:
+        d.close()
+    for i in range(3):
+        assert outs[i] + outs2[i] == want[i], i
+
+
 @pytest.mark.parametrize("mode", [O.HUFFMAN, O.STORE])
 def test_gzip_stream_beyond_4_gib(mode):
     """4.5 GiB in 64 MiB device pieces, each stamped with its index: zlib inflates every piece back and checks CRC-32

@@ -66,11 +66,30 @@ def test_inflate_plan_under_the_sanitizers():
     empty stream, a first start that is not 0, starts that go backwards or lie beyond their stream) through every rule of
     flate_amd/csrc/inflate_plan.h and through the host's side of flate_amd/csrc/member_plan.h.  It checks that the sub-batches
     partition [0, n), that the members of an accepted table are a contiguous ascending cover of the input range and of the
-    slots, that a refused table names the stream that was spoilt, and that a table's capacity is never below what it holds;
+    slots, that a refused table names the stream that was spoilt, that a table's capacity is never below what it holds, and
+    that the tables a host feed of the resumable inflater stages describe the caller's pieces and slots from 0;
     what the rules decide is the business of tests/test_inflate_plan_cpu.py and tests/test_members_cpu.py."""
     src = os.path.join(ROOT, "tests", "host_cpp", "test_inflate_plan.cpp")
     exe = os.path.join(ROOT, "tests", "host_cpp", "test_inflate_plan")
     deps = [src] + [os.path.join(ROOT, "flate_amd", "csrc", h) for h in ("inflate_plan.h", "member_plan.h", "flate_layout.h", "flate_common.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-o", exe, src],
+                       check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ok" in r.stdout
+
+
+def test_deflater_plan_under_the_sanitizers():
+    """tests/host_cpp/test_deflater_plan.cpp: a program of its own, built with AddressSanitizer and UBSan, that hands the feed
+    check of flate_amd/csrc/deflater_plan.h hostile tables (offsets near 2^64, offsets that go back, ops 3..255, pieces at the
+    limit and one byte above it), lays out what it accepts, and drives routing, layout and settle through random valid
+    sessions.  It checks that a table is accepted exactly when it may be, that every index of a layout is inside its table
+    and its staged regions are aligned and disjoint, and that every produced byte is handed out once; what the rules decide
+    is tests/test_deflater_cpu.py's business."""
+    src = os.path.join(ROOT, "tests", "host_cpp", "test_deflater_plan.cpp")
+    exe = os.path.join(ROOT, "tests", "host_cpp", "test_deflater_plan")
+    deps = [src] + [os.path.join(ROOT, "flate_amd", "csrc", h) for h in ("deflater_plan.h", "flate_layout.h", "flate_common.h")]
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
         subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-o", exe, src],
                        check=True)

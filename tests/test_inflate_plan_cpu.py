@@ -1,6 +1,6 @@
 """The host decisions of the inflate entry points (flate_amd/csrc/inflate_plan.h) on the CPU: the chunk table, which LDS
 ring a launch gets, when a pinned host call runs in sub-batches and how large they are, when k_inflate_par runs, when the
-span pool is given back, and how a host caller's output comes home.  The shim (tests/cpu_shim/inflate_plan_shim.cpp) is
+span pool is given back, how a host caller's output comes home, and the rules of the resumable inflater's host feeds.  The shim (tests/cpu_shim/inflate_plan_shim.cpp) is
 built the way tests/test_span_plan_cpu.py builds its own, without a sanitizer; tests/host_cpp/test_inflate_plan.cpp runs the
 same functions over random and hostile inputs under AddressSanitizer and UBSan (tests/test_host_cpp.py).  No GPU.
 
@@ -146,3 +146,38 @@ def test_copy_out_end_from_a_middle_slot():
     # the last slot produced nothing: the copy ends with the middle one's bytes
     assert P.copy_out([0, 100, 200, 210], [5, 100, 0]) == (P.DENSE, 105, 200)
     assert P.copy_out([0, 100, 200, 210], [100, 5, 0]) == (P.DENSE, 105, 105)
+
+
+# ---------------------------------------------------------------- the resumable inflater's host feeds
+
+def test_inflater_slot_of_a_stream_is_empty_or_holds_the_longest_match():
+    piece = [10, 15]                                                # five bytes go in
+    assert P.inflater_slots_ok(piece, [0, 0], [0]) is True          # no room: allowed, nothing comes out
+    assert P.inflater_slots_ok(piece, [0, 1], [0]) is False
+    assert P.inflater_slots_ok(piece, [0, 257], [0]) is False
+    assert P.inflater_slots_ok(piece, [0, 258], [0]) is True
+    assert P.inflater_slots_ok(piece, [40, 40 + 257], [1]) is False
+    assert P.inflater_slots_ok(piece, [40, 40 + 258], [1]) is True
+    # an empty piece is a feed all the same when it is final or has a slot
+    assert P.inflater_slots_ok([10, 10], [0, 1], [0]) is False
+    assert P.inflater_slots_ok([10, 10], [0, 0], [1]) is True
+    # a skipped stream (empty piece, not final, empty slot) among others: exempt, and the others are still checked
+    assert P.inflater_slots_ok([10, 10, 15], [0, 0, 300], [0, 0]) is True
+    assert P.inflater_slots_ok([10, 10, 15], [0, 0, 257], [0, 0]) is False
+    assert P.inflater_slots_ok([10, 15, 15], [0, 257, 257], [0, 0]) is False
+
+
+def test_inflater_offsets_must_ascend():
+    assert P.inflater_slots_ok([10, 9], [0, 300], [0]) is False
+    assert P.inflater_slots_ok([10, 15, 20], [0, 300, 299], [0, 0]) is False
+    assert P.inflater_slots_ok([7], [9], []) is True
+
+
+def test_inflater_copy_home_choice():
+    assert [P.inflater_copy_each(n) for n in (1, 16, 17, 0xffffffff)] == [True, True, False, False]
+
+
+def test_inflater_rebased_tables():
+    assert P.inflater_rebase([100, 150, 150, 400], [1000, 1258, 1258, 5000]) == ([0, 50, 50, 300], [0, 258, 258, 4000])
+    assert P.inflater_rebase([0, 5], [0, 300]) == ([0, 5], [0, 300])
+    assert P.inflater_rebase([1 << 40], [7]) == ([0], [0])
